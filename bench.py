@@ -24,6 +24,12 @@ config 5 the whole step's workload; `--weak` keeps round 1's mode (the framebuff
 
 value = nominal samples of all ranks per step / step time, in Msamples/s (nominal sample = one loop iteration of
 PerformWindowedLitRaymarch that geometry prescribes, independent of early termination and skipping).
+
+A plain run does only what `value` and `ms_per_step` need: setup, --warmup steps, --steps timed steps, the result line. Everything
+else the line can carry (the event-timed gpu_ms pass, the other operators' timings, the roofline, the CPU oracle baseline and the
+full-size parity, the N>1 checks of the gathered frame and the slab light volume, the one-GPU comparison, frame_delivery /
+tile_parallel) runs with --full; in a plain run those keys are null. --dump-outputs DIR writes what the last timed step computed
+(the frame and a seeded sample of the light volume, float32 .npy) for output-for-output comparison of two builds.
 """
 import argparse
 import json
@@ -116,6 +122,30 @@ def committed_counters(kind, per_step):
         if have is None or abs(have - want) > 0.15 * max(want, 1.0):
             return None, f"{rel} was collected with {want:.2f} {key} launches per step, this run made {have}: not quoted"
     return data, rel
+
+
+# --dump-outputs: at most this many float32 values per array (32 MiB + 16 MiB: the dump stays under 64 MB); larger arrays are
+# written as a fixed, seeded sample of their elements
+DUMP_MAX_VALUES = {"frame": 1 << 23, "light_volume": 1 << 22}
+DUMP_SEED = 0x5EED0D0
+
+
+def dump_outputs(path, arrays):
+    """Every array as path/<name>.npy in float32 (exact for the RGBA f32 frame and for UNORM8 codes or f32 light values). An
+    array with more elements than DUMP_MAX_VALUES allows is written as path/<name>_sample.npy: the elements at flat indices
+    drawn without replacement by a generator seeded with DUMP_SEED, in increasing index order (the same indices in every run
+    of the same shape). Returns {file name: shape}."""
+    os.makedirs(path, exist_ok=True)
+    written = {}
+    for name, arr in arrays.items():
+        arr = np.asarray(arr)
+        cap = DUMP_MAX_VALUES[name]
+        if arr.size > cap:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(arr.size, cap, replace=False))
+            arr, name = arr.reshape(-1)[idx], name + "_sample"
+        np.save(os.path.join(path, name + ".npy"), arr.astype(np.float32))
+        written[name + ".npy"] = list(arr.shape)
+    return written
 
 
 def gpu_ms(torch, stream, fn):
@@ -257,6 +287,13 @@ def main():
                     help="N>1, BASELINE config 4's decomposition taken literally: every GPU holds only its z slab of the data and "
                          "light volumes (tbrm_resources_create_slab); a step = slab-partitioned ChangeDirLight + light-volume halo "
                          "exchange + the frame marched slab by slab (strong scaling: one frame of the config's size)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: the event-timed gpu_ms pass, the other operators' "
+                         "timings, the roofline, the CPU baseline + full-size parity (unless --no-cpu-baseline), the N>1 frame / slab checks, "
+                         "the one-GPU comparison and frame_delivery / tile_parallel. Off: setup, warm-up, timed steps, result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32): the frame rank 0 holds "
+                         "(frame.npy; a seeded sample when larger than 2^23 values) and a seeded sample of the light volume")
     args = ap.parse_args()
     if args.config is None:
         args.config = 3
@@ -376,11 +413,13 @@ def main():
         reset_all_lights()  # first call: includes the brick metadata kernels (the buffers were reserved above)
         res.flush()
     reset_ms = (time.perf_counter() - t0) * 1e3
-    t0 = time.perf_counter()
-    if not (args.light_parallel_reset and dist is not None and not cfg["light_32bit"]):
-        reset_all_lights()
-        res.flush()
-    reset_warm_wall_ms = (time.perf_counter() - t0) * 1e3
+    reset_warm_wall_ms = None
+    if args.full:  # (the second reset is a measurement: it leaves the same light volume as the first)
+        t0 = time.perf_counter()
+        if not (args.light_parallel_reset and dist is not None and not cfg["light_32bit"]):
+            reset_all_lights()
+            res.flush()
+        reset_warm_wall_ms = (time.perf_counter() - t0) * 1e3
 
     # Two output tiles / gather buffers: the all-gather of frame k runs (asynchronously, on RCCL's stream) while the light
     # update of frame k+1 is already executing on the library's stream; a buffer is reused only after its gather is done.
@@ -536,9 +575,17 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    # ---- --dump-outputs: what the last timed step computed, before anything below runs another operator ----
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        from tbraymarcherplugin_amd import sharding
+
+        frame_out = sharding.assemble(gathered, fb_h, n_gpus) if gathered is not None else out
+        dumped = dump_outputs(args.dump_outputs, {"frame": frame_out.cpu().numpy(), "light_volume": res.download_light_volume()})
+
     # ---- N>1: the assembled frame must equal this rank's own render of the whole framebuffer (untimed check) ----
     gather_ok = None
-    if dist is not None:
+    if dist is not None and args.full:
         from tbraymarcherplugin_amd import sharding
 
         full = torch.empty((fb_h, fb_w, 4), dtype=torch.float32, device=device)
@@ -551,8 +598,8 @@ def main():
             print(f"[rank {rank}] frame-full max|d| = {float((frame - full).abs().max())}, own tile vs own full: "
                   f"{bool(torch.equal(out, full[rows]))}, gathered[rank] vs out: {bool(torch.equal(gathered[rank], out))}", flush=True)
 
-    # ---- per-kernel GPU time with HIP events on the library's stream (separate, untimed pass) -------------
-    n_event = max(3, min(args.steps, 20))
+    # ---- per-kernel GPU time with HIP events on the library's stream (separate, untimed pass; --full) -------------
+    n_event = max(3, min(args.steps, 20)) if args.full else 0
     for k in range(n_event):
         one_step(args.warmup + args.steps + k, True)
     for h in pending:
@@ -580,7 +627,7 @@ def main():
 
     # ---- slab mode: the partitioned + gathered light volume must equal the unpartitioned operator's (untimed replay) ----
     slab_ok = None
-    if slab_member is not None and not args.raymarch_only:
+    if slab_member is not None and not args.raymarch_only and args.full:
         from tbraymarcherplugin_amd import sharding
 
         res.flush()
@@ -612,7 +659,7 @@ def main():
     # Every rank runs the same operators, so the replicated light volumes stay identical.
     ops_ms = {}
     one_gpu = None
-    if not args.raymarch_only and slab_member is None and not args.timed_only:
+    if not args.raymarch_only and slab_member is None and not args.timed_only and args.full:
         res.flush()
         full_tile = abi.Tile(0, 0, fb_w, fb_h, 1)
         full = torch.empty((fb_h, fb_w, 4), dtype=torch.float32, device=device)
@@ -715,7 +762,7 @@ def main():
     # frame_delivery: this run's workload (config 3 by default). tile_parallel: north_star's tile-scaling workload, config 5
     # (512^3, ONE 2048^2 frame, 8 lights, TF-B) at this N and on one GPU in the same run — the number "tile-parallel scaling" is about.
     delivery = tile_parallel = None
-    if dist is not None and slab_member is None and not args.timed_only and not args.weak:
+    if dist is not None and slab_member is None and not args.timed_only and not args.weak and args.full:
         k_frames = max(5, min(args.steps, 20))
         delivery = frame_delivery(torch, dist, abi, res, cam, fb_w, fb_h, rp, world, rank, n_gpus, device, lib_stream, one_gpu_dry_run, k_frames, total_samples)
         delivery["workload"] = f"config {args.config}"
@@ -744,52 +791,54 @@ def main():
                 res5.close()
                 del vol5
 
-    # ---- roofline of the dominant kernel (algorithmic bytes) -------------------------------
-    b_data = np.dtype(cfg["dtype"]).itemsize
-    b_light = 4 if cfg["light_32bit"] else 1
-    V = n ** 3
-    ray_bytes = V * b_data + V * b_light + fb_w * rows_per_rank * 16 + 2048
-    pass_bytes = V * b_data + 2 * V * b_light
-    illum_bytes = 2 * pass_bytes  # fused Change = 2 axis passes
-    if ray_ms >= illum_ms:
-        dom = dict(kernel="k_raymarch_lit", achieved=ray_bytes / (ray_ms * 1e-3) / 1e9, launch_ms=ray_ms, alg_bytes=ray_bytes)
-    else:
-        dom = dict(kernel="k_light_occlusion+k_light_sweep (one ChangeDirLight = 2 axis passes)",
-                   achieved=illum_bytes / (illum_ms * 1e-3) / 1e9, launch_ms=illum_ms, alg_bytes=illum_bytes)
-    # HBM traffic from the PMC counters (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this same command,
-    # summarised by tools/pmc_traffic.py into profiles/): per launch of the raymarch kernel, or summed over the launches
-    # one ChangeDirLight makes (tools/pmc_traffic.py "_per_operator_call")
-    traffic = None
-    traffic_source = None
-    per_step = {"k_light_sweep": light_paths["launches_sweep"], "k_light_occlusion": light_paths["occlusion_single"] + light_paths["occlusion_dual"],
-                "k_raymarch_lit": light_paths["raymarch"]}
-    if args.config == 3 and n_gpus == 1 and not args.raymarch_only:
-        pmc, traffic_source = committed_counters("pmc_traffic", per_step)
-        if pmc is not None:
-            per_call = pmc["_per_operator_call"]
-            traffic = int(per_call["raymarch_hbm_bytes"] if dom["kernel"].startswith("k_raymarch") else per_call["change_dir_light_hbm_bytes"])
-            traffic_source += (": separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command (tools/measure_round.sh), NOT measured in "
-                               "this run; checked against this run's kernel sources and launches per step")
-    # why the fraction is what it is: the instruction-issue view of the hot kernels (tools/issue_roofline.py over two more
-    # --pmc passes of this command; committed numbers, like the traffic, under the same check)
-    issue = None
-    if args.config == 3 and n_gpus == 1 and not args.raymarch_only:
-        raw, where = committed_counters("issue", per_step)
-        if raw is not None:
-            issue = {k: {kk: vv for kk, vv in v.items() if kk != "per_launch"} for k, v in raw.items() if not k.startswith("_")}
-            issue["source"] = (where + ": rocprofv3 --pmc SQ_INSTS_VALU / SQ_INSTS_SALU / SQ_WAVE_CYCLES / SQ_WAIT_INST_ANY / "
-                               "SQ_ACTIVE_INST_LDS / GRBM_GUI_ACTIVE passes of this command (tools/measure_round.sh), NOT measured in this run; "
-                               "valu_issue_frac = SQ_INSTS_VALU x 4 / (1024 SIMDs x GRBM_GUI_ACTIVE)")
+    # ---- roofline of the dominant kernel (algorithmic bytes; --full) ---------------------------
+    roofline = issue = None
+    if args.full:
+        b_data = np.dtype(cfg["dtype"]).itemsize
+        b_light = 4 if cfg["light_32bit"] else 1
+        V = n ** 3
+        ray_bytes = V * b_data + V * b_light + fb_w * rows_per_rank * 16 + 2048
+        pass_bytes = V * b_data + 2 * V * b_light
+        illum_bytes = 2 * pass_bytes  # fused Change = 2 axis passes
+        if ray_ms >= illum_ms:
+            dom = dict(kernel="k_raymarch_lit", achieved=ray_bytes / (ray_ms * 1e-3) / 1e9, launch_ms=ray_ms, alg_bytes=ray_bytes)
         else:
-            issue = {"source": where}
-    roofline = {"bound": "hbm", "kernel": dom["kernel"], "achieved": round(dom["achieved"], 2), "peak": HBM_PEAK / 1e9,
-                "unit": "GB/s", "frac": round(dom["achieved"] * 1e9 / HBM_PEAK, 5), "traffic": traffic, "traffic_source": traffic_source,
-                "alg_bytes_per_launch": int(dom["alg_bytes"]), "launch_ms": round(dom["launch_ms"], 4),
-                "launch_ms_is": f"plain mean of {len(ms_ray)} event-timed calls (gpu_ms_spread lists every call)"}
+            dom = dict(kernel="k_light_occlusion+k_light_sweep (one ChangeDirLight = 2 axis passes)",
+                       achieved=illum_bytes / (illum_ms * 1e-3) / 1e9, launch_ms=illum_ms, alg_bytes=illum_bytes)
+        # HBM traffic from the PMC counters (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this same command,
+        # summarised by tools/pmc_traffic.py into profiles/): per launch of the raymarch kernel, or summed over the launches
+        # one ChangeDirLight makes (tools/pmc_traffic.py "_per_operator_call")
+        traffic = None
+        traffic_source = None
+        per_step = {"k_light_sweep": light_paths["launches_sweep"], "k_light_occlusion": light_paths["occlusion_single"] + light_paths["occlusion_dual"],
+                    "k_raymarch_lit": light_paths["raymarch"]}
+        if args.config == 3 and n_gpus == 1 and not args.raymarch_only:
+            pmc, traffic_source = committed_counters("pmc_traffic", per_step)
+            if pmc is not None:
+                per_call = pmc["_per_operator_call"]
+                traffic = int(per_call["raymarch_hbm_bytes"] if dom["kernel"].startswith("k_raymarch") else per_call["change_dir_light_hbm_bytes"])
+                traffic_source += (": separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command (tools/measure_round.sh), NOT measured in "
+                                   "this run; checked against this run's kernel sources and launches per step")
+        # why the fraction is what it is: the instruction-issue view of the hot kernels (tools/issue_roofline.py over two more
+        # --pmc passes of this command; committed numbers, like the traffic, under the same check)
+        issue = None
+        if args.config == 3 and n_gpus == 1 and not args.raymarch_only:
+            raw, where = committed_counters("issue", per_step)
+            if raw is not None:
+                issue = {k: {kk: vv for kk, vv in v.items() if kk != "per_launch"} for k, v in raw.items() if not k.startswith("_")}
+                issue["source"] = (where + ": rocprofv3 --pmc SQ_INSTS_VALU / SQ_INSTS_SALU / SQ_WAVE_CYCLES / SQ_WAIT_INST_ANY / "
+                                   "SQ_ACTIVE_INST_LDS / GRBM_GUI_ACTIVE passes of this command (tools/measure_round.sh), NOT measured in this run; "
+                                   "valu_issue_frac = SQ_INSTS_VALU x 4 / (1024 SIMDs x GRBM_GUI_ACTIVE)")
+            else:
+                issue = {"source": where}
+        roofline = {"bound": "hbm", "kernel": dom["kernel"], "achieved": round(dom["achieved"], 2), "peak": HBM_PEAK / 1e9,
+                    "unit": "GB/s", "frac": round(dom["achieved"] * 1e9 / HBM_PEAK, 5), "traffic": traffic, "traffic_source": traffic_source,
+                    "alg_bytes_per_launch": int(dom["alg_bytes"]), "launch_ms": round(dom["launch_ms"], 4),
+                    "launch_ms_is": f"plain mean of {len(ms_ray)} event-timed calls (gpu_ms_spread lists every call)"}
 
     # ---- CPU baseline: the oracle on this host's cores, rank 0, N=1 only, bounded sample -------------------
     cpu = parity = None
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline and args.full:
         moved = abi.DirLightParams(S.rotate_z(light_dirs[0], angle[0] + 5.0), lights[0].light_intensity)
         cpu, parity = cpu_baseline(args, cfg, res, vol_dev, lut, win, world, cam, rp, fb_w, fb_h, lights[0], moved)
 
@@ -829,16 +878,16 @@ def main():
                            # host wall clock, call to flush: the handle's first ResetAllLights (skipping metadata kernels inside; buffers
                            # reserved before it), the second one, and tbrm_resources_reserve itself
                            first_reset_all_lights_host_wall=round(reset_ms, 2), second_reset_all_lights_host_wall=round(reset_warm_wall_ms, 2),
-                           resources_reserve_host_wall=round(reserve_ms, 2)),
-            "gpu_ms_spread": spread,
+                           resources_reserve_host_wall=round(reserve_ms, 2)) if args.full else None,
+            "gpu_ms_spread": spread if args.full else None,
             "distributed": None if dist is None else {
                 "backend": dist.get_backend(), "world_size_seen": dist.get_world_size(), "ms_per_step_per_rank": per_rank_ms,
                 "light_update": args.light_update if slab_member is None else "slabs",
                 # what the tiles alone gain (the part of a step that shards), next to the whole step's figure in scaling_detail
-                "raymarch_ms_this_rank": round(ray_ms, 4)},
+                "raymarch_ms_this_rank": round(ray_ms, 4) if args.full else None},
             "timed_loop_records_gpu_timing_events": bool(timing_in_loop),
             "light_paths_per_step": light_paths,  # tbrm_path_counters over the timed loop: sweep / chain / slice passes and launches, occlusion launches
-            "raymarch_only_msamples_per_s": round(total_samples / (ray_ms * 1e-3) / 1e6, 2),
+            "raymarch_only_msamples_per_s": round(total_samples / (ray_ms * 1e-3) / 1e6, 2) if args.full else None,
             "light_cache": res.light_cache_stats(),  # factor cache (include/tbrm.h tbrm_light_cache_stats)
             # gpu_ms.reset_all_lights_batched_*: what tbrm_add_dir_lights made of this scene's lights
             "reset_batching": None if not ops_ms else dict(batch_info, note=(
@@ -856,6 +905,8 @@ def main():
             "roofline_issue": issue,
             "cpu_baseline": cpu,
             "full_size_parity": parity,
+            "full": bool(args.full),  # False: the keys that only --full measures or checks are null
+            "outputs_dumped": dumped,  # --dump-outputs: {file name: shape}
         }
         print(json.dumps(line), flush=True)
     res.close()
@@ -883,7 +934,7 @@ def slab_resident_bench(args, torch, dist, S, abi, rank, local_rank, n_gpus, dev
     res.upload_volume_slices(dlo, vol_dev[dlo:dhi].cpu().numpy())
     if dwrap >= 0:
         res.upload_volume_slices(dwrap, vol_dev[dwrap:dwrap + 8].cpu().numpy())
-    keep_whole = rank == 0  # rank 0 keeps the whole volume for the untimed check at the end
+    keep_whole = rank == 0 and args.full  # rank 0 keeps the whole volume for the untimed check at the end (--full)
     if not keep_whole:
         del vol_dev
     lut = abi.color_curve_to_lut(S.tf_keys(cfg["tf"]))
@@ -953,9 +1004,14 @@ def slab_resident_bench(args, torch, dist, S, abi, rank, local_rank, n_gpus, dev
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
 
-    # untimed check on rank 0: one whole handle replays the lights and renders the last frame
+    dumped = None
+    if args.dump_outputs and rank == 0:  # the frame (rank 0 holds the whole one) and rank 0's slab of the light volume
+        res.flush()
+        dumped = dump_outputs(args.dump_outputs, {"frame": frame[0].cpu().numpy(),
+                                                  "light_volume": res.download_light_slices(bounds[0][0], bounds[0][1] - bounds[0][0])})
+    # untimed check on rank 0 (--full): one whole handle replays the lights and renders the last frame
     ok = None
-    if rank == 0:
+    if rank == 0 and args.full:
         whole = abi.Resources(dims, fmt, cfg["light_32bit"], False, local_rank)
         whole.upload_volume_device(vol_dev.data_ptr(), vol_dev.numel() * vol_dev.element_size())
         whole.set_tf_lut(lut)
@@ -977,6 +1033,7 @@ def slab_resident_bench(args, torch, dist, S, abi, rank, local_rank, n_gpus, dev
         own = res.download_light_slices(bounds[0][0], bounds[0][1] - bounds[0][0])
         ok = bool(torch.equal(frame[0], want)) and bool(np.array_equal(own, whole.download_light_volume()[bounds[0][0]:bounds[0][1]]))
         whole.close()
+    if rank == 0:
         value = total_samples * args.steps / elapsed / 1e6
         print(json.dumps({
             "metric": "volume Msamples/s (rays x steps) at 512^3, 1024^2 view; % HBM roofline",
@@ -991,7 +1048,7 @@ def slab_resident_bench(args, torch, dist, S, abi, rank, local_rank, n_gpus, dev
                        "resident_data_slices": [dlo, dhi], "resident_light_slices": [llo, lhi]},
             "nominal_samples_per_step": total_samples,
             "slab_frame_and_light_volume_equal_one_whole_handle": ok,
-            "roofline": None, "cpu_baseline": None}))
+            "roofline": None, "cpu_baseline": None, "full": bool(args.full), "outputs_dumped": dumped}))
     res.close()
 
 

@@ -5,7 +5,7 @@ OUT=${1:-gpurun_out/l2}
 mkdir -p "$OUT"; export TMPDIR=/tmp
 for v in 0 1; do
   rm -rf /tmp/prof_l2_$v
-  TBRM_RAY_XCD_ROWS=$v rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum --output-format csv -d /tmp/prof_l2_$v -o p -- python bench.py --raymarch-only --no-cpu-baseline --timed-only --steps 10 --warmup 2 > /dev/null 2>&1
+  TBRM_RAY_XCD_ROWS=$v rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum --output-format csv -d /tmp/prof_l2_$v -o p -- python bench.py --full --raymarch-only --no-cpu-baseline --timed-only --steps 10 --warmup 2 > /dev/null 2>&1
   find /tmp/prof_l2_$v -name "*counter_collection.csv" -exec cp {} "$OUT/l2_rows$v.csv" \;
 done
 python - "$OUT" <<'PY'

@@ -14,7 +14,7 @@ for method in stochastic host_trap; do
   rm -rf /tmp/pcs_$method
   if [ $method = stochastic ]; then unit="--pc-sampling-unit cycles --pc-sampling-interval ${PCS_INTERVAL:-65536}"; else unit="--pc-sampling-unit time --pc-sampling-interval ${PCS_INTERVAL_US:-1}"; fi
   (cd /tmp && timeout 600 rocprofv3 --pc-sampling-beta-enabled --pc-sampling-method $method $unit --kernel-trace --output-format csv json -d /tmp/pcs_$method -o p -- \
-      python $ROOT/bench.py $ARGS --no-cpu-baseline --timed-only --steps ${PCS_STEPS:-40} --warmup 3 > "$ROOT/$OUT/$method.bench.json" 2> /tmp/pcs_$method.err)
+      python $ROOT/bench.py $ARGS --full --no-cpu-baseline --timed-only --steps ${PCS_STEPS:-40} --warmup 3 > "$ROOT/$OUT/$method.bench.json" 2> /tmp/pcs_$method.err)
   echo "rc=$?" > "$OUT/$method.log"
   grep -v amdgpu.ids /tmp/pcs_$method.err | tail -25 >> "$OUT/$method.log"
   find /tmp/pcs_$method -type f | sed 's/^/file: /' >> "$OUT/$method.log"
