@@ -1,0 +1,150 @@
+"""The CPU oracle and the host pass parameters against the independent float64 restatement (tests/exact_reference.py).
+
+The oracle and the kernels evaluate one fp32 definition and were written together; this file checks that
+definition against the operation as the reference states it, and checks the checker: every misreading listed in
+exact_reference.KNOWN_MUTATIONS, applied to the float64 side, must make at least one scene disagree with the oracle.
+Tolerances below are calibrated on this scene matrix (measured maxima in DESIGN.md 5).
+"""
+import numpy as np
+import pytest
+
+from tbraymarcherplugin_amd import abi
+import exact_reference as X
+import exact_scenes as E
+
+PROP_R32F_TOL = 1e-4    # north star; measured max 4.9e-5 (steep step TF), <= 6e-6 elsewhere
+U8_CODES = 2            # UNORM8: a flipped rounding in a ping-pong buffer moves later slices by < 1 code per light
+U8_EXACT_MIN = 0.98     # measured >= 0.988 per scene
+RGBA_TOL = 1e-4         # north star: smooth TFs, measured max 7.1e-5
+RGBA_TOL_STEEP = 2e-3   # steep TFs (bone, one-texel step): fp32 position sums (<= steps * 2^-24) times a TF slope of ~500 per
+                        # data unit; measured max 6.5e-4
+STEEP_TFS = ("B", "step")
+TAINT_CAP = 0.05        # no comparison may mask more than 5 % of its outputs
+MARGIN_MIN = 1e-3       # face-sort ties, the 0.99 snap and border-colour rounding ties are kept this far away
+
+
+def prop_compare(light32, o, e, taint):
+    """-> (passed, max untainted |d|, exact fraction)"""
+    d = np.abs(o - e)[~taint]
+    worst = float(d.max()) if d.size else 0.0
+    if light32:
+        return worst <= PROP_R32F_TOL, worst, float((d == 0).mean())
+    exact = float((d == 0).mean())
+    return worst <= U8_CODES and exact >= U8_EXACT_MIN, worst, exact
+
+
+def ray_tol(scene):
+    return RGBA_TOL_STEEP if scene["tf"] in STEEP_TFS else RGBA_TOL
+
+
+_cache = {}
+
+
+def oracle_prop(oracle_mod, scene):
+    key = ("p", scene["name"])
+    if key not in _cache:
+        _cache[key] = E.run_oracle(oracle_mod, scene)
+    return _cache[key]
+
+
+def oracle_ray(oracle_mod, scene):
+    key = ("r", scene["name"])
+    if key not in _cache:
+        _cache[key] = E.run_oracle_ray(oracle_mod, scene)
+    return _cache[key]
+
+
+@pytest.mark.parametrize("scene", E.PROP_SCENES, ids=E.PROP_IDS)
+def test_oracle_propagation_matches_float64_reference(oracle_mod, scene):
+    o, tf = oracle_prop(oracle_mod, scene)
+    e, taint, margins = E.run_exact(scene, tf)
+    for m in margins:
+        assert min(m.values()) > MARGIN_MIN, (scene["name"], m)
+    assert taint.mean() < TAINT_CAP
+    ok, worst, exact = prop_compare(scene["light32"], o, e, taint)
+    assert ok, f"{scene['name']}: max untainted |d| {worst}, exact {exact}, tainted {taint.mean():.4f}"
+    assert np.abs(o).max() > 0  # the scene lit something
+
+
+@pytest.mark.parametrize("scene", E.RAY_SCENES, ids=E.RAY_IDS)
+def test_oracle_raymarch_matches_float64_reference(oracle_mod, scene):
+    o, tf = oracle_ray(oracle_mod, scene)
+    e, taint = E.run_exact_ray(scene, tf)
+    assert taint.mean() < TAINT_CAP
+    d = np.abs(o - e)[~taint]
+    assert d.max() <= ray_tol(scene), f"{scene['name']}: max untainted |d| {d.max()}"
+    assert (o[..., 3] > 0.05).mean() > 0.02  # the frame shows the volume
+
+
+def _random_world(rng):
+    q = rng.normal(size=4)
+    q /= np.linalg.norm(q)
+    scale = rng.uniform(20.0, 200.0, size=3)
+    return abi.make_world(abi.Transform(abi.Quatd(*q), abi.Vec3d(*rng.uniform(-30, 30, 3)), abi.Vec3d(*scale)))
+
+
+def test_pass_parameters_match_float64_reference(abi_mod, oracle_mod):
+    """tbrm_host_light_passes and the oracle's light_passes against the float64 pass parameters (random lights,
+    transforms and dims, away from ties; the reference narrows to float where it binds: rtol 1e-6)."""
+    rng = np.random.default_rng(20261016)
+    checked = 0
+    while checked < 300:
+        world = _random_world(rng)
+        d = rng.normal(size=3)
+        inten = float(rng.uniform(0.0, 2.0))
+        dims = tuple(int(x) for x in rng.integers(1, 300, size=3))
+        passes, n, margins = X.light_passes(d, inten, world, dims)
+        if min(margins.values()) < 1e-4:
+            continue
+        light = abi.DirLightParams(d, inten)
+        for got, n_got in (abi.host_light_passes(light, world, dims), oracle_mod.light_passes(light, world, dims)):
+            assert n_got == n
+            for i in range(2):
+                g, r = got[i], passes[i]
+                assert (g.face, g.axis, tuple(g.td), g.start, g.stop, g.dir) == (r["face"], r["axis"], tuple(r["td"]), r["start"], r["stop"], r["dir"])
+                for name in ("weight", "light_alpha", "border_light", "step_size"):
+                    # abs: FaceWeight[1] = 1 - FaceWeight[0] is formed in float (ulp(1) = 1.2e-7, times intensity <= 2)
+                    assert getattr(g, name) == pytest.approx(r[name], rel=1e-6, abs=3e-7), name
+                np.testing.assert_allclose(list(g.prev_pixel_offset), r["prev_pixel_offset"], rtol=1e-6, atol=1e-9)
+                np.testing.assert_allclose(list(g.uvw_offset), r["uvw_offset"], rtol=1e-6, atol=1e-9)
+        checked += 1
+
+
+def test_local_clipping_and_borders_match_float64_reference(abi_mod, oracle_mod):
+    rng = np.random.default_rng(7)
+    for _ in range(50):
+        world = _random_world(rng)
+        world.clipping_plane = abi.ClippingPlaneParams(abi.Vec3d(*rng.uniform(-80, 80, 3)), abi.Vec3d(*rng.normal(size=3)))
+        c, dvec = X.local_clipping(world)
+        oc, od = oracle_mod.local_clipping(world)
+        np.testing.assert_allclose(oc, c, rtol=1e-6, atol=1e-6)
+        np.testing.assert_allclose(od, dvec, rtol=1e-6, atol=1e-6)
+        w = abi.WindowingParams(float(rng.uniform(0, 1)), float(rng.uniform(0.1, 1)))
+        for mode in (abi.BORDER_ENGINE_8BIT, abi.BORDER_EXACT_FLOAT):
+            assert oracle_mod.data_border(w, mode) == pytest.approx(X.data_border(w.center, w.width, mode), rel=1e-6, abs=1e-7)
+
+
+def _mutant_caught(oracle_mod, mutation):
+    X.MUTATIONS.clear()
+    X.MUTATIONS.add(mutation)
+    try:
+        for scene in E.PROP_SCENES:
+            o, tf = oracle_prop(oracle_mod, scene)
+            e, taint, _ = E.run_exact(scene, tf)
+            if not prop_compare(scene["light32"], o, e, taint)[0]:
+                return scene["name"]
+        for scene in E.RAY_SCENES:
+            o, tf = oracle_ray(oracle_mod, scene)
+            e, taint = E.run_exact_ray(scene, tf)
+            if np.abs(o - e)[~taint].max() > ray_tol(scene):
+                return scene["name"]
+    finally:
+        X.MUTATIONS.clear()
+    return None
+
+
+@pytest.mark.parametrize("mutation", X.KNOWN_MUTATIONS)
+def test_every_misreading_is_caught(oracle_mod, mutation):
+    """A subtly wrong restatement must disagree with the oracle beyond tolerance on at least one scene; if none does, the
+    scene matrix or the tolerance is too loose."""
+    assert _mutant_caught(oracle_mod, mutation) is not None, f"no scene catches the misreading {mutation!r}"
