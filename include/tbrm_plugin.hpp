@@ -15,6 +15,7 @@
 #pragma once
 
 #include "tbrm.h"
+#include "tbrm_labels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -271,6 +272,23 @@ public:
         bHasTF = true;
         bRequestedRecompute = true;
     }
+
+    // Label overlay (include/tbrm_labels.h; no counterpart in the reference's actor): thin forwards to the C-ABI. Labels change
+    // neither the illumination nor the skipping metadata of the light operators, so none of these requests a recompute; the
+    // Intensity and Octree renderers ignore them.
+    bool SetLabelVolume(const uint8_t* Labels, size_t NumBytes)
+    {
+        return RaymarchResources.Handle && tbrm_upload_label_volume(RaymarchResources.Handle, Labels, NumBytes) == TBRM_OK;
+    }
+    bool UpdateLabelRegion(const int32_t Origin[3], const int32_t Extent[3], const uint8_t* Labels, size_t NumBytes)
+    {
+        return RaymarchResources.Handle && tbrm_update_label_region(RaymarchResources.Handle, Origin, Extent, Labels, NumBytes) == TBRM_OK;
+    }
+    bool SetLabelColors(const float* Rgba256x4)
+    {
+        return RaymarchResources.Handle && tbrm_set_label_colors(RaymarchResources.Handle, Rgba256x4) == TBRM_OK;
+    }
+    bool ClearLabelVolume() { return RaymarchResources.Handle && tbrm_release_label_volume(RaymarchResources.Handle) == TBRM_OK; }
 
     // :746-784 — every windowing change requests a full recompute
     void SetWindowCenter(float Center) { if (Center != RaymarchResources.WindowingParameters.Center) { RaymarchResources.WindowingParameters.Center = Center; WindowingChanged(); } }

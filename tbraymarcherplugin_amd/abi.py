@@ -131,6 +131,14 @@ SYMBOLS = [
 
 ABI_VERSION = 5  # TBRM_ABI_VERSION of include/tbrm.h (tests/test_abi.py compares the two)
 
+# every symbol include/tbrm_labels.h declares (the label overlay; tests/test_labels_abi.py checks the header against this list)
+LABEL_SYMBOLS = [
+    "tbrm_labels_abi_version", "tbrm_make_default_label_colors", "tbrm_upload_label_volume", "tbrm_update_label_region",
+    "tbrm_download_label_volume", "tbrm_set_label_colors", "tbrm_release_label_volume", "tbrm_has_label_volume",
+]
+
+LABELS_ABI_VERSION = 1  # TBRM_LABELS_ABI_VERSION of include/tbrm_labels.h
+
 _lib = None
 
 
@@ -218,6 +226,17 @@ def load():
     lib.tbrm_host_plan_light.argtypes = [P(DirLightParams), P(WorldParams), P(C.c_int32 * 3), C.c_int, P(C.c_int32 * 8), P(C.c_int)]
     lib.tbrm_host_local_clipping.argtypes = [P(WorldParams), P(C.c_float * 3), P(C.c_float * 3)]
     lib.tbrm_host_world_to_local.argtypes = [P(Transform), P(C.c_float * 12)]
+    have = lib.tbrm_labels_abi_version() if hasattr(lib, "tbrm_labels_abi_version") else -1
+    if have != LABELS_ABI_VERSION:
+        raise ImportError(f"{LIB_PATH} has label ABI version {have}, this binding is written against {LABELS_ABI_VERSION}: rebuild it "
+                          "(`python tbraymarcherplugin_amd/build.py --force`)")
+    lib.tbrm_make_default_label_colors.argtypes = [vp]
+    lib.tbrm_upload_label_volume.argtypes = [vp, vp, C.c_size_t]
+    lib.tbrm_update_label_region.argtypes = [vp, P(C.c_int32 * 3), P(C.c_int32 * 3), vp, C.c_size_t]
+    lib.tbrm_download_label_volume.argtypes = [vp, vp, C.c_size_t]
+    lib.tbrm_set_label_colors.argtypes = [vp, vp]
+    lib.tbrm_release_label_volume.argtypes = [vp]
+    lib.tbrm_has_label_volume.argtypes = [vp]
     _lib = lib
     return lib
 
@@ -298,6 +317,13 @@ def color_curve_to_lut(keys):
 def make_default_tf_lut():
     out = np.empty((256, 4), dtype=np.float32)
     check(load().tbrm_make_default_tf_lut(out.ctypes.data))
+    return out
+
+
+def make_default_label_colors():
+    """The reference's GetColorFromLabelValue as a 256 x RGBA table (include/tbrm_labels.h)."""
+    out = np.empty((256, 4), dtype=np.float32)
+    check(load().tbrm_make_default_label_colors(out.ctypes.data))
     return out
 
 
@@ -389,6 +415,36 @@ class Resources:
 
     def set_windowing(self, w):
         check(self.lib.tbrm_set_windowing(self.handle, C.byref(w)))
+
+    # label overlay (include/tbrm_labels.h): uint8 [z, y, x] on the data volume's grid
+    def upload_label_volume(self, labels):
+        labels = np.ascontiguousarray(labels)
+        assert labels.dtype == np.uint8 and labels.shape == (self.desc.dim_z, self.desc.dim_y, self.desc.dim_x)
+        check(self.lib.tbrm_upload_label_volume(self.handle, labels.ctypes.data, labels.nbytes))
+
+    def update_label_region(self, origin, block):
+        """writes `block` (uint8 [ez, ey, ex]) at voxel `origin` (x, y, z) of the attached label volume"""
+        block = np.ascontiguousarray(block)
+        assert block.dtype == np.uint8 and block.ndim == 3
+        o = (C.c_int32 * 3)(*[int(v) for v in origin])
+        e = (C.c_int32 * 3)(block.shape[2], block.shape[1], block.shape[0])
+        check(self.lib.tbrm_update_label_region(self.handle, C.byref(o), C.byref(e), block.ctypes.data, block.nbytes))
+
+    def download_label_volume(self):
+        out = np.empty((self.desc.dim_z, self.desc.dim_y, self.desc.dim_x), dtype=np.uint8)
+        check(self.lib.tbrm_download_label_volume(self.handle, out.ctypes.data, out.nbytes))
+        return out
+
+    def set_label_colors(self, lut):
+        lut = np.ascontiguousarray(lut, dtype=np.float32)
+        assert lut.shape == (256, 4)
+        check(self.lib.tbrm_set_label_colors(self.handle, lut.ctypes.data))
+
+    def release_label_volume(self):
+        check(self.lib.tbrm_release_label_volume(self.handle))
+
+    def has_label_volume(self):
+        return bool(self.lib.tbrm_has_label_volume(self.handle))
 
     def is_initialized(self):
         return bool(self.lib.tbrm_resources_is_initialized(self.handle))

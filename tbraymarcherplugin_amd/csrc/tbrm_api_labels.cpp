@@ -1,0 +1,268 @@
+// tbrm_api_labels.cpp — the label overlay's C-ABI (include/tbrm_labels.h): a uint8 segmentation volume on the data volume's grid,
+// its colour table, and what the lit march needs to take the label step (k_raymarch_lit LABELS) with exact empty-space skipping.
+//
+// The reference sketches the feature in RaymarchExperimental.usf:138-215 (GetColorFromLabelValue, SampleLabelVolume,
+// AccumulateOneRaymarchLabelStep) and never calls it; DESIGN.md "Label overlay" pins the semantics the kernel implements.
+//
+// Metadata, per label upload / region update / colour change:
+//   d_lab_mask  per brick, the set of labels among its voxels (k_label_brick_masks; a region update recomputes the touched bricks)
+//   d_lab_live  per brick, "holds a label whose colour alpha is > 0" (k_label_live, which also ORs the bricks' sets into the volume's)
+// and, per frame when stale (ensure_label_skipping), the merge with the data volume's emptiness: d_empty_lab, d_dist_lab.
+// None of it touches d_empty, d_dist, empty_gen, data_gen or tf_gen: the light operators, their block lists and the factor cache
+// never see a label change. The occlusion stream never reads the label volume, so nothing here waits for it.
+#include "tbrm_resources.h"
+#include "../../include/tbrm_labels.h"
+
+#include <cmath>
+#include <cstring>
+
+using namespace tbrm;
+using namespace tbrm_host;
+
+namespace {
+
+void default_label_colors(float* out)
+{
+    for (int i = 0; i < 256; ++i) { // GetColorFromLabelValue (RaymarchExperimental.usf)
+        float* c = out + 4 * i;
+        c[0] = c[1] = c[2] = 0.0f;
+        c[3] = 1.0f; // 3 .. 255: opaque black, so that stray labels show
+        if (i == 0) c[3] = 0.0f;
+        else if (i == 1) { c[0] = 1.0f; c[3] = 0.5f; }
+        else if (i == 2) { c[1] = 1.0f; c[3] = 0.5f; }
+    }
+}
+
+size_t label_voxels(const tbrm_resources* r) { return (size_t) r->desc.dim_x * r->desc.dim_y * r->desc.dim_z; }
+size_t label_bricks(const tbrm_resources* r) { return (size_t) r->dbn[0] * r->dbn[1] * r->dbn[2]; }
+
+// the colour table to the device and the set of labels it shows
+int put_colors(tbrm_resources* r, const float* rgba)
+{
+    if (rgba != r->lab_colors) memcpy(r->lab_colors, rgba, sizeof(r->lab_colors));
+    for (int w = 0; w < 8; ++w) r->lab_alive[w] = 0u;
+    for (int i = 0; i < 256; ++i)
+        if (r->lab_colors[4 * i + 3] > 0.0f) r->lab_alive[i >> 5] |= 1u << (i & 31);
+    HIP_TRY(hipMemcpyAsync(r->d_lab_colors, r->lab_colors, sizeof(r->lab_colors), hipMemcpyHostToDevice, r->stream));
+    return TBRM_OK;
+}
+
+// the per-brick live bits and the volume's label set (from the per-brick sets); the merged metadata is stale after it
+int refresh_live(tbrm_resources* r)
+{
+    LabelLiveParams lp{};
+    lp.masks = r->d_lab_mask;
+    lp.n_bricks = (int) label_bricks(r);
+    for (int w = 0; w < 8; ++w) lp.alive[w] = r->lab_alive[w];
+    lp.live = r->d_lab_live;
+    lp.present = r->d_lab_present;
+    HIP_TRY(hipMemsetAsync(r->d_lab_present, 0, 8 * sizeof(uint32_t), r->stream));
+    HIP_TRY(launch_label_live(lp, r->stream));
+    HIP_TRY(hipMemcpyAsync(r->lab_present, r->d_lab_present, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    r->lab_skip_valid = false;
+    return TBRM_OK;
+}
+
+int brick_masks(tbrm_resources* r, const int b0[3], const int b1[3])
+{
+    LabelBrickParams bp{};
+    bp.labels = r->d_labels;
+    bp.masks = r->d_lab_mask;
+    bp.bnx = r->dbn[0];
+    bp.bny = r->dbn[1];
+    for (int c = 0; c < 3; ++c) { bp.b0[c] = b0[c]; bp.b1[c] = b1[c]; }
+    HIP_TRY(launch_label_brick_masks(bp, r->stream));
+    return TBRM_OK;
+}
+
+// does some label present in the volume show (colour alpha > 0)?
+bool labels_visible(const tbrm_resources* r)
+{
+    for (int w = 0; w < 8; ++w)
+        if (r->lab_present[w] & r->lab_alive[w]) return true;
+    return false;
+}
+
+// d_empty_lab / d_dist_lab from the current d_empty (ensure_skipping has run) and label occupancy: launches only, no allocation
+int ensure_label_skipping(tbrm_resources* r)
+{
+    if (r->lab_skip_valid && r->lab_empty_gen == r->empty_gen) return TBRM_OK;
+    const int mode = r->desc.data_address_mode == TBRM_ADDRESS_CLAMP ? ADDR_CLAMP : ADDR_WRAP;
+    LabelMergeParams mp{r->d_empty, r->d_lab_live, r->d_empty_lab, {r->bn[0], r->bn[1], r->bn[2]}};
+    HIP_TRY(launch_label_merge(mp, mode, r->stream));
+    for (int axis = 0; axis < 3; ++axis) { // the three separable passes of the data volume's field (k_brick_dist)
+        DistParams dp{r->d_empty_lab, axis == 0 ? nullptr : r->d_dist_lab[(axis + 1) & 1], r->d_dist_lab[axis & 1],
+            {r->bn[0], r->bn[1], r->bn[2]}, axis};
+        HIP_TRY(launch_brick_dist(dp, mode, r->stream));
+    }
+    r->lab_skip_valid = true;
+    r->lab_empty_gen = r->empty_gen;
+    return TBRM_OK;
+}
+
+} // namespace
+
+namespace tbrm_host {
+
+int label_ray_params(tbrm_resources* r, RayParams& p)
+{
+    if (!r->d_labels || !(labels_visible(r) || tune(TUNE_RAY_LABELS) > 0)) return TBRM_OK; // nothing shows: the kernel without labels
+    p.labels = r->d_labels;
+    p.lab_colors = r->d_lab_colors;
+    if (p.skip_dist) {
+        if (int e = ensure_label_skipping(r)) return e;
+        p.empty_bits = r->d_empty_lab;
+        p.skip_dist = r->d_dist_lab[0];
+    }
+    return TBRM_OK;
+}
+
+void release_labels(tbrm_resources* r)
+{
+    (void) hipFree(r->d_labels);
+    (void) hipFree(r->d_lab_mask);
+    (void) hipFree(r->d_lab_present);
+    (void) hipFree(r->d_lab_live);
+    (void) hipFree(r->d_empty_lab);
+    for (uint8_t*& d : r->d_dist_lab) { (void) hipFree(d); d = nullptr; }
+    (void) hipFree(r->d_lab_colors);
+    r->d_labels = nullptr;
+    r->d_lab_mask = r->d_lab_present = r->d_lab_live = r->d_empty_lab = nullptr;
+    r->d_lab_colors = nullptr;
+    for (int w = 0; w < 8; ++w) r->lab_present[w] = r->lab_alive[w] = 0u;
+    r->lab_skip_valid = false;
+}
+
+} // namespace tbrm_host
+
+extern "C" {
+
+int tbrm_labels_abi_version(void) { return TBRM_LABELS_ABI_VERSION; }
+
+int tbrm_make_default_label_colors(float* out)
+{
+    if (!out) return fail(TBRM_ERR_INVALID_ARG, "null argument");
+    default_label_colors(out);
+    return TBRM_OK;
+}
+
+int tbrm_upload_label_volume(tbrm_resources* r, const uint8_t* host_labels, size_t n_bytes)
+{
+    if (r && r->resident) return fail(TBRM_ERR_UNSUPPORTED, "slab-resident handle: label volumes are not supported");
+    if (!r || !host_labels) return fail(TBRM_ERR_INVALID_ARG, "null argument");
+    if (n_bytes != label_voxels(r)) return fail(TBRM_ERR_INVALID_ARG, "label volume is %zu bytes, expected %zu", n_bytes, label_voxels(r));
+    if (int e = bind(r)) return e;
+    if (!r->d_labels) { // everything the label step and its skipping metadata use: rendering allocates nothing
+        const size_t nb = label_bricks(r), nb_pad = (nb + 255) / 256 * 256;
+        hipError_t e = hipMalloc((void**) &r->d_labels, nb * 512);
+        if (e == hipSuccess) e = hipMalloc((void**) &r->d_lab_mask, nb * 8 * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc((void**) &r->d_lab_present, 8 * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc((void**) &r->d_lab_live, nb_pad / 8);
+        if (e == hipSuccess) e = hipMalloc((void**) &r->d_empty_lab, nb_pad / 8);
+        for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipMalloc((void**) &r->d_dist_lab[k], nb_pad);
+        if (e == hipSuccess) e = hipMalloc((void**) &r->d_lab_colors, 256 * sizeof(float4));
+        if (e != hipSuccess) {
+            release_labels(r);
+            return fail(e == hipErrorOutOfMemory ? TBRM_ERR_OUT_OF_MEMORY : TBRM_ERR_NO_DEVICE, "label volume allocation failed: %s", hipGetErrorString(e));
+        }
+        default_label_colors(r->lab_colors);
+        if (int e2 = put_colors(r, r->lab_colors)) { release_labels(r); return e2; }
+    }
+    void* staging = nullptr; // linear copy in HBM, re-laid out into bricks by the GPU (k_relayout, 1-byte elements)
+    HIP_TRY(hipMalloc(&staging, n_bytes));
+    const int dims[3] = {r->desc.dim_x, r->desc.dim_y, r->desc.dim_z};
+    hipError_t e1 = hipMemcpyAsync(staging, host_labels, n_bytes, hipMemcpyHostToDevice, r->stream);
+    if (e1 == hipSuccess) e1 = launch_relayout(relayout_params(staging, r->d_labels, dims, r->dbn, 1, true), r->stream);
+    if (e1 == hipSuccess) e1 = hipStreamSynchronize(r->stream); // the caller may free its buffer on return
+    (void) hipFree(staging);
+    HIP_TRY(e1);
+    const int b0[3] = {0, 0, 0}, b1[3] = {r->dbn[0], r->dbn[1], r->dbn[2]};
+    if (int e = brick_masks(r, b0, b1)) return e;
+    return refresh_live(r);
+}
+
+int tbrm_update_label_region(tbrm_resources* r, const int32_t origin[3], const int32_t extent[3], const uint8_t* host_labels, size_t n_bytes)
+{
+    if (!r || !origin || !extent || !host_labels) return fail(TBRM_ERR_INVALID_ARG, "null argument");
+    if (!r->d_labels) return fail(TBRM_ERR_NOT_INITIALIZED, "no label volume: upload one with tbrm_upload_label_volume");
+    const int dims[3] = {r->desc.dim_x, r->desc.dim_y, r->desc.dim_z};
+    size_t n = 1;
+    for (int c = 0; c < 3; ++c) {
+        if (origin[c] < 0 || extent[c] <= 0 || extent[c] > dims[c] - origin[c])
+            return fail(TBRM_ERR_INVALID_ARG, "region [%d, %d + %d) along axis %d of a volume %d wide", origin[c], origin[c], extent[c], c, dims[c]);
+        n *= (size_t) extent[c];
+    }
+    if (n_bytes != n) return fail(TBRM_ERR_INVALID_ARG, "region is %zu bytes, expected %zu", n_bytes, n);
+    if (int e = bind(r)) return e;
+    void* staging = nullptr;
+    HIP_TRY(hipMalloc(&staging, n_bytes));
+    LabelRegionParams rp{};
+    rp.src = (const uint8_t*) staging;
+    rp.dst = r->d_labels;
+    for (int c = 0; c < 3; ++c) { rp.origin[c] = origin[c]; rp.extent[c] = extent[c]; }
+    rp.bnx = r->dbn[0];
+    rp.bnxy = r->dbn[0] * r->dbn[1];
+    hipError_t e1 = hipMemcpyAsync(staging, host_labels, n_bytes, hipMemcpyHostToDevice, r->stream);
+    if (e1 == hipSuccess) e1 = launch_label_region(rp, r->stream);
+    if (e1 == hipSuccess) e1 = hipStreamSynchronize(r->stream);
+    (void) hipFree(staging);
+    HIP_TRY(e1);
+    int b0[3], b1[3]; // the bricks the box touches
+    for (int c = 0; c < 3; ++c) { b0[c] = origin[c] / kBrick; b1[c] = (origin[c] + extent[c] - 1) / kBrick + 1; }
+    if (int e = brick_masks(r, b0, b1)) return e;
+    return refresh_live(r);
+}
+
+int tbrm_download_label_volume(tbrm_resources* r, uint8_t* host_out, size_t n_bytes)
+{
+    if (!r || !host_out) return fail(TBRM_ERR_INVALID_ARG, "null argument");
+    if (!r->d_labels) return fail(TBRM_ERR_NOT_INITIALIZED, "no label volume");
+    if (n_bytes != label_voxels(r)) return fail(TBRM_ERR_INVALID_ARG, "label volume is %zu bytes, got %zu", label_voxels(r), n_bytes);
+    if (int e = bind(r)) return e;
+    void* staging = nullptr;
+    HIP_TRY(hipMalloc(&staging, n_bytes));
+    const int dims[3] = {r->desc.dim_x, r->desc.dim_y, r->desc.dim_z};
+    hipError_t e1 = launch_relayout(relayout_params(r->d_labels, staging, dims, r->dbn, 1, false), r->stream);
+    if (e1 == hipSuccess) e1 = hipMemcpyAsync(host_out, staging, n_bytes, hipMemcpyDeviceToHost, r->stream);
+    if (e1 == hipSuccess) e1 = hipStreamSynchronize(r->stream);
+    (void) hipFree(staging);
+    HIP_TRY(e1);
+    return TBRM_OK;
+}
+
+int tbrm_set_label_colors(tbrm_resources* r, const float* rgba_256x4)
+{
+    if (!r || !rgba_256x4) return fail(TBRM_ERR_INVALID_ARG, "null argument");
+    for (int i = 0; i < 1024; ++i) {
+        const float v = rgba_256x4[i];
+        if (!std::isfinite(v) || v < 0.0f || v > 1.0f)
+            return fail(TBRM_ERR_INVALID_ARG, "label colour %d component %d is %g: components must be finite and in [0, 1]", i / 4, i % 4, (double) v);
+    }
+    if (!r->d_labels) return fail(TBRM_ERR_NOT_INITIALIZED, "no label volume: upload one with tbrm_upload_label_volume");
+    if (int e = bind(r)) return e;
+    HIP_TRY(hipStreamSynchronize(r->stream)); // (a frame in flight may still read the table)
+    if (int e = put_colors(r, rgba_256x4)) return e;
+    return refresh_live(r);
+}
+
+int tbrm_release_label_volume(tbrm_resources* r)
+{
+    if (!r) return fail(TBRM_ERR_INVALID_ARG, "null argument");
+    if (!r->d_labels) return TBRM_OK;
+    if (int e = bind(r)) return e;
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    release_labels(r);
+    return TBRM_OK;
+}
+
+int tbrm_has_label_volume(const tbrm_resources* r)
+{
+    if (!r) {
+        (void) fail(TBRM_ERR_INVALID_ARG, "null argument");
+        return 0;
+    }
+    return r->d_labels ? 1 : 0;
+}
+
+} // extern "C"

@@ -80,6 +80,7 @@ int tbrm_raymarch_lit_device(tbrm_resources* r, const tbrm_camera* cam, const tb
         p.empty_bits = r->d_empty;
         p.skip_dist = r->d_dist[0];
     }
+    if (int e = label_ray_params(r, p)) return e; // (tbrm_labels.h: the label step, when a label volume shows something)
     if (int e = begin_timed(r, 1)) return e;
     HIP_TRY(launch_raymarch(p, r->stream));
     ++r->launches[2];
@@ -91,6 +92,7 @@ int tbrm_raymarch_lit_slab_device(tbrm_resources* r, const tbrm_camera* cam, con
                                   const tbrm_slab* slab, int direction)
 {
     if (!r || !cam || !tile || !rp || !world || !device_state_rgba || !slab) return fail(TBRM_ERR_INVALID_ARG, "null argument");
+    if (r->d_labels) return fail(TBRM_ERR_UNSUPPORTED, "the slab stage of the lit march has no label step: release the label volume first");
     if (!initialized(r)) return fail(TBRM_ERR_NOT_INITIALIZED, "resources have no volume or transfer function");
     if (slab->z_begin < 0 || slab->z_end > r->lv_dims[2] || slab->z_begin >= slab->z_end)
         return fail(TBRM_ERR_INVALID_ARG, "slab [%d, %d) of a light volume %d deep", slab->z_begin, slab->z_end, r->lv_dims[2]);

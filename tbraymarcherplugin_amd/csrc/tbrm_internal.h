@@ -265,6 +265,8 @@ struct RayParams {
     const uint16_t* octree;     // octree march only: the level marched (dense, x fastest)
     int oct_dims[3];            // its dimensions
     float oct_depth0;           // depth of octree level 0 (the z coordinate is rescaled by data depth / this)
+    const uint8_t* labels;      // k_raymarch_lit LABELS: the label volume, bricked on the data volume's grid (null: no label step)
+    const float4* lab_colors;   // ... its colour table (256 x RGBA float)
 };
 
 struct BrickParams {
@@ -355,6 +357,8 @@ enum Tunable : int {
                              // (DualOcc); 0: one launch per pass
     TUNE_SWEEP_CHAIN,        // consecutive sweep passes of an operator per launch (k_light_sweep_chain): 1 = one launch per pass, up to 4
     TUNE_RAY_XCD_ROWS,       // k_raymarch_lit: rows of pixel blocks per band dealt to one XCD (0: blocks in launch order, i.e. round-robin)
+    TUNE_RAY_LABELS,         // 1: the lit march takes the label step whenever a label volume is attached, even when no label present in
+                             // it has a colour alpha > 0 (a test hook: the same frame by the other kernel); 0: only when one does
     TUNE_COUNT
 };
 int tune(Tunable t);
@@ -384,5 +388,36 @@ hipError_t launch_count_samples(const RayParams& p, hipStream_t s);
 hipError_t launch_brick_minmax(const BrickParams& p, hipStream_t s);
 hipError_t launch_brick_empty(const EmptyParams& p, hipStream_t s);
 hipError_t launch_brick_dist(const DistParams& p, int addr_mode, hipStream_t s);
+
+// label overlay (tbrm_api_labels.cpp, tbrm_volume_kernels.hip)
+struct LabelBrickParams {
+    const uint8_t* labels; // bricked label volume
+    uint32_t* masks;       // per brick: 8 words, the set of labels among its voxels
+    int bnx, bny;          // brick grid (x, y)
+    int b0[3], b1[3];      // bricks [b0, b1) per axis to (re)compute
+};
+struct LabelLiveParams {
+    const uint32_t* masks;
+    int n_bricks;
+    uint32_t alive[8];     // labels whose colour alpha is > 0
+    uint32_t* live;        // per brick bit: holds an alive label
+    uint32_t* present;     // 8 words, OR of every brick's set (pre-cleared)
+};
+struct LabelMergeParams {
+    const uint32_t* empty; // k_brick_empty bits of the data volume
+    const uint32_t* live;  // LabelLiveParams::live
+    uint32_t* out;         // empty and no live label brick within Chebyshev distance 1 (the sampler's brick addressing)
+    int bn[3];
+};
+struct LabelRegionParams {
+    const uint8_t* src;    // the sub-box, dense, x fastest
+    uint8_t* dst;          // bricked label volume
+    int origin[3], extent[3];
+    int bnx, bnxy;
+};
+hipError_t launch_label_brick_masks(const LabelBrickParams& p, hipStream_t s);
+hipError_t launch_label_live(const LabelLiveParams& p, hipStream_t s);
+hipError_t launch_label_merge(const LabelMergeParams& p, int addr_mode, hipStream_t s);
+hipError_t launch_label_region(const LabelRegionParams& p, hipStream_t s);
 
 } // namespace tbrm

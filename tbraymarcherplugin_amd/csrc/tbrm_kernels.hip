@@ -170,12 +170,19 @@ extern "C" __attribute__((visibility("default"))) int tbrm_debug_ray_stats(unsig
 // into LDS, one {voxel offset, brick-index part} pair per texel index -2 .. n + 1 and axis (tbrm_api.cpp build_ray_tables); a
 // sample's base and +1 entries of an axis arrive with one 16-byte LDS read. The host picks it when no sample position can lie more than two texels outside the volume
 // (a step of at most one texel: positions stay within one step of the unit cube) and the tables are small.
-template <int DFMT, int LFMT, int DMODE, int kRayLanes, bool SLAB = false, bool TAB = false>
+//
+// LABELS: the label overlay (include/tbrm_labels.h). The lane that takes sample idx also loads the label byte of the sample's
+// nearest voxel, beside the data taps; the replay then applies, per sample and in ray order, the data step, the unlit label step
+// and the early-exit test. The full step's (rgb * a', a') of every colour-table entry is computed once per workgroup into LDS
+// (dynamic, behind the tables: LABELS = false keeps the static layout); the fractional step computes its own. The host passes the
+// skipping distance field that has the label occupancy merged in (tbrm_api_labels.cpp), so skipped samples stay exact no-ops.
+template <int DFMT, int LFMT, int DMODE, int kRayLanes, bool SLAB = false, bool TAB = false, bool LABELS = false>
 __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6 waves per SIMD (80 VGPRs): measured 3-8 % faster than 5 or 8
 {
     static_assert(kRayLanes == 4 || kRayLanes == 8, "instantiated for 4 and 8 lanes per ray");
     static_assert(!(TAB && SLAB), "slab stages keep the arithmetic path (relocated layers)");
-    extern __shared__ __attribute__((aligned(16))) uint2 s_tab[]; // TAB: [x | y | z], n + 4 entries each
+    static_assert(!(LABELS && SLAB), "slab stages have no label step");
+    extern __shared__ __attribute__((aligned(16))) uint2 s_tab[]; // TAB: [x | y | z], n + 4 entries each; LABELS: then s_lab, s_lb
     const uint2* const tab_x = s_tab;
     const uint2* const tab_y = tab_x + (TAB ? p.data.nx + 4 : 0);
     const uint2* const tab_z = tab_y + (TAB ? p.data.ny + 4 : 0);
@@ -185,6 +192,14 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
     __shared__ float4 s_tf[256];
     __shared__ float4 s_x[256]; // per lane: (colour * alpha, alpha) of its sample; alpha < 0: nothing to accumulate
     s_tf[threadIdx.x] = p.tf[threadIdx.x];
+    // LABELS: per colour-table entry its full-step (rgb * a', a'); per lane the label of its sample (-1: no label step)
+    float4* const s_lab = reinterpret_cast<float4*>(s_tab + (TAB ? (p.data.nx + p.data.ny + p.data.nz + 12 + 1) & ~1 : 0));
+    short* const s_lb = reinterpret_cast<short*>(s_lab + 256);
+    if constexpr (LABELS) {
+        const float4 c = p.lab_colors[threadIdx.x];
+        const float a = c.w != 0.0f ? one_minus_pow01_(1.0f - c.w, 100.0f * (1 / p.steps)) : 0.0f; // (the data path's step_world)
+        s_lab[threadIdx.x] = make_float4(c.x * a, c.y * a, c.z * a, a);
+    }
     if constexpr (!TAB) __syncthreads();
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -288,6 +303,7 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
         }
         int ix = 0, iy = 0, iz = 0;
         float fx = 0.0f, fy = 0.0f, fz = 0.0f;
+        int lab = -1; // LABELS: the label of this lane's sample when it has a label step to take
         // (after a trip in which no lane of the wave sampled, the lanes inside their proven-empty range look their brick up
         // again as well: all ranges then start from here, and the wave can take the trips they share in one go — below)
         const bool renew = eager && has && !live && idx <= safe_until;
@@ -340,6 +356,12 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
             if constexpr (TAB) dt = tab_dt;
             else dt = tap_offsets<DMODE, SLAB>(p.data, ix, iy, iz);
             dtaps.issue(p.data.data, dt);
+            if constexpr (LABELS) { // the nearest label voxel (SampleLabelVolume): rint((N - 1) * saturate(pos)) per axis, in [0, N - 1]
+                const int lx = (int) __builtin_rintf((float) (p.data.nx - 1) * saturate_(q0));
+                const int ly = (int) __builtin_rintf((float) (p.data.ny - 1) * saturate_(q1));
+                const int lz = (int) __builtin_rintf((float) (p.data.nz - 1) * saturate_(q2));
+                lab = p.labels[brick_off(lx, ly, lz, p.data.bnx, p.data.bnxy)];
+            }
             // LightVolume.SampleLevel(Wrap, saturate(CurPos)) (WindowedRaymarchMaterials.usf:30)
             const float sp0 = saturate_(q0), sp1 = saturate_(q1), sp2 = saturate_(q2);
             if (same_grid && sp0 == q0 && sp1 == q1 && sp2 == q2) {
@@ -366,12 +388,17 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
                     x = make_float4((cs.x * l) * a, (cs.y * l) * a, (cs.z * l) * a, a);
                 }
             }
+            if constexpr (LABELS) {
+                if (is_full && s_lab[lab].w == 0.0f) lab = -1; // adds exactly nothing
+            }
         }
 
         // AccumulateLightEnergy (RaymarchMaterialCommon.usf:82-88) over the ray's 8 samples, in order, in every lane of
         // the ray; the early exit belongs to the full steps only (:75-79). A trip in which no lane of the wave has
         // anything to accumulate (empty space, windowed-out values) needs no exchange.
-        const bool any_x = __builtin_amdgcn_ballot_w64(x.w >= 0.0f || x.w != x.w) != 0;
+        bool to_accumulate = x.w >= 0.0f || x.w != x.w;
+        if constexpr (LABELS) to_accumulate = to_accumulate || lab >= 0;
+        const bool any_x = __builtin_amdgcn_ballot_w64(to_accumulate) != 0;
 #ifdef TBRM_RAY_STATS
         {
             const unsigned long long nx = __builtin_popcountll(__builtin_amdgcn_ballot_w64(x.w >= 0.0f || x.w != x.w));
@@ -380,16 +407,43 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
 #endif
         if (any_x) {
             s_x[threadIdx.x] = x;
+            if constexpr (LABELS) s_lb[threadIdx.x] = (short) lab;
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
             for (int t = 0; t < kRayLanes; ++t) {
                 const float4 c = xs[t];
-                if (!done && !(c.w < 0.0f)) {
-                    const float om = 1.0f - le3;
-                    le0 = le0 + (c.x * om);
-                    le1 = le1 + (c.y * om);
-                    le2 = le2 + (c.z * om);
-                    le3 = le3 + (c.w * om);
+                if constexpr (!LABELS) {
+                    if (!done && !(c.w < 0.0f)) {
+                        const float om = 1.0f - le3;
+                        le0 = le0 + (c.x * om);
+                        le1 = le1 + (c.y * om);
+                        le2 = le2 + (c.z * om);
+                        le3 = le3 + (c.w * om);
+                        if (le3 > 0.95f && base + t < max_steps) { le3 = 1.0f; done = true; }
+                    }
+                } else if (!done) { // the data step, then the label step (AccumulateOneRaymarchLabelStep: unlit), then the exit test
+                    if (!(c.w < 0.0f)) {
+                        const float om = 1.0f - le3;
+                        le0 = le0 + (c.x * om);
+                        le1 = le1 + (c.y * om);
+                        le2 = le2 + (c.z * om);
+                        le3 = le3 + (c.w * om);
+                    }
+                    const int lb = s_lb[(threadIdx.x & ~(kRayLanes - 1)) + t];
+                    if (lb >= 0) {
+                        float4 e;
+                        if (base + t < max_steps) e = s_lab[lb];
+                        else { // the fractional step (once per ray): its own a' with the step 100 * FinalStep
+                            const float4 raw = p.lab_colors[lb];
+                            const float a = raw.w != 0.0f ? one_minus_pow01_(1.0f - raw.w, 100.0f * final_step) : 0.0f;
+                            e = make_float4(raw.x * a, raw.y * a, raw.z * a, a);
+                        }
+                        const float om = 1.0f - le3;
+                        le0 = le0 + (e.x * om);
+                        le1 = le1 + (e.y * om);
+                        le2 = le2 + (e.z * om);
+                        le3 = le3 + (e.w * om);
+                    }
                     if (le3 > 0.95f && base + t < max_steps) { le3 = 1.0f; done = true; }
                 }
             }
@@ -428,27 +482,32 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
     if ((SLAB ? mine : valid) && b == 0) reinterpret_cast<float4*>(p.out)[(size_t) j * p.tile_w + i] = make_float4(le0, le1, le2, le3);
 }
 
-template <int DFMT, int LFMT, int RL>
+template <int DFMT, int LFMT, int RL, bool LABELS>
 static hipError_t launch_ray3(const RayParams& p, hipStream_t s)
 {
     constexpr int BW = 8, BH = RL == 4 ? 8 : 4; // 4 waves of 4x4 / 4x2 rays
     const dim3 grid((p.tile_w + BW - 1) / BW, (p.tile_h + BH - 1) / BH), block(256);
+    // LABELS: the colour-table contributions and the exchanged label bytes, behind the tables (4.5 KiB)
+    constexpr size_t lab_bytes = LABELS ? 256 * sizeof(float4) + 256 * sizeof(short) : 0;
     if (p.slab_on) {
-        if (p.data_addr_mode == ADDR_CLAMP) hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_CLAMP, RL, true>), grid, block, 0, s, p);
-        else hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_WRAP, RL, true>), grid, block, 0, s, p);
-        return hipGetLastError();
+        if constexpr (LABELS) return hipErrorInvalidValue; // (the host refuses slab stages while labels are attached)
+        else {
+            if (p.data_addr_mode == ADDR_CLAMP) hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_CLAMP, RL, true>), grid, block, 0, s, p);
+            else hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_WRAP, RL, true>), grid, block, 0, s, p);
+            return hipGetLastError();
+        }
     }
     // the offset tables (k_raymarch_lit TAB): a step of at most one texel along every axis — then no sample's base tap lies below
     // -2 or above n — and tables of at most 16 KiB (six workgroups per CU keep their place)
     const size_t tab_bytes = (size_t) ((p.data.nx + p.data.ny + p.data.nz + 12 + 1) & ~1) * sizeof(uint2);
     const bool tab = p.tab != nullptr && tune(TUNE_RAY_TABLES) != 0 && (float) std::max(p.data.nx, std::max(p.data.ny, p.data.nz)) <= p.steps && tab_bytes <= 16 * 1024;
     if (tab) {
-        if (p.data_addr_mode == ADDR_CLAMP) hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_CLAMP, RL, false, true>), grid, block, tab_bytes, s, p);
-        else hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_WRAP, RL, false, true>), grid, block, tab_bytes, s, p);
+        if (p.data_addr_mode == ADDR_CLAMP) hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_CLAMP, RL, false, true, LABELS>), grid, block, tab_bytes + lab_bytes, s, p);
+        else hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_WRAP, RL, false, true, LABELS>), grid, block, tab_bytes + lab_bytes, s, p);
         return hipGetLastError();
     }
-    if (p.data_addr_mode == ADDR_CLAMP) hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_CLAMP, RL>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_WRAP, RL>), grid, block, 0, s, p);
+    if (p.data_addr_mode == ADDR_CLAMP) hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_CLAMP, RL, false, false, LABELS>), grid, block, lab_bytes, s, p);
+    else hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_WRAP, RL, false, false, LABELS>), grid, block, lab_bytes, s, p);
     return hipGetLastError();
 }
 template <int DFMT, int LFMT>
@@ -464,7 +523,8 @@ static hipError_t launch_ray2(const RayParams& p, hipStream_t s)
     const double load = (double) p.tile_w * (double) p.tile_h * 512.0 / (double) (p.steps > 1.0f ? p.steps : 1.0f);
     const int forced = tune(TUNE_RAY_LANES);
     const int rl = forced ? forced : (load <= 700000.0 ? 8 : 4);
-    return rl == 8 ? launch_ray3<DFMT, LFMT, 8>(p, s) : launch_ray3<DFMT, LFMT, 4>(p, s);
+    if (p.labels) return rl == 8 ? launch_ray3<DFMT, LFMT, 8, true>(p, s) : launch_ray3<DFMT, LFMT, 4, true>(p, s);
+    return rl == 8 ? launch_ray3<DFMT, LFMT, 8, false>(p, s) : launch_ray3<DFMT, LFMT, 4, false>(p, s);
 }
 template <int DFMT>
 static hipError_t launch_ray1(const RayParams& p, hipStream_t s)

@@ -299,6 +299,20 @@ struct tbrm_resources {
     uint64_t passes[3]{};        // axis passes run as a sweep / as the chunked chain / one slice per launch (tbrm_path_counters)
     uint64_t occ_launches = 0;   // occlusion launches that served one pass (dual_launches: both passes of a light)
     uint64_t pair_sweeps = 0;    // sweep launches that propagated two lights' passes at once (PASS_ADD2)
+
+    // label overlay (tbrm_api_labels.cpp; include/tbrm_labels.h): all null until the first label upload
+    uint8_t* d_labels = nullptr;     // the label volume, bricked on the data volume's grid
+    uint32_t* d_lab_mask = nullptr;  // per brick: 8 words, the set of labels among its voxels
+    uint32_t* d_lab_present = nullptr; // 8 words: the volume's label set (read back into lab_present)
+    uint32_t* d_lab_live = nullptr;  // per brick bit: holds a label whose colour alpha is > 0
+    uint32_t* d_empty_lab = nullptr; // d_empty with the live label bricks' Chebyshev-1 neighbourhoods removed
+    uint8_t* d_dist_lab[2]{};        // its distance field (as d_dist; [0] is final): what the lit march with labels leaps by
+    float4* d_lab_colors = nullptr;  // 256 x RGBA float
+    float lab_colors[1024]{};
+    uint32_t lab_present[8]{};       // labels present in the volume
+    uint32_t lab_alive[8]{};         // labels whose colour alpha is > 0
+    bool lab_skip_valid = false;     // d_empty_lab / d_dist_lab hold the merge of the current label occupancy ...
+    uint64_t lab_empty_gen = 0;      // ... with this empty_gen's d_empty
 };
 
 
@@ -321,6 +335,9 @@ int begin_timed(tbrm_resources* r, int kind);
 int end_timed(tbrm_resources* r, int kind);
 int ensure_skipping(tbrm_resources* r);
 int raymarch_clip_mode(const float cc[3], const float cd[3]);
+// label overlay (tbrm_api_labels.cpp)
+int label_ray_params(tbrm_resources* r, RayParams& p); // the lit march's label step, when one is due (after the skipping metadata)
+void release_labels(tbrm_resources* r);                // (the stream must be idle)
 RelayoutParams relayout_params(const void* src, void* dst, const int dims[3], const int bn[3], size_t elem, bool to_bricks);
 
 // ---- the light-pass layer (tbrm_light_plan.cpp, tbrm_factor_cache.cpp, tbrm_light_enqueue.cpp, tbrm_light_operators.cpp) ------------------------------------------------------------------------

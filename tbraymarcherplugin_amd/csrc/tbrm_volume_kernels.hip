@@ -175,6 +175,126 @@ hipError_t launch_brick_dist(const DistParams& p, int addr_mode, hipStream_t s)
     return hipGetLastError();
 }
 
+// ---- label overlay: per-brick label sets, live bricks, the merged emptiness (tbrm_api_labels.cpp) -----------------------------
+// One wave per brick: the set of the labels among its 512 voxels (8 words). A brick of the grid's ragged edge holds padding
+// voxels (label 0, k_relayout zeroes them) that no sample reads: they only make the set larger, never the skipping inexact.
+__global__ __launch_bounds__(64) void k_label_brick_masks(const LabelBrickParams p)
+{
+    const int ex = p.b1[0] - p.b0[0], ey = p.b1[1] - p.b0[1];
+    const int k = blockIdx.x;
+    const int bx = p.b0[0] + k % ex, by = p.b0[1] + (k / ex) % ey, bz = p.b0[2] + k / (ex * ey);
+    const size_t b = ((size_t) bz * p.bny + by) * p.bnx + bx;
+    __shared__ uint32_t s_m[8];
+    if (threadIdx.x < 8) s_m[threadIdx.x] = 0u;
+    __syncthreads();
+    const uint2 v = reinterpret_cast<const uint2*>(p.labels + b * 512)[threadIdx.x]; // 8 voxels per lane
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const uint32_t l = ((i < 4 ? v.x : v.y) >> (8 * (i & 3))) & 255u;
+        atomicOr(&s_m[l >> 5], 1u << (l & 31));
+    }
+    __syncthreads();
+    if (threadIdx.x < 8) p.masks[b * 8 + threadIdx.x] = s_m[threadIdx.x];
+}
+
+hipError_t launch_label_brick_masks(const LabelBrickParams& p, hipStream_t s)
+{
+    const long n = (long) (p.b1[0] - p.b0[0]) * (p.b1[1] - p.b0[1]) * (p.b1[2] - p.b0[2]);
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_label_brick_masks, dim3((unsigned) n), dim3(64), 0, s, p);
+    return hipGetLastError();
+}
+
+// Per brick: does it hold a label whose colour alpha is > 0 (one bit per brick, as k_brick_empty writes them); and the volume's
+// label set (the OR of the bricks' sets).
+__global__ __launch_bounds__(256) void k_label_live(const LabelLiveParams p)
+{
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    uint32_t m[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    bool live = false;
+    if (b < p.n_bricks) {
+#pragma unroll
+        for (int w = 0; w < 8; ++w) {
+            m[w] = p.masks[(size_t) b * 8 + w];
+            live = live || (m[w] & p.alive[w]) != 0u;
+        }
+    }
+    const unsigned long long lv = __ballot(live);
+    const int lane = threadIdx.x & 63;
+    if (lane == 0) p.live[(blockIdx.x * 256 + threadIdx.x) >> 5] = (uint32_t) lv;
+    if (lane == 32) p.live[(blockIdx.x * 256 + threadIdx.x) >> 5] = (uint32_t) (lv >> 32);
+#pragma unroll
+    for (int w = 0; w < 8; ++w) {
+        uint32_t x = m[w];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) x |= __shfl_xor(x, o, 64);
+        if (lane == 0 && x) atomicOr(&p.present[w], x);
+    }
+}
+
+hipError_t launch_label_live(const LabelLiveParams& p, hipStream_t s)
+{
+    if (p.n_bricks == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_label_live, dim3((p.n_bricks + 255) / 256), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+// empty_lab(b) = empty(b) && no live label brick within Chebyshev distance 1 of b, neighbours addressed like the sampler's
+// bricks (wrap: a torus; clamp: the edge brick repeats). Why one brick suffices: a sample at position q (within rounding of the
+// unit cube: the march never leaves it by more than that) has its data base tap at ix = floor(q N - 1/2) in [-1, N - 1] and its
+// label voxel at rint((N - 1) saturate(q)); (N - 1) q = (q N - 1/2) + (1/2 - q) lies within 1/2 of q N - 1/2, so the label voxel
+// is ix - 1, ix or ix + 1, clipped to [0, N - 1]: within one brick of the base tap's brick, or, where wrap addressing sends
+// ix = -1 to the last brick, in brick 0, its torus neighbour.
+template <int MODE>
+__global__ __launch_bounds__(256) void k_label_merge(const LabelMergeParams p)
+{
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    const int nb = p.bn[0] * p.bn[1] * p.bn[2];
+    bool empty = false;
+    if (b < nb) {
+        empty = ((p.empty[b >> 5] >> (b & 31)) & 1u) != 0u;
+        const int c0 = b % p.bn[0], c1 = (b / p.bn[0]) % p.bn[1], c2 = b / (p.bn[0] * p.bn[1]);
+        for (int dz = -1; dz <= 1 && empty; ++dz)
+            for (int dy = -1; dy <= 1 && empty; ++dy)
+                for (int dx = -1; dx <= 1 && empty; ++dx) {
+                    const int q = (address<MODE>(c2 + dz, p.bn[2]) * p.bn[1] + address<MODE>(c1 + dy, p.bn[1])) * p.bn[0] + address<MODE>(c0 + dx, p.bn[0]);
+                    if ((p.live[q >> 5] >> (q & 31)) & 1u) empty = false;
+                }
+    }
+    const unsigned long long m = __ballot(empty);
+    const int lane = threadIdx.x & 63;
+    if (lane == 0) p.out[(blockIdx.x * 256 + threadIdx.x) >> 5] = (uint32_t) m;
+    if (lane == 32) p.out[(blockIdx.x * 256 + threadIdx.x) >> 5] = (uint32_t) (m >> 32);
+}
+
+hipError_t launch_label_merge(const LabelMergeParams& p, int addr_mode, hipStream_t s)
+{
+    const int nb = p.bn[0] * p.bn[1] * p.bn[2];
+    if (nb == 0) return hipSuccess;
+    if (addr_mode == ADDR_CLAMP) hipLaunchKernelGGL(k_label_merge<ADDR_CLAMP>, dim3((nb + 255) / 256), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(k_label_merge<ADDR_WRAP>, dim3((nb + 255) / 256), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+// A dense x-fastest sub-box of the label volume into its bricked place (tbrm_update_label_region): one thread per voxel.
+__global__ __launch_bounds__(256) void k_label_region(const LabelRegionParams p)
+{
+    const size_t n = (size_t) p.extent[0] * p.extent[1] * p.extent[2];
+    const size_t i = (size_t) blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int x = p.origin[0] + (int) (i % p.extent[0]), y = p.origin[1] + (int) ((i / p.extent[0]) % p.extent[1]);
+    const int z = p.origin[2] + (int) (i / ((size_t) p.extent[0] * p.extent[1]));
+    p.dst[brick_off(x, y, z, p.bnx, p.bnxy)] = p.src[i];
+}
+
+hipError_t launch_label_region(const LabelRegionParams& p, hipStream_t s)
+{
+    const size_t n = (size_t) p.extent[0] * p.extent[1] * p.extent[2];
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_label_region, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
 __global__ void k_selftest_decode(float* u8, float* u16)
 {
     const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
