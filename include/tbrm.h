@@ -180,7 +180,8 @@ TBRM_API int tbrm_device_count(int* out_count);   /* TBRM_ERR_NO_DEVICE when the
  * load; 4 / 8), chain_fast_loop (1), chain_rect_planes (1), occ_overlap (2 = workgroups per CU of an occlusion launch that
  * runs beside a chunked chain; 0 = one after the other), light_sweep (1 = axis passes take the pipelined sweep kernel where
  * it applies; 2 = except the passes of a Change whose two lights pull opposite ways, which otherwise take two sweeps; 0 = the
- * chunked chain everywhere), sweep_prefetch (0 = 2 slices), stream_priority (of a handle's own stream, read by tbrm_resources_create: 0 = default, 1 = highest, -1 = lowest),
+ * chunked chain everywhere), sweep_prefetch (accepted, no effect: a sweep tile requests its neighbours' hand-off
+ * words a distance fixed per kernel instantiation ahead — 2 slices, 3 for six-chunk records), stream_priority (of a handle's own stream, read by tbrm_resources_create: 0 = default, 1 = highest, -1 = lowest),
  * sweep_debug (diagnostics: bit 0 tiles do not
  * wait for each other, bits 3 / 4 skip buffer hazards — WRONG light volumes —; bit 1 prints per-tile time stamps at tbrm_flush,
  * bit 2 the host's time per operator phase, bit 5 leaves out the events behind tbrm_last_gpu_time_ms), occ_dual (1 = the two

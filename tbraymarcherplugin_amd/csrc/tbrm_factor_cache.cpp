@@ -342,7 +342,7 @@ static size_t pass_blocks_max(const tbrm_resources* r, size_t* slice_elems_max, 
         const int W = r->lv_dims[u], H = r->lv_dims[v], D = ceil_div(r->lv_dims[a], 8) * 8;
         best = std::max(best, (size_t) ceil_div(W, 16) * ceil_div(H, 16) * (size_t) (D / 8));
         elems = std::max(elems, (size_t) W * H);
-        tiles = std::max(tiles, ceil_div(W, kSweepTile) * ceil_div(H, sweep_tile_rows()));
+        tiles = std::max(tiles, ceil_div(W, kSweepTile) * ceil_div(H, kSweepTile));
         depth = std::max(depth, D);
     }
     if (slice_elems_max) *slice_elems_max = elems;
@@ -374,10 +374,10 @@ int reserve_resources(tbrm_resources* r, int n_lights, unsigned flags)
     if (eager) {
         const size_t gw = r->lv_fmt != FMT_U8 ? 4 : 1;
         // (reach 4 where that is small — a volume of up to 256^3 —, else 2)
-        const int reach = (size_t) depth * (size_t) tiles * (size_t) sweep_record_words(4, 4, sweep_tile_rows()) * gw * 4 <= ((size_t) 64 << 20) ? 4 : 2;
-        const size_t words = (size_t) depth * (size_t) tiles * (size_t) sweep_record_words(reach, reach, sweep_tile_rows()) * gw;
+        const int reach = (size_t) depth * (size_t) tiles * (size_t) sweep_record_words(4, 4) * gw * 4 <= ((size_t) 64 << 20) ? 4 : 2;
+        const size_t words = (size_t) depth * (size_t) tiles * (size_t) sweep_record_words(reach, reach) * gw;
         // (chained passes have a region of the first buffer each: kSweepChainMax passes of reach 1, or two of reach 2)
-        const size_t first = std::max(words, (size_t) kSweepChainMax * (((size_t) depth * (size_t) tiles * (size_t) sweep_record_words(reach, reach, sweep_tile_rows()) + 63) & ~(size_t) 63));
+        const size_t first = std::max(words, (size_t) kSweepChainMax * (((size_t) depth * (size_t) tiles * (size_t) sweep_record_words(reach, reach) + 63) & ~(size_t) 63));
         if (first < ((size_t) 1 << 32))
             if (int e = ensure_sweep(r, std::max<size_t>(first, 1), words, (size_t) tiles)) return e;
     }

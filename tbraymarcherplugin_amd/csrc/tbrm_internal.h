@@ -183,7 +183,9 @@ struct SweepParams {
     uint32_t r_epoch;
     uint32_t* rec[2];       // [0]: the hand-off records, [slice of the launch][tile][32*hx + 32*hy words]; [1]: r_from_records
     uint32_t epoch;         // this launch's tag, 1 .. 2^16 - 1 (records are not cleared between launches)
-    int prefetch;           // slices ahead of their use that the neighbours' records are requested
+    int unused0;            // (0; read by nothing. It and unused1 keep every other field where it is in the kernel-argument segment: without
+                            // them the compiler pairs the scalar loads of the arguments differently, and the scalar register allocation
+                            // and SGPR spill counts of the sweep kernels move — a layout change wants a measurement of its own)
     int stagger_ns;         // a tile d tiles away from the upstream corner starts d * stagger_ns late: the distance it would
                             // otherwise fall behind by polling (a tile can never make up lag, and every poll that finds nothing
                             // costs a memory round trip: arriving late on purpose is cheaper than arriving early)
@@ -192,7 +194,7 @@ struct SweepParams {
     int debug;              // diagnostics (sweep_debug tunable): bit 0 = tiles do not wait for each other (WRONG results: slice time alone);
                             // bit 1 = every tile leaves four time stamps (10 ns units) in `stamps`
     unsigned long long* stamps; // [tile][4]: start of slice 0, end of slice 63, end of the last slice, after the write-back
-    int tile_rows;          // height of a tile: 32, or 16 (two workgroups per CU; tbrm_light_sweep.h sweep_tile_rows); a tile is 32 wide
+    int unused1;            // (0; see unused0)
     int lv_f32;             // the light volume (and the planes) are floats: k_light_sweep<..., FMT_F32>, record words are 8-byte {float, launch tag} granules
     int reinit_slice;       // > 0: the launch's first reinit_slice slices lie in front of the volume (a pass that runs downwards from a
                             // depth that is no multiple of 8, padded to whole brick layers): slice reinit_slice - 1 hands on the pass's
@@ -336,7 +338,8 @@ enum Tunable : int {
     TUNE_CHAIN_RECT_PLANES,  // 0: no 72 x 48 LDS planes (a pass with taps two texels wide along x runs 8-slice chunks in square planes)
     TUNE_OCC_OVERLAP,        // workgroups per CU of an occlusion launch that runs beside the previous span's chain (0: never beside it)
     TUNE_LIGHT_SWEEP,        // 0: axis passes never take the pipelined sweep kernel (k_light_sweep); 1: where it applies
-    TUNE_SWEEP_PREFETCH,     // slices ahead that a sweep tile requests its neighbours' hand-off records (0: default)
+    TUNE_SWEEP_PREFETCH,     // accepted, no effect (the name is part of the C-ABI's documented surface): the distance a sweep tile requests its
+                             // neighbours' hand-off words ahead is fixed per kernel instantiation — 2 slices, 3 for six-chunk records
     TUNE_STREAM_PRIORITY,    // priority of a handle's own stream, read when the handle is created: 0 = default, 1 = the highest the
                              // device offers, -1 = the lowest
     TUNE_SWEEP_DEBUG,        // diagnostics. 1: sweep tiles do not wait for each other (WRONG results), 2: per-tile time stamps, 4: host

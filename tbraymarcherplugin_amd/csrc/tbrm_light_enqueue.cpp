@@ -415,7 +415,7 @@ int enqueue_sweep_pair(tbrm_resources* r, const PassPlan& pa, const PassPlan& pb
     SweepParams q = pa.sq;
     q.sx = fit.sx; q.sy = fit.sy; q.hx = fit.hx; q.hy = fit.hy;
     q.r_from_records = 0;
-    const size_t words = (size_t) pa.D * p.tiles_x * p.tiles_y * (size_t) sweep_record_words(fit.hx, fit.hy, q.tile_rows);
+    const size_t words = (size_t) pa.D * p.tiles_x * p.tiles_y * (size_t) sweep_record_words(fit.hx, fit.hy);
     if (words >= ((size_t) 1 << 32)) return fail(TBRM_ERR_UNSUPPORTED, "hand-off records too large");
     if (int e = ensure_sweep(r, std::max<size_t>(words, 1), 0)) return e;
     q.rec[0] = r->sweep_rec[0];
@@ -461,7 +461,7 @@ int enqueue_sweep_chain(tbrm_resources* r, const PassPlan* plans, int n)
     int tiles_max = 0;
     for (int k = 0; k < n; ++k) {
         const PassPlan& plan = plans[k];
-        const size_t words = (size_t) plan.D * plan.p.tiles_x * plan.p.tiles_y * (size_t) sweep_record_words(plan.sq.hx, plan.sq.hy, plan.sq.tile_rows);
+        const size_t words = (size_t) plan.D * plan.p.tiles_x * plan.p.tiles_y * (size_t) sweep_record_words(plan.sq.hx, plan.sq.hy);
         offset[k + 1] = offset[k] + ((words + 63) & ~(size_t) 63);
         tiles_max = std::max(tiles_max, plan.p.tiles_x * plan.p.tiles_y);
     }

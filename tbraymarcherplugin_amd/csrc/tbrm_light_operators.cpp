@@ -126,7 +126,7 @@ static int run_passes(tbrm_resources* r, const PropParams& base, std::vector<Pas
         if (k >= specs.size() || !chunked[k] || is_second[k] || partner[k] >= 0) return false;
         const PassPlan& pl = plans[k];
         return pl.sweep && (pl.mode == PASS_ADD || pl.mode == PASS_CHANGE) && !pl.sq.r_from_records && !pl.sq.lv_f32 && !(pl.sq.debug & 1) &&
-               sweep_halo_chunks(pl.sq.hx, pl.sq.hy, pl.sq.tile_rows) <= 3;
+               sweep_halo_chunks(pl.sq.hx, pl.sq.hy) <= 3;
     };
     for (size_t i = 0; i < specs.size(); ++i) {
         if (is_second[i]) continue; // (took its turn with its partner)

@@ -90,8 +90,7 @@ bool sweep_fit(const tbrm_resources* r, const tbrm_light_pass& pa, const tbrm_li
         fit.hx = std::max(fit.hx, tx.reach);
         fit.hy = std::max(fit.hy, ty.reach);
     }
-    const int th = sweep_tile_rows();
-    if (!opposite) return fit.hx <= 14 && fit.hy <= 14 && sweep_halo_chunks(fit.hx, fit.hy, th) <= (f32 ? 3 : 6);
+    if (!opposite) return fit.hx <= 14 && fit.hy <= 14 && sweep_halo_chunks(fit.hx, fit.hy) <= (f32 ? 3 : 6);
     if (tune(TUNE_LIGHT_SWEEP) == 2) return false; // (diagnostics: such passes take the chain, as before round 3's last week)
     fit.two_way = true;
     fit.sx = side[0][0].side; fit.hx = side[0][0].reach; fit.sy = side[0][1].side; fit.hy = side[0][1].reach;
@@ -103,7 +102,7 @@ bool sweep_fit(const tbrm_resources* r, const tbrm_light_pass& pa, const tbrm_li
         for (int si = 0; si < 2; ++si) (side[si][ax].side < 0 ? lo : hi) = std::max(side[si][ax].side < 0 ? lo : hi, side[si][ax].reach);
         room[ax] = lo + hi;
     }
-    return room[0] <= 14 && room[1] <= 14 && sweep_halo_chunks(fit.hx, fit.hy, th) <= (f32 ? 3 : 6) && sweep_halo_chunks(fit.r_hx, fit.r_hy, th) <= (f32 ? 3 : 6);
+    return room[0] <= 14 && room[1] <= 14 && sweep_halo_chunks(fit.hx, fit.hy) <= (f32 ? 3 : 6) && sweep_halo_chunks(fit.r_hx, fit.r_hy) <= (f32 ? 3 : 6);
 }
 
 // Why sweep_fit declines a one-stream pass (tbrm_host_plan_light; diagnostics): 0 it does not, 1 previous-slice taps on both sides of
@@ -117,7 +116,7 @@ int sweep_decline_reason(const tbrm_resources* r, const tbrm_light_pass& pa)
     const TapSide tx = prev_tap_side(pa.td[0], pa.prev_pixel_offset[0]), ty = prev_tap_side(pa.td[1], pa.prev_pixel_offset[1]);
     if (!tx.ok || !ty.ok) return 1;
     if (tx.reach > 14 || ty.reach > 14) return 2;
-    if (sweep_halo_chunks(tx.reach, ty.reach, sweep_tile_rows()) > (r->lv_fmt != FMT_U8 ? 3 : 6)) return 3;
+    if (sweep_halo_chunks(tx.reach, ty.reach) > (r->lv_fmt != FMT_U8 ? 3 : 6)) return 3;
     return 0;
 }
 
@@ -474,6 +473,7 @@ static void fill_pass_params(const tbrm_resources* r, const PropParams& base, co
     plan.D = pa.td[2];
     plan.start = pa.start;
     plan.dir = pa.dir;
+    static_assert(kSweepTile == kChunkTile, "the sweep and the chain walk the same 32 x 32 tiles");
     p.tiles_x = ceil_div(W, kChunkTile);
     p.tiles_y = ceil_div(H, kChunkTile);
     p.tile_row0 = 0;
@@ -609,18 +609,14 @@ static int plan_pass_sweep(tbrm_resources* r, const PropParams& base, const tbrm
     q.sx = sfit.sx; q.sy = sfit.sy; q.hx = sfit.hx; q.hy = sfit.hy;
     q.r_from_records = sfit.two_way ? 1 : 0;
     q.r_sx = sfit.r_sx; q.r_sy = sfit.r_sy; q.r_hx = sfit.r_hx; q.r_hy = sfit.r_hy;
-    q.tile_rows = sweep_tile_rows(); // (the sweep's tiles: 32 wide, 16 or 32 high)
-    p.tiles_y = ceil_div(p.H, q.tile_rows);
-    const size_t words = (size_t) D * p.tiles_x * p.tiles_y * (size_t) sweep_record_words(sfit.hx, sfit.hy, q.tile_rows) * (size_t) (r->lv_fmt != FMT_U8 && change && !sfit.two_way ? 2 : 1); // (float records: a granule per stream handed over)
-    const size_t words1 = sfit.two_way ? (size_t) D * p.tiles_x * p.tiles_y * (size_t) sweep_record_words(sfit.r_hx, sfit.r_hy, q.tile_rows) : 0;
+    const size_t words = (size_t) D * p.tiles_x * p.tiles_y * (size_t) sweep_record_words(sfit.hx, sfit.hy) * (size_t) (r->lv_fmt != FMT_U8 && change && !sfit.two_way ? 2 : 1); // (float records: a granule per stream handed over)
+    const size_t words1 = sfit.two_way ? (size_t) D * p.tiles_x * p.tiles_y * (size_t) sweep_record_words(sfit.r_hx, sfit.r_hy) : 0;
     if (words >= ((size_t) 1 << 32) || words1 >= ((size_t) 1 << 32)) return declined("hand-off records too large");
     const size_t gw = r->lv_fmt != FMT_U8 ? 2 : 1; // 32-bit words per record word (float light volumes: {float, launch tag})
     if (words * gw >= ((size_t) 1 << 32) || words1 * gw >= ((size_t) 1 << 32)) return declined("hand-off records too large");
     if (int e = ensure_sweep(r, std::max<size_t>(words * gw, 1), words1 * gw)) return e;
     // (the record buffers may still grow while the operator's other passes are planned: taken at enqueue time)
-    // (measured at 512^3, profiles/r03_sweep_ablation.txt: requests two slices ahead beat three by 3 - 4 %, start delays of 1 - 2 us
-    // per hop tie and beat 3 - 4 us)
-    q.prefetch = tune(TUNE_SWEEP_PREFETCH) > 0 ? std::min(tune(TUNE_SWEEP_PREFETCH), 6) : 2;
+    // (measured at 512^3, profiles/r03_sweep_ablation.txt: start delays of 1 - 2 us per hop tie and beat 3 - 4 us)
     q.stagger_ns = 1500;
     q.debug = tune(TUNE_SWEEP_DEBUG);
     q.reinit_slice = pa.dir < 0 ? pad : 0;

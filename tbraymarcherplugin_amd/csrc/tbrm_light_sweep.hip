@@ -57,51 +57,40 @@ __device__ __forceinline__ W sweep_load_word(const W* p) { return __hip_atomic_l
 template <class W>
 __device__ __forceinline__ void sweep_store_word(W* p, W w) { __hip_atomic_store(p, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// The slow path of a hand-off: the neighbour has not published the word yet. Its load is inline assembly so that the
-// compiler's wait-count bookkeeping of the caller never sees a loop with a memory operation in it (it would answer with
-// s_waitcnt vmcnt(0) at every later use of a request that is still in flight).
-__device__ __noinline__ uint32_t sweep_poll(const uint32_t* src, uint32_t epoch, int* error, unsigned long long give_up_ticks)
+// The slow path of a wait for another tile's word: it is not there yet. W is the word (uint32_t or uint64_t), arrived(w) says
+// whether it is, SLEEP is the pause between two looks. The load is inline assembly so that the compiler's wait-count bookkeeping
+// of the caller never sees a loop with a memory operation in it (it would answer with s_waitcnt vmcnt(0) at every later use of a
+// request that is still in flight); for the same reason the three callers below are not inlined.
+template <int SLEEP, class W, class F>
+__device__ __forceinline__ W sweep_poll_until(const W* src, int* error, unsigned long long give_up_ticks, F arrived)
 {
-    uint32_t w = 0;
+    W w = 0;
     const unsigned long long t0 = wall_clock64(); // (100 MHz, constant: a starved or shared device gets wall time, not a poll count)
     for (;;) {
-        asm volatile("global_load_dword %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(w) : "v"(src) : "memory");
-        if ((w >> 16) == epoch) return w;
+        if constexpr (sizeof(W) == 8) asm volatile("global_load_dwordx2 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(w) : "v"(src) : "memory");
+        else asm volatile("global_load_dword %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(w) : "v"(src) : "memory");
+        if (arrived(w)) return w;
         if (wall_clock64() - t0 >= give_up_ticks) break;
-        __builtin_amdgcn_s_sleep(2);
+        __builtin_amdgcn_s_sleep(SLEEP);
     }
     atomicOr(error, 1);
     return w;
+}
+// a hand-off: the neighbour has not published the word yet
+__device__ __noinline__ uint32_t sweep_poll(const uint32_t* src, uint32_t epoch, int* error, unsigned long long give_up_ticks)
+{
+    return sweep_poll_until<2>(src, error, give_up_ticks, [=](uint32_t w) { return (w >> 16) == epoch; });
 }
 // float light volumes: a record word is {float, launch tag} in one 8-byte granule (one store, one load: nothing can tear)
 __device__ __noinline__ uint64_t sweep_poll(const uint64_t* src, uint32_t epoch, int* error, unsigned long long give_up_ticks)
 {
-    uint64_t w = 0;
-    const unsigned long long t0 = wall_clock64();
-    for (;;) {
-        asm volatile("global_load_dwordx2 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(w) : "v"(src) : "memory");
-        if ((uint32_t) (w >> 32) == epoch) return w;
-        if (wall_clock64() - t0 >= give_up_ticks) break;
-        __builtin_amdgcn_s_sleep(2);
-    }
-    atomicOr(error, 1);
-    return w;
+    return sweep_poll_until<2>(src, error, give_up_ticks, [=](uint64_t w) { return (uint32_t) (w >> 32) == epoch; });
 }
-
-// CHAIN (k_light_sweep_chain, tbrm_internal.h SweepLink): the slow path of waiting for the pass before — the tile that owns the
-// bricks about to be read has not written them back yet. Same form as sweep_poll.
+// CHAIN (k_light_sweep_chain, tbrm_internal.h SweepLink): waiting for the pass before — the tile that owns the bricks about to be
+// read has not written them back yet
 __device__ __noinline__ uint32_t sweep_poll_progress(const uint32_t* src, uint32_t epoch, uint32_t needed, int* error, unsigned long long give_up_ticks)
 {
-    uint32_t w = 0;
-    const unsigned long long t0 = wall_clock64();
-    for (;;) {
-        asm volatile("global_load_dword %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(w) : "v"(src) : "memory");
-        if ((w >> 16) == epoch && (w & 0xffffu) >= needed) return w;
-        if (wall_clock64() - t0 >= give_up_ticks) break;
-        __builtin_amdgcn_s_sleep(8);
-    }
-    atomicOr(error, 1);
-    return w;
+    return sweep_poll_until<8>(src, error, give_up_ticks, [=](uint32_t w) { return (w >> 16) == epoch && (w & 0xffffu) >= needed; });
 }
 // 16 bytes of the light volume past the XCD's L2 in both directions (MI355X_MICROARCH.md: "16-B sc1 stores AND sc1 loads")
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
@@ -170,15 +159,14 @@ __device__ __forceinline__ v2f quantize2_unfloored(v2f x) // (>= 0.5: the conver
 // reference's expression (ChangeDirLightShader.usf:152-154).
 // CHAIN: the tile belongs to one of several passes of ONE launch (k_light_sweep_chain; SweepLink says how it waits for the pass
 // before and what it publishes for the pass behind); `ticket` is the tile's ticket within its pass.
-template <int MODE, int AXIS, int PF, int HC, bool RREC, int LFMT, int TH, bool CHAIN>
+template <int MODE, int AXIS, int PF, int HC, bool RREC, int LFMT, bool CHAIN>
 __device__ __forceinline__ void sweep_tile(const ChunkParams& p, const SweepParams& q, const SweepLink& link, const int ticket)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    static_assert(TH == 32 || TH == 16, "a tile is 32 x 32 or 32 x 16 pixels");
     static_assert(!CHAIN || (LFMT == FMT_U8 && !RREC && (MODE == PASS_ADD || MODE == PASS_CHANGE)), "chained passes: Add / fused Change over a UNORM8 light volume");
-    constexpr int T = kSweepTile, CS = sweep_col_stride(TH), PLANE = sweep_plane(TH), LVB = kSweepLvBrick;
-    constexpr int R = 2, NWC = sweep_compute_waves(TH), NTC = NWC * 64, NT = sweep_threads(MODE, TH);
-    constexpr int NB = sweep_blocks(TH), NBR = sweep_bricks(TH);
+    constexpr int T = kSweepTile, CS = kSweepColStride, PLANE = kSweepPlane, LVB = kSweepLvBrick;
+    constexpr int R = 2, NWC = kSweepComputeWaves, NTC = NWC * 64, NT = sweep_threads(MODE);
+    constexpr int NB = kSweepBlocks, NBR = kSweepBricks;
     constexpr int NS = sweep_two_streams(MODE) ? 2 : 1;
     constexpr bool LV = MODE != PASS_PLANES; // the light volume is updated
     constexpr bool F32 = LFMT == FMT_F32;
@@ -196,7 +184,7 @@ __device__ __forceinline__ void sweep_tile(const ChunkParams& p, const SweepPara
     const int ui = ticket % p.tiles_x, uj = ticket / p.tiles_x;
     const int tile_x = q.sx > 0 ? p.tiles_x - 1 - ui : ui, tile_y = q.sy > 0 ? p.tiles_y - 1 - uj : uj;
     const int tile_lin = tile_y * p.tiles_x + tile_x;
-    const int base_x = tile_x * T, base_y = tile_y * TH;
+    const int base_x = tile_x * T, base_y = tile_y * T;
     const int n = p.n_steps, G = n >> 3; // whole brick layers (the launcher's check)
     const int hx = q.hx, hy = q.hy;
     if constexpr (CHAIN) {
@@ -212,15 +200,10 @@ __device__ __forceinline__ void sweep_tile(const ChunkParams& p, const SweepPara
     float* const lds = (float*) smem;
     auto plane = [&](int buf, int si) -> float* { return lds + (buf * NS + si) * PLANE; };
     uint8_t* const lvt = (uint8_t*) (lds + 2 * NS * PLANE);
-    int32_t* const sslot = (int32_t*) (lvt + (F32 ? 0 : 3 * NBR * LVB)); // [si][2 x TH / 16 blocks][slice group]: rank of the block, < 0: flagged empty
+    int32_t* const sslot = (int32_t*) (lvt + (F32 ? 0 : 3 * NBR * LVB)); // [si][2 x 2 blocks][slice group]: rank of the block, < 0: flagged empty
     // the ring of factor slices, [slot][si][2 x 2 blocks][kSweepFBlock]: filled FS - 1 slices ahead by the loader wave
     float* const fring = (float*) (sslot + NS * NB * G);
-    constexpr int FS = sweep_factor_slots(MODE); // (divides the loop's eight slices: a slice's slot is a constant)
-    // EARLY: what a compute wave reads of the next slice that no other compute wave writes — its factors, the bytes of the voxels it
-    // updates — is read at the END of a slice, in front of the barrier, where the wave would wait anyway: the burst of LDS reads
-    // behind the barrier, which all eight waves start at once and the arithmetic waits for, is a third shorter
-    constexpr bool EARLY_LV = TBRM_SWEEP_EARLY_READS != 0;   // the voxels' bytes
-    constexpr bool EARLY = EARLY_LV && FS >= 8;              // ... and the factors (the loader lands a slice one barrier earlier: a ring of eight)
+    constexpr int FS = kSweepFactorSlots; // (the loop's eight slices: a slice's slot is a constant)
     constexpr int kFSlot = NS * NB * kSweepFBlock; // floats per slot
     auto stream = [&](int si) -> const ChunkStream& { return si == 0 ? p.a : p.r; };
 
@@ -248,7 +231,7 @@ __device__ __forceinline__ void sweep_tile(const ChunkParams& p, const SweepPara
         sslot[i] = slot;
     }
 
-    // ---- light-volume bricks: a layer = the 4 x TH / 8 bricks under the tile, in pieces of 16 bytes, one per compute thread ----
+    // ---- light-volume bricks: a layer = the 4 x 4 bricks under the tile, in pieces of 16 bytes, one per compute thread ----
     constexpr int dim_u = AXIS == 0 ? 1 : 0, dim_v = AXIS == 2 ? 1 : 2, dim_s = AXIS; // plane axes -> volume axes
     const int lbn[3] = {p.lv_bnx, p.lv_bnxy / p.lv_bnx, (p.lv_dims[2] + 7) >> 3};
     const int piece = (int) threadIdx.x & (NTC - 1);
@@ -287,7 +270,7 @@ __device__ __forceinline__ void sweep_tile(const ChunkParams& p, const SweepPara
         }
     };
     // CHAIN: which tile of the pass before owns the bricks of this tile's layer g, and how many of ITS layers it must have written
-    // back (SweepLink). The tile's bricks along the pass before's axis a: one layer when a is this pass's axis, else the four (TH / 8)
+    // back (SweepLink). The tile's bricks along the pass before's axis a: one layer when a is this pass's axis, else the four
     // bricks of the tile's extent along a; along the pass before's plane axes they lie inside one of its tiles (a range of bricks
     // under a tile is aligned to it, a single layer lies inside one). Both are affine in the volume layer L = layer_of(g):
     //   progress word  dep_base[dep_c1 * (L >> 2)]      (L >> 2: the tile of the pass before that holds layer L, when this pass's
@@ -307,7 +290,6 @@ __device__ __forceinline__ void sweep_tile(const ChunkParams& p, const SweepPara
         lo[dim_v] = base_y >> 3;
         lo[dim_s] = 0;
         const int lo_a = a == 0 ? lo[0] : (a == 1 ? lo[1] : lo[2]), lo_u = ua == 0 ? lo[0] : lo[1], lo_v = va == 1 ? lo[1] : lo[2];
-        static_assert(TH == 32 || !CHAIN, "chained passes: four brick layers per tile along both plane axes");
         int c0;
         if (dim_s == a) { // same axis: the same tile of the pass before, layer by layer
             c0 = (lo_v >> 2) * link.in_tiles_x + (lo_u >> 2);
@@ -344,7 +326,7 @@ __device__ __forceinline__ void sweep_tile(const ChunkParams& p, const SweepPara
     }
 
     const uint32_t epoch = q.epoch & 0xffffu, tag = epoch << 16;
-    const int RW = TH * hx + T * hy, RWS = RW * NSW;
+    const int RW = T * hx + T * hy, RWS = RW * NSW;
     const uint32_t rec_slice = (uint32_t) (n_tiles * RWS); // words per slice
     __syncthreads(); // planes, flags and the first brick layer are in LDS
     // Staggered start (SweepParams::stagger_ns): the tile's lag behind its upstream neighbours, taken up front
@@ -363,7 +345,7 @@ __device__ __forceinline__ void sweep_tile(const ChunkParams& p, const SweepPara
         // =================================================== the hand-off wave(s) ================================================
         // A tile publishes E_x = its hx columns and E_y = its hy rows on the side AWAY from the light, words [row][column of
         // E_x] then [row of E_y][column]; its halo is the same cells of the three upstream neighbours.
-        const int e0x = q.sx > 0 ? 0 : T - hx, e0y = q.sy > 0 ? 0 : TH - hy;
+        const int e0x = q.sx > 0 ? 0 : T - hx, e0y = q.sy > 0 ? 0 : T - hy;
         int pub_cell[HC];      // LDS cell of the word this lane publishes (chunk h: word 64 h + lane), < 0: none
         bool hal_on[HC];       // this lane fetches halo word 64 h + lane
         int hal_dst[HC];
@@ -374,20 +356,20 @@ __device__ __forceinline__ void sweep_tile(const ChunkParams& p, const SweepPara
             {
                 int cx = 0, cy = 0;
                 const bool on = w < RW;
-                if (w < TH * hx) { cy = w / max(hx, 1); cx = e0x + (w - cy * hx); }
-                else { const int m = w - TH * hx; cy = e0y + m / T; cx = m % T; }
+                if (w < T * hx) { cy = w / max(hx, 1); cx = e0x + (w - cy * hx); }
+                else { const int m = w - T * hx; cy = e0y + m / T; cx = m % T; }
                 pub_cell[h] = on ? (ox + cx) * CS + oy + cy : -1;
             }
-            const int nx = TH * hx, ny = T * hy, nc = hx * hy;
+            const int nx = T * hx, ny = T * hy, nc = hx * hy;
             int ntx = tile_x, nty = tile_y, word = 0, cxh = 0, cyh = 0; // neighbour tile, its word, the halo cell in tile coordinates
             bool on = false;
             if (w < nx) { const int row = w / max(hx, 1), kx = w - row * hx; ntx += q.sx; word = row * hx + kx; cxh = (q.sx > 0 ? T : -hx) + kx; cyh = row; on = true; }
-            else if (w < nx + ny) { const int m = w - nx, ky = m / T, col = m - ky * T; nty += q.sy; word = nx + ky * T + col; cxh = col; cyh = (q.sy > 0 ? TH : -hy) + ky; on = true; }
+            else if (w < nx + ny) { const int m = w - nx, ky = m / T, col = m - ky * T; nty += q.sy; word = nx + ky * T + col; cxh = col; cyh = (q.sy > 0 ? T : -hy) + ky; on = true; }
             else if (w < nx + ny + nc) {
                 const int m = w - nx - ny, ky = m / max(hx, 1), kx = m - ky * hx;
                 ntx += q.sx; nty += q.sy;
                 word = (e0y + ky) * hx + kx;
-                cxh = (q.sx > 0 ? T : -hx) + kx; cyh = (q.sy > 0 ? TH : -hy) + ky;
+                cxh = (q.sx > 0 ? T : -hx) + kx; cyh = (q.sy > 0 ? T : -hy) + ky;
                 on = true;
             }
             // (a neighbour's pixels beyond the buffer are not handed over: their cells hold the border colour from the start)
@@ -403,24 +385,24 @@ __device__ __forceinline__ void sweep_tile(const ChunkParams& p, const SweepPara
         bool rh_on[HC];
         int rh_dst[HC];
         uint32_t rh_src[HC];
-        const int r_RW = TH * q.r_hx + T * q.r_hy;
+        const int r_RW = T * q.r_hx + T * q.r_hy;
         const uint32_t r_rec_slice = (uint32_t) (n_tiles * r_RW);
         if constexpr (RREC) {
             const int rhx = q.r_hx, rhy = q.r_hy;
-            const int re0y = q.r_sy > 0 ? 0 : TH - rhy;
+            const int re0y = q.r_sy > 0 ? 0 : T - rhy;
 #pragma unroll
             for (int h = 0; h < HC; ++h) {
                 const int w = h * 64 + lane;
-                const int nx = TH * rhx, ny = T * rhy, nc = rhx * rhy;
+                const int nx = T * rhx, ny = T * rhy, nc = rhx * rhy;
                 int ntx = tile_x, nty = tile_y, word = 0, cxh = 0, cyh = 0;
                 bool on = false;
                 if (w < nx) { const int row = w / max(rhx, 1), kx = w - row * rhx; ntx += q.r_sx; word = row * rhx + kx; cxh = (q.r_sx > 0 ? T : -rhx) + kx; cyh = row; on = true; }
-                else if (w < nx + ny) { const int m = w - nx, ky = m / T, col = m - ky * T; nty += q.r_sy; word = nx + ky * T + col; cxh = col; cyh = (q.r_sy > 0 ? TH : -rhy) + ky; on = true; }
+                else if (w < nx + ny) { const int m = w - nx, ky = m / T, col = m - ky * T; nty += q.r_sy; word = nx + ky * T + col; cxh = col; cyh = (q.r_sy > 0 ? T : -rhy) + ky; on = true; }
                 else if (w < nx + ny + nc) {
                     const int m = w - nx - ny, ky = m / max(rhx, 1), kx = m - ky * rhx;
                     ntx += q.r_sx; nty += q.r_sy;
                     word = (re0y + ky) * rhx + kx;
-                    cxh = (q.r_sx > 0 ? T : -rhx) + kx; cyh = (q.r_sy > 0 ? TH : -rhy) + ky;
+                    cxh = (q.r_sx > 0 ? T : -rhx) + kx; cyh = (q.r_sy > 0 ? T : -rhy) + ky;
                     on = true;
                 }
                 on = on && (unsigned) ntx < (unsigned) p.tiles_x && (unsigned) nty < (unsigned) p.tiles_y &&
@@ -521,8 +503,7 @@ __device__ __forceinline__ void sweep_tile(const ChunkParams& p, const SweepPara
         for (int g = q.reinit_slice > 0 ? 1 : 0; g < G - 1; ++g) group(g, std::false_type{}, std::false_type{});
         group(G - 1, std::false_type{}, std::true_type{});
         };
-        if constexpr (HW == 1) handoff(std::true_type{}, std::true_type{});
-        else if (wave == NWC) handoff(std::true_type{}, std::false_type{});
+        if (wave == NWC) handoff(std::true_type{}, std::false_type{});
         else handoff(std::false_type{}, std::true_type{});
     } else if (wave >= NWC + HW) {
         // ================================================= the factor loader =====================================================
@@ -569,9 +550,9 @@ __device__ __forceinline__ void sweep_tile(const ChunkParams& p, const SweepPara
                 }
             }
         };
-        // EARLY: the compute waves read slice s + 1's factors at the end of slice s, in front of the barrier: a slice has to have
-        // landed one barrier earlier
-        constexpr int AW = EARLY ? A - 2 : A - 1;
+        // the compute waves read slice s + 1's factors at the end of slice s, in front of the barrier: a slice has to have landed
+        // one barrier earlier
+        constexpr int AW = A - 2;
         static_assert(AW >= 1, "at least one slice of factor loads stays in flight");
         auto landed = [&]() { // everything but the last AW slices' loads
             sweep_wait_loads<AW * L>();
@@ -743,15 +724,14 @@ __device__ __forceinline__ void sweep_tile(const ChunkParams& p, const SweepPara
             lv_prev[lv_at[0]] = (uint8_t) (w0 ? (uint32_t) qn.x : code_old[0]);
             lv_prev[lv_at[1]] = (uint8_t) (w1 ? (uint32_t) qn.y : code_old[1]);
         };
-        // EARLY: read at the end of the slice before
+        // What a compute wave reads of the next slice that no other compute wave writes — its factors (the loader lands a slice one
+        // barrier earlier: a ring of eight), the bytes of the voxels it updates — is read at the END of a slice, in front of the
+        // barrier, where the wave would wait anyway: the burst of LDS reads behind the barrier, which all eight waves start at once
+        // and the arithmetic waits for, is a third shorter (round 5)
         v2f fac_n[NS];
         uint32_t code_n[R] = {0, 0};
 #pragma unroll
-        for (int si = 0; si < NS; ++si) fac_n[si] = (v2f) 1.0f;
-        if constexpr (EARLY) {
-#pragma unroll
-            for (int si = 0; si < NS; ++si) { fac_n[si].x = f_lane[si * NB * kSweepFBlock]; fac_n[si].y = f_lane[si * NB * kSweepFBlock + 16]; }
-        }
+        for (int si = 0; si < NS; ++si) { fac_n[si].x = f_lane[si * NB * kSweepFBlock]; fac_n[si].y = f_lane[si * NB * kSweepFBlock + 16]; }
         auto group = [&](int g, auto first_c, auto last_c) {
             constexpr bool FIRST = decltype(first_c)::value, LAST = decltype(last_c)::value;
             uint8_t* const lv_layer = lvt + (g % 3) * kLvBuf;
@@ -775,19 +755,16 @@ __device__ __forceinline__ void sweep_tile(const ChunkParams& p, const SweepPara
                     *(uint4*) ((uint8_t*) piece_lds + ((g + 1) % 3) * kLvBuf) = lv_next;
                     lv_next = load_layer(g + 2);
                 }
-                // LDS reads: the voxels of the slice before, this slice's taps
+                // LDS reads: this slice's taps (its factors and the voxels of the slice before were read at that slice's end)
                 uint32_t code_old[R] = {0, 0};
                 if constexpr (LVS) {
 #pragma unroll
-                    for (int k = 0; k < R; ++k) code_old[k] = EARLY_LV ? code_n[k] : (uint32_t) lv_prev[lv_at[k]];
+                    for (int k = 0; k < R; ++k) code_old[k] = code_n[k];
                 }
                 // per stream and row: the taps' two columns, each (row iy, row iy + 1)
-                v2f ca[NS][R], cb[NS][R], fac[NS];
-                const float* const f_at = f_lane + (K8 % FS) * kFSlot;
+                v2f ca[NS][R], cb[NS][R];
 #pragma unroll
                 for (int si = 0; si < NS; ++si) {
-                    if constexpr (EARLY) fac[si] = fac_n[si];
-                    else { fac[si].x = f_at[si * NB * kSweepFBlock]; fac[si].y = f_at[si * NB * kSweepFBlock + 16]; }
 #pragma unroll
                     for (int k = 0; k < R; ++k) {
                         const float* const pt = plane(CUR, si) + tap[si][k];
@@ -817,7 +794,7 @@ __device__ __forceinline__ void sweep_tile(const ChunkParams& p, const SweepPara
                     xa[si].y = __builtin_fmaf(wfy[si].y, d1, ca[si][1].x);
                 }
 #pragma unroll
-                for (int si = 0; si < NS; ++si) lv_l[si] = xa[si] * fac[si];
+                for (int si = 0; si < NS; ++si) lv_l[si] = xa[si] * fac_n[si];
                 if constexpr (F32) { // a float buffer returns what was written (:120); the light volume takes L at once
                     if constexpr (LV) {
                         bool real = true; // (not the slices a ragged pass is padded with: in front of a downward pass,
@@ -864,12 +841,12 @@ __device__ __forceinline__ void sweep_tile(const ChunkParams& p, const SweepPara
                         for (int si = 0; si < NS; ++si) lv_l[si] = (v2f) 0.0f;
                     }
                 }
-                if constexpr (EARLY) { // the next slice's factors (landed a barrier ago)
+                { // the next slice's factors (landed a barrier ago)
                     const float* const f_nx = f_lane + ((K8 + 1) % FS) * kFSlot;
 #pragma unroll
                     for (int si = 0; si < NS; ++si) { fac_n[si].x = f_nx[si * NB * kSweepFBlock]; fac_n[si].y = f_nx[si * NB * kSweepFBlock + 16]; }
                 }
-                if constexpr (EARLY_LV && LVS) { // the voxels this slice's L goes to
+                if constexpr (LVS) { // the voxels this slice's L goes to
 #pragma unroll
                     for (int k = 0; k < R; ++k) code_n[k] = lv_prev[lv_at[k]];
                 }
@@ -895,7 +872,7 @@ __device__ __forceinline__ void sweep_tile(const ChunkParams& p, const SweepPara
         if constexpr (LVS) { // the last slice's voxels, then the last layer
             uint32_t code_old[R];
 #pragma unroll
-            for (int k = 0; k < R; ++k) code_old[k] = EARLY_LV ? code_n[k] : (uint32_t) lv_prev[lv_at[k]];
+            for (int k = 0; k < R; ++k) code_old[k] = code_n[k];
             light_volume_update(code_old);
         }
     }
@@ -919,20 +896,20 @@ __device__ __forceinline__ void sweep_tile(const ChunkParams& p, const SweepPara
     }
 }
 
-template <int MODE, int AXIS, int PF, int HC, bool RREC, int LFMT, int TH>
-__global__ __launch_bounds__(sweep_threads(MODE, TH), (TH == 16 && HC <= 3) ? 4 : 1) void k_light_sweep(const ChunkParams p, const SweepParams q)
+template <int MODE, int AXIS, int PF, int HC, bool RREC, int LFMT>
+__global__ __launch_bounds__(sweep_threads(MODE), 1) void k_light_sweep(const ChunkParams p, const SweepParams q)
 {
     __shared__ int s_ticket;
     if (threadIdx.x == 0) s_ticket = atomicAdd(q.ticket, 1);
     __syncthreads();
-    sweep_tile<MODE, AXIS, PF, HC, RREC, LFMT, TH, false>(p, q, SweepLink{}, __builtin_amdgcn_readfirstlane(s_ticket));
+    sweep_tile<MODE, AXIS, PF, HC, RREC, LFMT, false>(p, q, SweepLink{}, __builtin_amdgcn_readfirstlane(s_ticket));
 }
 
 // Up to kSweepChainMax consecutive passes of an operator in ONE launch (SweepChainArgs): tickets run through the passes in order —
 // every tile of pass i in front of every tile of pass i + 1 — and a workgroup becomes whatever tile its ticket says, of whatever
 // axis that pass runs along (the three bodies side by side: the launch's registers and LDS are the largest body's).
-template <int MODE, int PF, int HC, int TH>
-__global__ __launch_bounds__(sweep_threads(MODE, TH), 1) void k_light_sweep_chain(const SweepChainArgs)
+template <int MODE, int PF, int HC>
+__global__ __launch_bounds__(sweep_threads(MODE), 1) void k_light_sweep_chain(const SweepChainArgs)
 {
     // The argument block is read where it lies, in the kernel-argument segment (constant address space: scalar loads), through a
     // pointer — a by-value struct indexed with the pass number would be copied to scratch first (3 KB per lane, every field a
@@ -953,62 +930,59 @@ __global__ __launch_bounds__(sweep_threads(MODE, TH), 1) void k_light_sweep_chai
     const SweepParams q = *(const SweepParams*) &c->pass[pi].q;
     const SweepLink link = *(const SweepLink*) &c->pass[pi].link;
     const int local = t - link.ticket0;
-    if (p.axis == 0) sweep_tile<MODE, 0, PF, HC, false, FMT_U8, TH, true>(p, q, link, local);
-    else if (p.axis == 1) sweep_tile<MODE, 1, PF, HC, false, FMT_U8, TH, true>(p, q, link, local);
-    else sweep_tile<MODE, 2, PF, HC, false, FMT_U8, TH, true>(p, q, link, local);
+    if (p.axis == 0) sweep_tile<MODE, 0, PF, HC, false, FMT_U8, true>(p, q, link, local);
+    else if (p.axis == 1) sweep_tile<MODE, 1, PF, HC, false, FMT_U8, true>(p, q, link, local);
+    else sweep_tile<MODE, 2, PF, HC, false, FMT_U8, true>(p, q, link, local);
 }
 
-template <int MODE, int AXIS, int PF, int HC, int TH, bool RREC = false, int LFMT = FMT_U8>
+template <int MODE, int AXIS, int PF, int HC, bool RREC = false, int LFMT = FMT_U8>
 static hipError_t launch_sweep5(const ChunkParams& p, const SweepParams& q, hipStream_t s)
 {
     static std::atomic<uint64_t> attr_done{0};
-    if (const hipError_t e = allow_big_lds(k_light_sweep<MODE, AXIS, PF, HC, RREC, LFMT, TH>, attr_done, 159 * 1024); e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_light_sweep<MODE, AXIS, PF, HC, RREC, LFMT, TH>), dim3(p.tiles_x * p.tiles_y), dim3(sweep_threads(MODE, TH)), sweep_lds_bytes(MODE, p.n_steps, LFMT, TH), s, p, q);
+    if (const hipError_t e = allow_big_lds(k_light_sweep<MODE, AXIS, PF, HC, RREC, LFMT>, attr_done, 159 * 1024); e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_light_sweep<MODE, AXIS, PF, HC, RREC, LFMT>), dim3(p.tiles_x * p.tiles_y), dim3(sweep_threads(MODE)), sweep_lds_bytes(MODE, p.n_steps, LFMT), s, p, q);
     return hipGetLastError();
 }
 // Requests run two slices ahead of their use (three for the six-chunk records, whose ring of three slices is what fits the
 // registers): distances 3, 4 and 6 lost to 2 in every measurement of rounds 3 and 4 and are not instantiated.
-template <int MODE, int AXIS, int TH>
+template <int MODE, int AXIS>
 static hipError_t launch_sweep4(const ChunkParams& p, const SweepParams& q, hipStream_t s)
 {
-    const int hc = sweep_halo_chunks(q.hx, q.hy, TH);
+    const int hc = sweep_halo_chunks(q.hx, q.hy);
     if (q.lv_f32) { // float light volumes: Add, fused Change, planes; up to three words per lane and stream (sweep_fit)
         if constexpr (MODE == PASS_ADD || MODE == PASS_CHANGE || MODE == PASS_PLANES) {
             if (q.r_from_records) {
                 if constexpr (MODE == PASS_CHANGE) {
-                    if (std::max(hc, sweep_halo_chunks(q.r_hx, q.r_hy, TH)) <= 3) return launch_sweep5<MODE, AXIS, 2, 3, TH, true, FMT_F32>(p, q, s);
+                    if (std::max(hc, sweep_halo_chunks(q.r_hx, q.r_hy)) <= 3) return launch_sweep5<MODE, AXIS, 2, 3, true, FMT_F32>(p, q, s);
                 }
                 return hipErrorInvalidConfiguration;
             }
-            if (hc <= 2) return launch_sweep5<MODE, AXIS, 2, 2, TH, false, FMT_F32>(p, q, s);
-            if (hc <= 3) return launch_sweep5<MODE, AXIS, 2, 3, TH, false, FMT_F32>(p, q, s);
+            if (hc <= 2) return launch_sweep5<MODE, AXIS, 2, 2, false, FMT_F32>(p, q, s);
+            if (hc <= 3) return launch_sweep5<MODE, AXIS, 2, 3, false, FMT_F32>(p, q, s);
         }
         return hipErrorInvalidConfiguration;
     }
     if constexpr (MODE == PASS_CHANGE) {
         if (q.r_from_records) { // (sweep_fit: both streams' words fit three per lane)
-            const int hc2 = std::max(hc, sweep_halo_chunks(q.r_hx, q.r_hy, TH));
-            if (hc2 <= 3) return launch_sweep5<MODE, AXIS, 2, 3, TH, true>(p, q, s);
-            if (hc2 <= 6) return launch_sweep5<MODE, AXIS, 3, 6, TH, true>(p, q, s);
+            const int hc2 = std::max(hc, sweep_halo_chunks(q.r_hx, q.r_hy));
+            if (hc2 <= 3) return launch_sweep5<MODE, AXIS, 2, 3, true>(p, q, s);
+            if (hc2 <= 6) return launch_sweep5<MODE, AXIS, 3, 6, true>(p, q, s);
             return hipErrorInvalidConfiguration;
         }
     }
-    if constexpr (TH == 16) { // (a 32 x 16 tile with a reach of one texel hands 49 words on: one per lane)
-        if (hc <= 1) return launch_sweep5<MODE, AXIS, 2, 1, TH>(p, q, s);
-    }
-    if (hc <= 2) return launch_sweep5<MODE, AXIS, 2, 2, TH>(p, q, s);
-    if (hc <= 3) return launch_sweep5<MODE, AXIS, 2, 3, TH>(p, q, s);
-    if (hc <= 6) return launch_sweep5<MODE, AXIS, 3, 6, TH>(p, q, s); // (six words per lane and stream: a ring of three slices is what fits the registers)
+    if (hc <= 2) return launch_sweep5<MODE, AXIS, 2, 2>(p, q, s);
+    if (hc <= 3) return launch_sweep5<MODE, AXIS, 2, 3>(p, q, s);
+    if (hc <= 6) return launch_sweep5<MODE, AXIS, 3, 6>(p, q, s); // (six words per lane and stream: a ring of three slices is what fits the registers)
     return hipErrorInvalidConfiguration; // (sweep_fit rules these out)
 }
-template <int MODE, int TH>
+template <int MODE>
 hipError_t launch_sweep_unit(const ChunkParams& p, const SweepParams& q, hipStream_t s)
 {
-    return p.axis == 0 ? launch_sweep4<MODE, 0, TH>(p, q, s) : (p.axis == 1 ? launch_sweep4<MODE, 1, TH>(p, q, s) : launch_sweep4<MODE, 2, TH>(p, q, s));
+    return p.axis == 0 ? launch_sweep4<MODE, 0>(p, q, s) : (p.axis == 1 ? launch_sweep4<MODE, 1>(p, q, s) : launch_sweep4<MODE, 2>(p, q, s));
 }
 
 // the chained form: every pass of the launch with the hand-off geometry of the widest (HC chunks of 64 words per slice)
-template <int MODE, int TH>
+template <int MODE>
 hipError_t launch_sweep_chain_unit(const SweepChainArgs& c, hipStream_t s)
 {
     if constexpr (MODE != PASS_ADD && MODE != PASS_CHANGE) return hipErrorInvalidConfiguration;
@@ -1016,9 +990,9 @@ hipError_t launch_sweep_chain_unit(const SweepChainArgs& c, hipStream_t s)
         int hc = 0, grid = 0;
         size_t lds = 0;
         for (int k = 0; k < c.n; ++k) {
-            hc = std::max(hc, sweep_halo_chunks(c.pass[k].q.hx, c.pass[k].q.hy, TH));
+            hc = std::max(hc, sweep_halo_chunks(c.pass[k].q.hx, c.pass[k].q.hy));
             grid += c.pass[k].p.tiles_x * c.pass[k].p.tiles_y;
-            lds = std::max(lds, sweep_lds_bytes(MODE, c.pass[k].p.n_steps, FMT_U8, TH));
+            lds = std::max(lds, sweep_lds_bytes(MODE, c.pass[k].p.n_steps, FMT_U8));
         }
         // ONE workgroup per CU (a one-stream tile takes 80 KiB: two would fit): a tile of the next pass that is resident beside a
         // tile of this one spends the whole pass polling for it (measured: a warm reset 2.94 ms against 1.92) — it is to arrive
@@ -1027,28 +1001,19 @@ hipError_t launch_sweep_chain_unit(const SweepChainArgs& c, hipStream_t s)
         auto go = [&](auto kernel) -> hipError_t {
             static std::atomic<uint64_t> attr_done{0};
             if (const hipError_t e = allow_big_lds(kernel, attr_done, 159 * 1024); e != hipSuccess) return e;
-            hipLaunchKernelGGL(kernel, dim3(grid), dim3(sweep_threads(MODE, TH)), lds, s, c);
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(sweep_threads(MODE)), lds, s, c);
             return hipGetLastError();
         };
-        if (hc <= 2) return go(k_light_sweep_chain<MODE, 2, 2, TH>);
-        if (hc <= 3) return go(k_light_sweep_chain<MODE, 2, 3, TH>);
+        if (hc <= 2) return go(k_light_sweep_chain<MODE, 2, 2>);
+        if (hc <= 3) return go(k_light_sweep_chain<MODE, 2, 3>);
         return hipErrorInvalidConfiguration; // (the host chains passes of up to three chunks)
     }
 }
 
-#ifdef TBRM_SWEEP_UNIT_MODE
-template hipError_t launch_sweep_unit<TBRM_SWEEP_UNIT_MODE, TBRM_SWEEP_UNIT_TH>(const ChunkParams&, const SweepParams&, hipStream_t);
-template hipError_t launch_sweep_chain_unit<TBRM_SWEEP_UNIT_MODE, TBRM_SWEEP_UNIT_TH>(const SweepChainArgs&, hipStream_t);
-#else
-// (no unit named: every mode and tile height in this one translation unit — what a plain `hipcc -c` of this file builds)
-template hipError_t launch_sweep_unit<PASS_ADD, 32>(const ChunkParams&, const SweepParams&, hipStream_t);
-template hipError_t launch_sweep_unit<PASS_CHANGE, 32>(const ChunkParams&, const SweepParams&, hipStream_t);
-template hipError_t launch_sweep_unit<PASS_ADD2, 32>(const ChunkParams&, const SweepParams&, hipStream_t);
-template hipError_t launch_sweep_unit<PASS_PLANES, 32>(const ChunkParams&, const SweepParams&, hipStream_t);
-template hipError_t launch_sweep_unit<PASS_ADD, 16>(const ChunkParams&, const SweepParams&, hipStream_t);
-template hipError_t launch_sweep_unit<PASS_CHANGE, 16>(const ChunkParams&, const SweepParams&, hipStream_t);
-template hipError_t launch_sweep_unit<PASS_ADD2, 16>(const ChunkParams&, const SweepParams&, hipStream_t);
-template hipError_t launch_sweep_unit<PASS_PLANES, 16>(const ChunkParams&, const SweepParams&, hipStream_t);
+#ifndef TBRM_SWEEP_UNIT_MODE
+#error "tbrm_light_sweep.hip is compiled once per sweep mode: -DTBRM_SWEEP_UNIT_MODE=0 (PASS_ADD), 1 (PASS_CHANGE), 2 (PASS_ADD2) or 5 (PASS_PLANES)"
 #endif
+template hipError_t launch_sweep_unit<TBRM_SWEEP_UNIT_MODE>(const ChunkParams&, const SweepParams&, hipStream_t);
+template hipError_t launch_sweep_chain_unit<TBRM_SWEEP_UNIT_MODE>(const SweepChainArgs&, hipStream_t);
 
 } // namespace tbrm
