@@ -76,6 +76,18 @@ KNOWN_MUTATIONS = (
     "light_clamp_addr",    # light volume read with clamp addressing
     "ppo_div_tdx",         # PrevPixelOffset divided by TD.x instead of TD.z
     "change_guard",        # Change given Add's uvw == saturate(uvw) guard
+    # Intensity and Octree render modes (tests/mode_reference.py)
+    "intensity_final_step_saturated",   # the fractional step clip-tested at saturate(CurPos) like the full steps
+    "intensity_material_address_mode",  # data read with the lit material's address mode instead of clamp
+    "intensity_cutoffs",                # the TF path's low / high cut-offs applied to the intensity
+    "octree_round_nearest",             # int3 conversion rounding to nearest
+    "octree_floor_negative",            # int3 conversion as floor: slightly negative coordinates leave the level
+    "octree_z_no_depth_ratio",          # z scaled by the level's depth alone
+    "octree_xy_data_dims",              # x, y scaled by the data's width instead of the pyramid's power of two
+    "octree_load_clamps",               # Load outside the level clamped to the edge texel instead of reading 0
+    "octree_final_step_scaled",         # the fractional step's opacity exponent scaled by FinalStep, as the lit march does
+    "octree_exit_on_final_step",        # the 0.95 exit applied after the fractional step too
+    "pyramid_no_pow2_padding",          # base level at the data's dimensions
 )
 
 
