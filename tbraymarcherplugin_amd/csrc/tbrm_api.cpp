@@ -324,11 +324,9 @@ static int create_impl(const tbrm_resources_desc* desc, const tbrm_slab* owned, 
     r->res_light.hi = r->lbn[2];
     if (owned) { // slab-resident: which brick layers this handle keeps
         const int lz = r->lv_dims[2], dz = desc->dim_z;
-        if (owned->z_begin < 0 || owned->z_end > lz || owned->z_begin >= owned->z_end || owned->z_begin % kChunkTile || owned->z_end % kChunkTile ||
-            lz % kChunkTile) {
+        if (!slab_bounds_ok(lz, *owned)) {
             delete r;
-            return fail(TBRM_ERR_INVALID_ARG, "slab [%d, %d) of a light volume %d deep: bounds and depth must be multiples of %d",
-                        owned->z_begin, owned->z_end, lz, kChunkTile);
+            return fail_slab_bounds(lz, *owned);
         }
         r->resident = true;
         r->owned = *owned;

@@ -1,5 +1,8 @@
 // tbrm_light_enqueue.cpp — a PassPlan's launches on the handle's two streams: block lists and occlusion on the occlusion stream,
-// sweeps / chain chunks / slices on the handle's stream, and the events that order them.
+// sweeps / chain chunks / slices on the handle's stream, and the events that order them. The bookkeeping every kind of sweep launch
+// shares is stated once: where a pass's factors live (factor_stores, bind_sweep_factors), what a launch waits for (wait_for_factors),
+// what it leaves behind (occlusion_recorded, sweep_read_marks), the diagnostics' stamp buffer (ensure_sweep_stamps); so are the
+// read / write buffers of the slice-per-launch form (fill_pass_buffers, slice_buffer, bind_slice_buffers, sliced_plane).
 #include "tbrm_light_passes.h"
 
 namespace tbrm_host {
@@ -116,6 +119,28 @@ static int enqueue_block_lists(tbrm_resources* r, const PassPlan& plan)
     return TBRM_OK;
 }
 
+// Where the factors that a pass's own occlusion computes for its stream si live: stream a's in the cache entry being filled (if the
+// pass has one) and, beyond its capacity, in the pass's scratch buffer; stream r's in the scratch buffer alone
+static void factor_stores(const tbrm_resources* r, const PassPlan& plan, int si, float*& keep, uint32_t& cap, float*& spill)
+{
+    FactorEntry* const e = si == 0 && !plan.f_hit[0] ? plan.f_entry[0] : nullptr;
+    keep = e ? e->base : nullptr;
+    cap = e ? (uint32_t) e->cap_blocks : 0u;
+    spill = r->f_scratch[plan.f_buf].store[si];
+}
+
+// The pass's occlusion is on stream s: what its sweep (ev_ready) and later hits on the entry it fills (ev_filled) wait for
+static int occlusion_recorded(tbrm_resources* r, const PassPlan& plan, hipStream_t s)
+{
+    HIP_TRY(hipEventRecord(r->f_scratch[plan.f_buf].ev_ready, s));
+    if (FactorEntry* const e = plan.f_hit[0] ? nullptr : plan.f_entry[0]) {
+        HIP_TRY(hipEventRecord(e->ev_filled, s));
+        e->enqueued = true;
+    }
+    plan.occ_enqueued = true;
+    return TBRM_OK;
+}
+
 // The occlusion of a sweep pass (plan_pass_sweep): the whole pass's empty-block flags, work list and block ranks, then one
 // launch that leaves the factors of the live blocks block-compact in the cache entry being filled and / or the scratch
 // buffer — all on the occlusion stream, beside whatever the handle's stream is running (the sweep of the pass before, a
@@ -123,8 +148,6 @@ static int enqueue_block_lists(tbrm_resources* r, const PassPlan& plan)
 int enqueue_sweep_occlusion(tbrm_resources* r, const PassPlan& plan)
 {
     if (!plan.sweep || plan.occ_mode < 0 || plan.occ_enqueued) return TBRM_OK;
-    FactorScratch& f = r->f_scratch[plan.f_buf];
-    FactorEntry* const e = plan.f_hit[0] ? nullptr : plan.f_entry[0];
     hipStream_t s = r->occ_stream;
     if (int e2 = order_behind_inputs(r)) return e2;
     // the buffers about to be overwritten may still be read by earlier sweeps
@@ -144,21 +167,11 @@ int enqueue_sweep_occlusion(tbrm_resources* r, const PassPlan& plan)
     // fills what is free; the resident grids that pay beside the chunked chain (occ_overlap) only slow this pair down
     // (measured: cached Change 1.48 ms, 1.58 - 1.68 with 4 - 8 resident workgroups per CU)
     p.occ_grid_cap = 0;
-    p.a.fs_keep = e ? e->base : nullptr;
-    p.a.fs_cap = e ? (uint32_t) e->cap_blocks : 0u;
-    p.a.fs_spill = f.store[0];
-    p.r.fs_keep = nullptr;
-    p.r.fs_cap = 0;
-    p.r.fs_spill = f.store[1];
+    factor_stores(r, plan, 0, p.a.fs_keep, p.a.fs_cap, p.a.fs_spill);
+    factor_stores(r, plan, 1, p.r.fs_keep, p.r.fs_cap, p.r.fs_spill);
     HIP_TRY(launch_light_occlusion(p, plan.occ_mode, s));
     ++r->occ_launches;
-    HIP_TRY(hipEventRecord(f.ev_ready, s));
-    if (e) {
-        HIP_TRY(hipEventRecord(e->ev_filled, s));
-        e->enqueued = true;
-    }
-    plan.occ_enqueued = true;
-    return TBRM_OK;
+    return occlusion_recorded(r, plan, s);
 }
 
 // May ONE occlusion launch serve both passes (tbrm_internal.h DualOcc)? They are passes of the same operator (same volume,
@@ -217,19 +230,12 @@ int enqueue_dual_occlusion(tbrm_resources* r, const PassPlan& pa, const PassPlan
     }
     for (int k = 0; k < 2; ++k) {
         const PassPlan& plan = *plans[k];
-        FactorScratch& f = r->f_scratch[plan.f_buf];
-        FactorEntry* const e = plan.f_hit[0] ? nullptr : plan.f_entry[0];
         if (int e2 = enqueue_block_lists(r, plan)) return e2;
         DualPass& P = d.pass[k];
         P.axis = plan.p.axis; P.start = plan.start; P.dir = plan.dir;
         P.blocks_x = plan.p.occ_blocks_x; P.blocks_y = plan.p.occ_blocks_y;
         P.step100[0] = plan.p.a.step100; P.step100[1] = plan.p.r.step100;
-        P.fs_keep[0] = e ? e->base : nullptr;
-        P.fs_cap[0] = e ? (uint32_t) e->cap_blocks : 0u;
-        P.fs_spill[0] = f.store[0];
-        P.fs_keep[1] = nullptr;
-        P.fs_cap[1] = 0;
-        P.fs_spill[1] = f.store[1];
+        for (int si = 0; si < 2; ++si) factor_stores(r, plan, si, P.fs_keep[si], P.fs_cap[si], P.fs_spill[si]);
         P.fs_slot = plan.lists->slot;
         P.flags = plan.lists->flags;
     }
@@ -249,26 +255,35 @@ int enqueue_dual_occlusion(tbrm_resources* r, const PassPlan& pa, const PassPlan
     pc.occ_grid_cap = 0;
     HIP_TRY(launch_light_occlusion(pc, pa.occ_mode, s, &d));
     ++r->dual_launches;
-    for (int k = 0; k < 2; ++k) {
-        const PassPlan& plan = *plans[k];
-        FactorEntry* const e = plan.f_hit[0] ? nullptr : plan.f_entry[0];
-        HIP_TRY(hipEventRecord(r->f_scratch[plan.f_buf].ev_ready, s));
-        if (e) {
-            HIP_TRY(hipEventRecord(e->ev_filled, s));
-            e->enqueued = true;
-        }
-        plan.occ_enqueued = true;
-    }
+    for (const PassPlan* plan : plans)
+        if (int e2 = occlusion_recorded(r, *plan, s)) return e2;
     return TBRM_OK;
 }
 
-// What a sweep launch of the plan is handed: the pass's parameters with its factor stores, the sweep's with the handle's
-// records, tickets and error word (the launch tag is the caller's: next_sweep_epoch)
-static void sweep_launch_params(tbrm_resources* r, const PassPlan& plan, ChunkParams& p, SweepParams& q)
+// The factor stores of stream si of a sweep launch: the cache entry that holds every live block (a hit), else what this pass's own
+// occlusion computed (factor_stores), under the ranks of the jointly computed work list
+static void bind_sweep_factors(tbrm_resources* r, const PassPlan& plan, int si, ChunkStream& st)
 {
-    FactorScratch& f = r->f_scratch[plan.f_buf];
-    const int ns = plan.n_streams();
+    if (!plan.f_hit[si]) {
+        factor_stores(r, plan, si, st.fs_keep, st.fs_cap, st.fs_spill);
+        st.fs_slot = plan.lists->slot;
+        return;
+    }
+    FactorEntry* const e = plan.f_entry[si];
+    st.fs_keep = e->base; st.fs_cap = (uint32_t) e->cap_blocks; st.fs_spill = nullptr; st.fs_slot = e->lists->slot;
+    e->lists->last_read_op = std::max(e->lists->last_read_op, r->op_serial); // (new_lists: not rewritten under this sweep)
+}
+
+// What a sweep launch of the plan is handed: the pass's parameters with its factor stores, the sweep's with the handle's
+// records, tickets and error word (the launch tag is the caller's: next_sweep_epoch). second (enqueue_sweep_pair): the launch's
+// stream r is that pass's stream a, from its own factors
+static void sweep_launch_params(tbrm_resources* r, const PassPlan& plan, ChunkParams& p, SweepParams& q, const PassPlan* second = nullptr)
+{
     p = plan.p;
+    if (second) {
+        p.r = second->p.a;
+        p.b_added2 = second->p.b_added;
+    }
     p.j0 = plan.start;
     p.n_steps = plan.D;
     p.first_chunk = plan.pass_begins_here ? 1 : 0; // (a slab behind the first continues from the planes it was handed)
@@ -276,27 +291,23 @@ static void sweep_launch_params(tbrm_resources* r, const PassPlan& plan, ChunkPa
     p.a.plane_in = plan_plane(r, 0, 0); p.a.plane_out = plan_plane(r, 1, 0);
     p.r.plane_in = plan_plane(r, 0, 1); p.r.plane_out = plan_plane(r, 1, 1);
     p.ones = r->d_ones;
-    ChunkStream* const streams[2] = {&p.a, &p.r};
-    for (int si = 0; si < ns; ++si) {
-        FactorEntry* const e = plan.f_entry[si];
-        ChunkStream& st = *streams[si];
-        if (plan.f_hit[si]) { // every live block is in the entry
-            st.fs_keep = e->base; st.fs_cap = (uint32_t) e->cap_blocks; st.fs_spill = nullptr; st.fs_slot = e->lists->slot;
-            e->lists->last_read_op = std::max(e->lists->last_read_op, r->op_serial); // (new_lists: not rewritten under this sweep)
-        } else { // computed by this pass: stream a into its entry (if it has one) and the scratch, stream r into the scratch,
-                 // both under the ranks of the jointly computed work list
-            FactorEntry* const filled = plan.f_entry[0];
-            st.fs_keep = (si == 0 && filled) ? filled->base : nullptr;
-            st.fs_cap = (si == 0 && filled) ? (uint32_t) filled->cap_blocks : 0u;
-            st.fs_spill = f.store[si];
-            st.fs_slot = plan.lists->slot;
-        }
-    }
+    bind_sweep_factors(r, plan, 0, p.a);
+    if (second) bind_sweep_factors(r, *second, 0, p.r);
+    else if (plan.n_streams() == 2) bind_sweep_factors(r, plan, 1, p.r);
     q = plan.sq;
     q.rec[0] = r->sweep_rec[0];
     q.rec[1] = r->sweep_rec[1];
     q.ticket = r->sweep_ticket;
     q.error = r->sweep_error;
+}
+
+// What a sweep of the plan waits for on the handle's stream: the occlusion the pass computed, and the cache entries it reads
+static int wait_for_factors(tbrm_resources* r, const PassPlan& plan)
+{
+    if (plan.occ_mode >= 0) HIP_TRY(hipStreamWaitEvent(r->stream, r->f_scratch[plan.f_buf].ev_ready, 0));
+    for (int si = 0; si < plan.n_streams(); ++si)
+        if (plan.f_hit[si]) HIP_TRY(hipStreamWaitEvent(r->stream, plan.f_entry[si]->ev_filled, 0)); // (it may still be being filled)
+    return TBRM_OK;
 }
 
 // who read what: later operators wait for this operator's "sweeps done" event (wait_for_readers); the buffers' own events
@@ -319,15 +330,25 @@ static int sweep_read_marks(tbrm_resources* r, const PassPlan& plan)
     return TBRM_OK;
 }
 
+// diagnostics (sweep_debug bit 2): room for the per-tile time stamps of a launch of `tiles` tiles (printed by tbrm_flush)
+static int ensure_sweep_stamps(tbrm_resources* r, int tiles)
+{
+    if (tiles > r->sweep_stamp_tiles || !r->sweep_stamps) {
+        drain_streams(r);
+        count_alloc(r, 2, "sweep stamps (diagnostics)");
+        (void) hipFree(r->sweep_stamps);
+        r->sweep_stamps = nullptr;
+        HIP_TRY(hipMalloc((void**) &r->sweep_stamps, (size_t) tiles * 4 * sizeof(unsigned long long)));
+    }
+    r->sweep_stamp_tiles = tiles;
+    return TBRM_OK;
+}
+
 // The sweep of a sweep pass on the handle's stream, behind the occlusion it consumes
 static int enqueue_sweep(tbrm_resources* r, const PassPlan& plan)
 {
     if (int e = enqueue_sweep_occlusion(r, plan)) return e;
-    FactorScratch& f = r->f_scratch[plan.f_buf];
-    const int ns = plan.n_streams();
-    if (plan.occ_mode >= 0) HIP_TRY(hipStreamWaitEvent(r->stream, f.ev_ready, 0));
-    for (int si = 0; si < ns; ++si)
-        if (plan.f_hit[si]) HIP_TRY(hipStreamWaitEvent(r->stream, plan.f_entry[si]->ev_filled, 0)); // (it may still be being filled)
+    if (int e = wait_for_factors(r, plan)) return e;
     ChunkParams p;
     SweepParams q;
     sweep_launch_params(r, plan, p, q);
@@ -351,16 +372,8 @@ static int enqueue_sweep(tbrm_resources* r, const PassPlan& plan)
     }
     if (int e = next_sweep_epoch(r, q.epoch)) return e;
     q.stamps = nullptr;
-    if (q.debug & 2) { // diagnostics: per-tile time stamps of this launch (printed by tbrm_flush)
-        const int tiles = p.tiles_x * p.tiles_y;
-        if (tiles > r->sweep_stamp_tiles || !r->sweep_stamps) {
-            drain_streams(r);
-            count_alloc(r, 2, "sweep stamps (diagnostics)");
-            (void) hipFree(r->sweep_stamps);
-            r->sweep_stamps = nullptr;
-            HIP_TRY(hipMalloc((void**) &r->sweep_stamps, (size_t) tiles * 4 * sizeof(unsigned long long)));
-        }
-        r->sweep_stamp_tiles = tiles;
+    if (q.debug & 2) { // diagnostics: per-tile time stamps of this launch
+        if (int e = ensure_sweep_stamps(r, p.tiles_x * p.tiles_y)) return e;
         r->sweep_stamp_chain[0] = 0;
         r->sweep_stamp_tx = p.tiles_x;
         r->sweep_stamp_sx = q.sx;
@@ -383,45 +396,16 @@ int enqueue_sweep_pair(tbrm_resources* r, const PassPlan& pa, const PassPlan& pb
     const PassPlan* const plans[2] = {&pa, &pb};
     for (const PassPlan* plan : plans) {
         if (int e = enqueue_sweep_occlusion(r, *plan)) return e;
-        if (plan->occ_mode >= 0) HIP_TRY(hipStreamWaitEvent(r->stream, r->f_scratch[plan->f_buf].ev_ready, 0));
-        if (plan->f_hit[0]) HIP_TRY(hipStreamWaitEvent(r->stream, plan->f_entry[0]->ev_filled, 0));
+        if (int e = wait_for_factors(r, *plan)) return e;
     }
-    ChunkParams p = pa.p;
-    p.r = pb.p.a;
-    p.b_added2 = pb.p.b_added;
-    p.j0 = pa.start;
-    p.n_steps = pa.D;
-    p.first_chunk = 1;
-    p.occ_phase = 0;
-    p.a.plane_in = plan_plane(r, 0, 0); p.a.plane_out = plan_plane(r, 1, 0);
-    p.r.plane_in = plan_plane(r, 0, 1); p.r.plane_out = plan_plane(r, 1, 1);
-    p.ones = r->d_ones;
-    ChunkStream* const streams[2] = {&p.a, &p.r};
-    for (int si = 0; si < 2; ++si) { // each stream from its own pass's factors (enqueue_sweep, stream a)
-        const PassPlan& plan = *plans[si];
-        FactorScratch& f = r->f_scratch[plan.f_buf];
-        FactorEntry* const e = plan.f_entry[0];
-        ChunkStream& st = *streams[si];
-        if (plan.f_hit[0]) {
-            st.fs_keep = e->base; st.fs_cap = (uint32_t) e->cap_blocks; st.fs_spill = nullptr; st.fs_slot = e->lists->slot;
-            e->lists->last_read_op = std::max(e->lists->last_read_op, r->op_serial);
-        } else {
-            st.fs_keep = e ? e->base : nullptr;
-            st.fs_cap = e ? (uint32_t) e->cap_blocks : 0u;
-            st.fs_spill = f.store[0];
-            st.fs_slot = plan.lists->slot;
-        }
-    }
-    SweepParams q = pa.sq;
-    q.sx = fit.sx; q.sy = fit.sy; q.hx = fit.hx; q.hy = fit.hy;
-    q.r_from_records = 0;
-    const size_t words = (size_t) pa.D * p.tiles_x * p.tiles_y * (size_t) sweep_record_words(fit.hx, fit.hy);
+    const size_t words = (size_t) pa.D * pa.p.tiles_x * pa.p.tiles_y * (size_t) sweep_record_words(fit.hx, fit.hy);
     if (words >= ((size_t) 1 << 32)) return fail(TBRM_ERR_UNSUPPORTED, "hand-off records too large");
     if (int e = ensure_sweep(r, std::max<size_t>(words, 1), 0)) return e;
-    q.rec[0] = r->sweep_rec[0];
-    q.rec[1] = r->sweep_rec[1];
-    q.ticket = r->sweep_ticket;
-    q.error = r->sweep_error;
+    ChunkParams p;
+    SweepParams q;
+    sweep_launch_params(r, pa, p, q, &pb); // (behind ensure_sweep: the records may have grown)
+    q.sx = fit.sx; q.sy = fit.sy; q.hx = fit.hx; q.hy = fit.hy;
+    q.r_from_records = 0;
     q.stamps = nullptr;
     q.debug &= ~2;
     if (int e = next_sweep_epoch(r, q.epoch)) return e;
@@ -429,19 +413,8 @@ int enqueue_sweep_pair(tbrm_resources* r, const PassPlan& pa, const PassPlan& pb
     ++r->launches[0];
     ++r->sweep_launches;
     ++r->pair_sweeps;
-    for (const PassPlan* plan : plans) {
-        FactorScratch& f = r->f_scratch[plan->f_buf];
-        if (r->op_many_passes) HIP_TRY(hipEventRecord(f.ev_idle, r->stream));
-        f.used = true;
-        f.last_read_op = r->op_serial;
-        f.idle_recorded = r->op_many_passes;
-        if (FactorEntry* const e = plan->f_entry[0]) {
-            if (r->op_many_passes) HIP_TRY(hipEventRecord(e->ev_idle, r->stream));
-            e->read_yet = true;
-            e->last_read_op = r->op_serial;
-            e->idle_recorded = r->op_many_passes;
-        }
-    }
+    for (const PassPlan* plan : plans)
+        if (int e = sweep_read_marks(r, *plan)) return e;
     return TBRM_OK;
 }
 
@@ -470,26 +443,16 @@ int enqueue_sweep_chain(tbrm_resources* r, const PassPlan* plans, int n)
     SweepChainArgs c{};
     c.n = n;
     int ticket0 = 0;
-    const bool stamps = (tune(TUNE_SWEEP_DEBUG) & 2) != 0; // diagnostics: per-tile time stamps of this launch (printed by tbrm_flush)
+    const bool stamps = (tune(TUNE_SWEEP_DEBUG) & 2) != 0; // diagnostics: per-tile time stamps of this launch
     if (stamps) {
         int total = 0;
         for (int k = 0; k < n; ++k) total += plans[k].p.tiles_x * plans[k].p.tiles_y;
-        if (total > r->sweep_stamp_tiles || !r->sweep_stamps) {
-            drain_streams(r);
-            count_alloc(r, 2, "sweep stamps (diagnostics)");
-            (void) hipFree(r->sweep_stamps);
-            r->sweep_stamps = nullptr;
-            HIP_TRY(hipMalloc((void**) &r->sweep_stamps, (size_t) total * 4 * sizeof(unsigned long long)));
-        }
-        r->sweep_stamp_tiles = total;
+        if (int e = ensure_sweep_stamps(r, total)) return e;
         for (int k = 0; k < 4; ++k) r->sweep_stamp_chain[k] = k < n ? plans[k].p.tiles_x * plans[k].p.tiles_y : 0;
     }
     for (int k = 0; k < n; ++k) {
         const PassPlan& plan = plans[k];
-        FactorScratch& f = r->f_scratch[plan.f_buf];
-        if (plan.occ_mode >= 0) HIP_TRY(hipStreamWaitEvent(r->stream, f.ev_ready, 0));
-        for (int si = 0; si < plan.n_streams(); ++si)
-            if (plan.f_hit[si]) HIP_TRY(hipStreamWaitEvent(r->stream, plan.f_entry[si]->ev_filled, 0));
+        if (int e = wait_for_factors(r, plan)) return e;
         SweepChainPass& P = c.pass[k];
         sweep_launch_params(r, plan, P.p, P.q);
         P.q.rec[0] = r->sweep_rec[0] + offset[k];
@@ -517,8 +480,46 @@ int enqueue_sweep_chain(tbrm_resources* r, const PassPlan* plans, int n)
     ++r->launches[0];
     ++r->sweep_launches;
     ++r->chain_launches;
-    for (int k = 0; k < n; ++k) sweep_read_marks(r, plans[k]);
+    for (int k = 0; k < n; ++k)
+        if (int e = sweep_read_marks(r, plans[k])) return e;
     return TBRM_OK;
+}
+
+// ---- the slice-per-launch form: the reference's read / write buffers (tbrm_resources::d_buf) ---------------------------------------
+// The buffers of a pass start from the light's initial value (LightingShaders.cpp:74-79): two per stream, the removed light's
+// (a two-stream pass) in 0 / 1 and the added light's behind them
+int fill_pass_buffers(tbrm_resources* r, const tbrm_light_pass& pa, const tbrm_light_pass* pr)
+{
+    const size_t npx = (size_t) pa.td[0] * pa.td[1];
+    int b = 0;
+    for (const tbrm_light_pass* q : {pr, &pa}) {
+        if (!q) continue;
+        for (int k = 0; k < 2; ++k, ++b) HIP_TRY(launch_fill(r->d_buf[pa.axis][b], r->lv_fmt, npx, q->light_alpha, r->stream));
+    }
+    return TBRM_OK;
+}
+
+// Slice j reads the buffer of its parity and writes the other one: read and write buffers switch each slice (LightingShaders.cpp:149-156)
+static void* slice_buffer(const tbrm_resources* r, int ax, int j, bool added_of_two, bool write)
+{
+    const int e = (j % 2 == 0) ? 0 : 1;
+    return r->d_buf[ax][(added_of_two ? 2 : 0) + (write ? 1 - e : e)];
+}
+
+static void bind_slice_buffers(const tbrm_resources* r, PropParams& p, int j, bool change)
+{
+    p.loop = j;
+    p.a.read = slice_buffer(r, p.axis, j, change, false);
+    p.a.write = slice_buffer(r, p.axis, j, change, true);
+    if (!change) return;
+    p.r.read = slice_buffer(r, p.axis, j, false, false);
+    p.r.write = slice_buffer(r, p.axis, j, false, true);
+}
+
+// the read buffer of stream si (0: a, 1: r) before this handle's slice number `boundary` (== n_chunks: what its last slice wrote)
+void* sliced_plane(const tbrm_resources* r, const PassPlan& plan, int boundary, int si)
+{
+    return slice_buffer(r, plan.p.axis, plan.start + boundary * plan.dir, plan.mode != PASS_ADD && si == 0, false);
 }
 
 static bool plan_has_occlusion(const PassPlan& plan) { return !plan.sliced && !plan.sweep && plan.n_chunks > 0; }
@@ -550,18 +551,7 @@ static int enqueue_plan_chunk_impl(tbrm_resources* r, const PassPlan& plan, int 
 {
     if (plan.sliced) {
         PropParams sp = plan.slice_params;
-        const int j = plan.start + c * plan.dir;
-        const int e = (j % 2 == 0) ? 0 : 1, ax = plan.p.axis;
-        sp.loop = j;
-        if (plan.mode == PASS_ADD) {
-            sp.a.read = r->d_buf[ax][e];
-            sp.a.write = r->d_buf[ax][1 - e];
-        } else {
-            sp.r.read = r->d_buf[ax][e];
-            sp.r.write = r->d_buf[ax][1 - e];
-            sp.a.read = r->d_buf[ax][2 + e];
-            sp.a.write = r->d_buf[ax][3 - e];
-        }
+        bind_slice_buffers(r, sp, plan.start + c * plan.dir, plan.mode != PASS_ADD);
         HIP_TRY(launch_propagate_slice(sp, plan.mode != PASS_ADD, r->stream));
         ++r->launches[1];
         return TBRM_OK;
@@ -635,33 +625,13 @@ static int enqueue_plan_chunk_impl(tbrm_resources* r, const PassPlan& plan, int 
 int enqueue_pass_sliced(tbrm_resources* r, PropParams p, const tbrm_light_pass& pa, const tbrm_light_pass* pr)
 {
     const bool change = pr != nullptr;
-    const size_t npx = (size_t) pa.td[0] * pa.td[1];
-    const int ax = pa.axis;
-    if (!change) {
-        HIP_TRY(launch_fill(r->d_buf[ax][0], r->lv_fmt, npx, pa.light_alpha, r->stream));
-        HIP_TRY(launch_fill(r->d_buf[ax][1], r->lv_fmt, npx, pa.light_alpha, r->stream));
-    } else {
-        HIP_TRY(launch_fill(r->d_buf[ax][0], r->lv_fmt, npx, pr->light_alpha, r->stream));
-        HIP_TRY(launch_fill(r->d_buf[ax][1], r->lv_fmt, npx, pr->light_alpha, r->stream));
-        HIP_TRY(launch_fill(r->d_buf[ax][2], r->lv_fmt, npx, pa.light_alpha, r->stream));
-        HIP_TRY(launch_fill(r->d_buf[ax][3], r->lv_fmt, npx, pa.light_alpha, r->stream));
-    }
-    p.axis = ax;
+    if (int e = fill_pass_buffers(r, pa, pr)) return e;
+    p.axis = pa.axis;
     for (int c = 0; c < 3; ++c) p.td[c] = pa.td[c];
     fill_stream(p.a, pa);
     if (change) fill_stream(p.r, *pr);
     for (int j = pa.start; j != pa.stop; j += pa.dir) {
-        p.loop = j;
-        const int e = (j % 2 == 0) ? 0 : 1; // switch read and write buffers each slice
-        if (!change) {
-            p.a.read = r->d_buf[ax][e];
-            p.a.write = r->d_buf[ax][1 - e];
-        } else {
-            p.r.read = r->d_buf[ax][e];
-            p.r.write = r->d_buf[ax][1 - e];
-            p.a.read = r->d_buf[ax][2 + e];
-            p.a.write = r->d_buf[ax][3 - e];
-        }
+        bind_slice_buffers(r, p, j, change);
         HIP_TRY(launch_propagate_slice(p, change, r->stream));
         ++r->launches[1];
     }

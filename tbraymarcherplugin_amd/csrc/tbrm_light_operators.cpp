@@ -13,6 +13,13 @@ struct PassSpec {
     int mode = PASS_ADD;
     float b_added = 0.0f, b_added2 = 0.0f;
 };
+static PassSpec add_spec(const tbrm_light_pass& p, float b_added)
+{
+    PassSpec q;
+    q.a = p;
+    q.b_added = b_added;
+    return q;
+}
 
 // Runs the axis passes of one operator in order. Every pass is planned before anything is enqueued: a pass the chunk
 // kernels decline takes the one-slice-per-launch path, any other planning failure leaves the light volume untouched.
@@ -85,15 +92,20 @@ static int run_passes(tbrm_resources* r, const PropParams& base, std::vector<Pas
         // sharing a sweep needs both passes on the sweep
         pair_sweeps[i] = chunked[i] && chunked[(size_t) j] && plans[i].sweep && plans[(size_t) j].sweep;
     }
+    // The occlusion of pass k, if it is a sweep pass that still has it to compute: with pass k + 1's in ONE launch where the two
+    // sample the same positions (the two passes of a light, dual_fit), else on its own
+    auto occlusion_of = [&](size_t k) -> int {
+        if (k >= specs.size() || !chunked[k]) return TBRM_OK;
+        const bool dual = k + 1 < specs.size() && chunked[k + 1] && dual_fit(plans[k], plans[k + 1]);
+        const int e = dual ? enqueue_dual_occlusion(r, plans[k], plans[k + 1]) : enqueue_sweep_occlusion(r, plans[k]);
+        if (e) quiesce_occ_stream(r);
+        return e;
+    };
     bool any_pair = false;
     for (size_t i = 0; i < specs.size(); ++i) any_pair = any_pair || (partner[i] >= 0 && pair_sweeps[i]);
     if (any_pair) // (a group of two lights: four passes, four scratch buffers — every occlusion can go first)
-        for (size_t k = 0; k < specs.size(); ++k) {
-            if (!chunked[k]) continue;
-            const int e = (k + 1 < specs.size() && chunked[k + 1] && dual_fit(plans[k], plans[k + 1])) ? enqueue_dual_occlusion(r, plans[k], plans[k + 1])
-                                                                                                       : enqueue_sweep_occlusion(r, plans[k]);
-            if (e) { quiesce_occ_stream(r); return e; }
-        }
+        for (size_t k = 0; k < specs.size(); ++k)
+            if (int e = occlusion_of(k)) return e;
     auto run_single = [&](size_t i) -> int {
         const PassSpec& q = specs[i];
         if (!chunked[i]) {
@@ -106,14 +118,9 @@ static int run_passes(tbrm_resources* r, const PropParams& base, std::vector<Pas
         ++r->passes[plans[i].sweep ? 0 : 1];
         const PassPlan* next = i + 1 < specs.size() && chunked[i + 1] ? &plans[i + 1] : nullptr;
         // sweep passes: this pass's occlusion, and the next pass's behind it on the occlusion stream, so that it runs beside
-        // this pass's sweep — the two passes of a light in ONE launch where they sample the same positions (dual_fit)
-        auto occlusion_of = [&](size_t k) -> int {
-            if (k >= specs.size() || !chunked[k]) return TBRM_OK;
-            if (k + 1 < specs.size() && chunked[k + 1] && dual_fit(plans[k], plans[k + 1])) return enqueue_dual_occlusion(r, plans[k], plans[k + 1]);
-            return enqueue_sweep_occlusion(r, plans[k]);
-        };
-        if (int e = occlusion_of(i)) { quiesce_occ_stream(r); return e; }
-        if (int e = occlusion_of(i + 1)) { quiesce_occ_stream(r); return e; }
+        // this pass's sweep
+        if (int e = occlusion_of(i)) return e;
+        if (int e = occlusion_of(i + 1)) return e;
         probe.lap("occlusion");
         for (int c = 0; c < plans[i].n_chunks; ++c)
             if (int e = enqueue_plan_chunk(r, plans[i], c, next)) return e; // (enqueue_plan_chunk has drained the second stream)
@@ -182,12 +189,7 @@ static void add_light_specs(const tbrm_resources* r, const tbrm_dir_light_params
     tbrm_light_pass passes[2];
     int n = 0;
     if (!host_light_passes(light, world, r->lv_dims, r->desc.border_mode, passes, &n)) return; // :41-46
-    for (int i = 0; i < n; ++i) { // breaks on weight == 0 (:65,:94)
-        PassSpec q;
-        q.a = passes[i];
-        q.b_added = added ? 1.0f : -1.0f;
-        specs.push_back(q);
-    }
+    for (int i = 0; i < n; ++i) specs.push_back(add_spec(passes[i], added ? 1.0f : -1.0f)); // breaks on weight == 0 (:65,:94)
 }
 
 // AddDirLightToSingleLightVolume_RenderThread (LightingShaders.cpp:35-166)
@@ -196,6 +198,19 @@ int enqueue_add(tbrm_resources* r, const tbrm_dir_light_params& light, bool adde
     std::vector<PassSpec> specs;
     add_light_specs(r, light, added, world, specs);
     return run_passes(r, base_prop_params(r, world), specs);
+}
+
+// an axis pass of light `light` of a batch (enqueue_add_batch)
+struct BatchEntry { int light, pass; tbrm_light_pass p; bool done; };
+// one entry of `schedule`: pass a, and the pass b that shares its slice loop (null: none)
+static void put_schedule(int32_t* schedule, int& entries, const BatchEntry& a, const BatchEntry* b)
+{
+    if (schedule) {
+        int32_t* const o = schedule + 4 * entries;
+        o[0] = a.light; o[1] = a.pass;
+        o[2] = b ? b->light : -1; o[3] = b ? b->pass : -1;
+    }
+    ++entries;
 }
 
 // Several AddDirLightToSingleLightVolume calls as one (the multi-light optimisation of the Sunden/Ropinski
@@ -209,13 +224,12 @@ int enqueue_add(tbrm_resources* r, const tbrm_dir_light_params& light, bool adde
 int enqueue_add_batch(tbrm_resources* r, const tbrm_dir_light_params* lights, int n_lights, bool added, const tbrm_world_params& world,
                       int32_t* schedule, int32_t* n_entries)
 {
-    struct Entry { int light, pass; tbrm_light_pass p; bool done; };
-    std::vector<Entry> all;
+    std::vector<BatchEntry> all;
     for (int i = 0; i < n_lights; ++i) {
         tbrm_light_pass passes[2];
         int n = 0;
         if (!host_light_passes(lights[i], world, r->lv_dims, r->desc.border_mode, passes, &n)) continue; // zero direction
-        for (int k = 0; k < n; ++k) all.push_back(Entry{i, k, passes[k], false});
+        for (int k = 0; k < n; ++k) all.push_back(BatchEntry{i, k, passes[k], false});
     }
     const PropParams base = base_prop_params(r, world);
     if (cache_usable(r))
@@ -227,12 +241,8 @@ int enqueue_add_batch(tbrm_resources* r, const tbrm_dir_light_params* lights, in
     // (DualOcc) — into the four scratch buffers / their cache entries, and passes of the two lights that leave the same cube face
     // and pull the same way are swept TOGETHER (enqueue_sweep_pair). A light's partner is the later light it shares most faces
     // with. Groups of two keep every factor store of a pair resident without more scratch than single operators use.
-    auto sweepable = [&](const tbrm_light_pass& q) {
-        SweepFit sf;
-        return sweep_fit(r, q, nullptr, PASS_ADD, sf) && ceil_div(q.td[2], 8) * 8 <= sweep_max_slices() && tune(TUNE_SPARSE_OCC) != 0 && tune(TUNE_OCC_LIST) != 0;
-    };
     bool all_sweep = pairing && !all.empty() && r->lv_fmt == FMT_U8; // (the two-light sweep is built for UNORM8 light volumes)
-    for (const Entry& e : all) all_sweep = all_sweep && sweepable(e.p);
+    for (const BatchEntry& e : all) all_sweep = all_sweep && add_pass_on_sweep(r, e.p);
     if (all_sweep) {
         auto pair_fits = [&](const tbrm_light_pass& x, const tbrm_light_pass& y) {
             SweepFit sf;
@@ -256,15 +266,8 @@ int enqueue_add_batch(tbrm_resources* r, const tbrm_dir_light_params* lights, in
                 std::vector<PassSpec> specs;
                 for (int li = l0; li < std::min(l0 + kGroup, n_lights); ++li)
                     for (size_t k : of_light[(size_t) li]) {
-                        PassSpec q;
-                        q.a = all[k].p;
-                        q.b_added = b;
-                        specs.push_back(q);
-                        if (schedule) {
-                            schedule[4 * entries + 0] = all[k].light; schedule[4 * entries + 1] = all[k].pass;
-                            schedule[4 * entries + 2] = -1; schedule[4 * entries + 3] = -1;
-                        }
-                        ++entries;
+                        specs.push_back(add_spec(all[k].p, b));
+                        put_schedule(schedule, entries, all[k], nullptr);
                     }
                 if (n_entries) *n_entries = entries;
                 if (specs.empty()) continue;
@@ -300,10 +303,7 @@ int enqueue_add_batch(tbrm_resources* r, const tbrm_dir_light_params* lights, in
             std::vector<PassSpec> specs;
             std::vector<int> partner(group.size(), -1);
             for (size_t g = 0; g < group.size(); ++g) {
-                PassSpec q;
-                q.a = all[group[g]].p;
-                q.b_added = b;
-                specs.push_back(q);
+                specs.push_back(add_spec(all[group[g]].p, b));
                 for (const auto& pr : best_pairs)
                     if (pr.first == group[g])
                         for (size_t h = 0; h < group.size(); ++h)
@@ -314,13 +314,7 @@ int enqueue_add_batch(tbrm_resources* r, const tbrm_dir_light_params* lights, in
                 if (j >= 0) second[(size_t) j] = 1;
             for (size_t g = 0; g < group.size(); ++g) { // the order the sweeps run in (run_passes)
                 if (second[g]) continue;
-                if (schedule) {
-                    const Entry& ea = all[group[g]];
-                    schedule[4 * entries + 0] = ea.light; schedule[4 * entries + 1] = ea.pass;
-                    schedule[4 * entries + 2] = partner[g] >= 0 ? all[group[(size_t) partner[g]]].light : -1;
-                    schedule[4 * entries + 3] = partner[g] >= 0 ? all[group[(size_t) partner[g]]].pass : -1;
-                }
-                ++entries;
+                put_schedule(schedule, entries, all[group[g]], partner[g] >= 0 ? &all[group[(size_t) partner[g]]] : nullptr);
             }
             if (n_entries) *n_entries = entries;
             if (int e = run_passes(r, base, specs, partner)) return e;
@@ -331,7 +325,7 @@ int enqueue_add_batch(tbrm_resources* r, const tbrm_dir_light_params* lights, in
     std::vector<PassSpec> specs;
     int entries = 0;
     for (size_t ia = 0; ia < all.size(); ++ia) {
-        Entry& a = all[ia];
+        BatchEntry& a = all[ia];
         if (a.done) continue;
         a.done = true;
         // Partner: a later pass of the same face whose previous-slice taps fall inside this pass's tap range or the other
@@ -341,18 +335,14 @@ int enqueue_add_batch(tbrm_resources* r, const tbrm_dir_light_params* lights, in
         // paired pass (lights 1 and 7: 3.61 -> 2.53 ms for both passes); with diverging directions the wider windows and
         // shorter chunks cost up to 0.2 ms more than they save.
         // A pass that the pipelined sweep takes is not paired: a sweep of its own costs less than its half of a paired chain.
-        auto kept = [&](const tbrm_light_pass& q) {
-            SweepFit sf;
-            return sweep_fit(r, q, nullptr, PASS_ADD, sf) && ceil_div(q.td[2], 8) * 8 <= sweep_max_slices() && tune(TUNE_SPARSE_OCC) != 0 && tune(TUNE_OCC_LIST) != 0;
-        };
-        Entry* partner = nullptr;
+        BatchEntry* partner = nullptr;
         ChunkFit fa;
-        if (pairing && !kept(a.p) && chunk_fit(r, a.p, nullptr, fa)) {
+        if (pairing && !add_pass_on_sweep(r, a.p) && chunk_fit(r, a.p, nullptr, fa)) {
             int best_area = INT32_MAX;
             for (size_t ib = ia + 1; ib < all.size(); ++ib) {
-                Entry& b2 = all[ib];
+                BatchEntry& b2 = all[ib];
                 ChunkFit fb, fp;
-                if (b2.done || b2.light == a.light || b2.p.face != a.p.face || kept(b2.p)) continue;
+                if (b2.done || b2.light == a.light || b2.p.face != a.p.face || add_pass_on_sweep(r, b2.p)) continue;
                 if (!chunk_fit(r, b2.p, nullptr, fb) || !chunk_fit(r, a.p, &b2.p, fp)) continue;
                 if (tune(TUNE_LIGHT_BATCHING) == 2) { partner = &b2; break; } // diagnostics: pair whatever fits
                 const int sx = fp.tx.hi - fp.tx.lo, sy = fp.ty.hi - fp.ty.lo;
@@ -361,14 +351,8 @@ int enqueue_add_batch(tbrm_resources* r, const tbrm_dir_light_params* lights, in
                 if (sx * sy < best_area) { best_area = sx * sy; partner = &b2; }
             }
         }
-        if (schedule) {
-            schedule[4 * entries + 0] = a.light; schedule[4 * entries + 1] = a.pass;
-            schedule[4 * entries + 2] = partner ? partner->light : -1; schedule[4 * entries + 3] = partner ? partner->pass : -1;
-        }
-        ++entries;
-        PassSpec q;
-        q.a = a.p;
-        q.b_added = b;
+        put_schedule(schedule, entries, a, partner);
+        PassSpec q = add_spec(a.p, b);
         if (partner) {
             partner->done = true;
             q.r = partner->p;

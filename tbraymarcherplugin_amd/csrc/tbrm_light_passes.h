@@ -1,6 +1,7 @@
 // tbrm_light_passes.h — what the four translation units of the host side of the illumination operators share beyond
 // tbrm_resources.h: tbrm_light_plan.cpp (which kernel a pass takes, its geometry), tbrm_factor_cache.cpp (occlusion stores, the
-// factor cache), tbrm_light_enqueue.cpp (launches and stream ordering), tbrm_light_operators.cpp (Add / Change / batches). Internal.
+// factor cache), tbrm_light_enqueue.cpp (launches and stream ordering, the slice-per-launch form's read / write buffers),
+// tbrm_light_operators.cpp (Add / Change / batches). Internal.
 #pragma once
 #include "tbrm_resources.h"
 #include "tbrm_light_chain.h"
@@ -48,4 +49,5 @@ int ensure_occ_stream(tbrm_resources* r);
 int enqueue_sweep_pair(tbrm_resources* r, const PassPlan& pa, const PassPlan& pb, const SweepFit& fit);
 int enqueue_sweep_chain(tbrm_resources* r, const PassPlan* plans, int n);
 int enqueue_pass_sliced(tbrm_resources* r, PropParams p, const tbrm_light_pass& pa, const tbrm_light_pass* pr);
+int fill_pass_buffers(tbrm_resources* r, const tbrm_light_pass& pa, const tbrm_light_pass* pr);
 } // namespace tbrm_host

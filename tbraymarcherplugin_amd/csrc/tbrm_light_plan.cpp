@@ -1,6 +1,8 @@
 // tbrm_light_plan.cpp — host side of the illumination operators, planning: what LightingShaders.cpp:35-326 does on the render
 // thread (per light the axis passes, per pass the slice loop) becomes a PassPlan — the pipelined sweep where it applies
 // (sweep_fit), else the chunked chain (chunk_fit), else one slice per launch — with its geometry and the factor cache's part in it.
+// The rules several planners share are stated once: the previous-slice tap scan (scan_prev_taps), why a pass is not swept
+// (sweep_fit_reason), a slab's bounds (slab_bounds_ok / fail_slab_bounds) and its run along z (slab_run_along_z).
 #include "tbrm_light_passes.h"
 
 namespace tbrm_host {
@@ -18,19 +20,40 @@ unsigned event_flags()
 bool force_slice_kernel() { return tune(TUNE_FORCE_SLICE_KERNEL) == 1; }
 int chunk_steps_override() { return tune(TUNE_CHUNK_STEPS); }
 
-TapRange prev_tap_range(int size, float off)
+// The texel coordinate of pixel c's previous-slice fetch along one buffer axis, with the kernel's own fp32 sequence (texel_split of
+// ((c + 0.5) / size + offset) over `texels` texels; the light planes: texels == size)
+static float tap_texel(int c, int size, float off, int texels)
 {
-    TapRange t;
+    const float u = (((float) (uint32_t) c + 0.5f) / (float) size) + off;
+    const float x = u * (float) texels - 0.5f;
+    return std::fmin(std::fmax(x, -0x1p30f), 0x1p30f);
+}
+
+// (tap index - pixel index) of the previous-slice bilinear fetch over every pixel of one buffer axis: hi includes the +1 tap,
+// hi_nz only where its weight is not zero. scanned false: no finite offset
+struct TapScan { int lo = INT32_MAX, hi = INT32_MIN, hi_nz = INT32_MIN; bool scanned = false; };
+static TapScan scan_prev_taps(int size, float off)
+{
+    TapScan t;
     if (!std::isfinite(off) || size <= 0) return t;
-    t.lo = INT32_MAX; t.hi = INT32_MIN;
     for (int c = 0; c < size; ++c) {
-        const float u = (((float) (uint32_t) c + 0.5f) / (float) size) + off;
-        float x = u * (float) size - 0.5f;
-        x = std::fmin(std::fmax(x, -0x1p30f), 0x1p30f);
-        const int d = (int) std::floor(x) - c;
+        const float x = tap_texel(c, size, off, size);
+        const float fl = std::floor(x);
+        const int d = (int) fl - c;
         t.lo = std::min(t.lo, d);
         t.hi = std::max(t.hi, d + 1);
+        t.hi_nz = std::max(t.hi_nz, x - fl != 0.0f ? d + 1 : d);
     }
+    t.scanned = true;
+    return t;
+}
+
+static TapRange prev_tap_range(int size, float off)
+{
+    TapRange t;
+    const TapScan s = scan_prev_taps(size, off);
+    if (!s.scanned) return t;
+    t.lo = s.lo; t.hi = s.hi;
     t.ok = std::abs(t.lo) <= 64 && std::abs(t.hi) <= 64;
     return t;
 }
@@ -38,26 +61,16 @@ TapRange prev_tap_range(int size, float off)
 
 // ---- the pipelined sweep (tbrm_light_sweep.hip) ---------------------------------------------------------------------------
 // Which side of a pixel the previous-slice taps of NON-ZERO weight lie on along one buffer axis, and how far, over every
-// pixel of the axis, with the kernel's own fp32 sequence. side 0: every pixel reads itself alone. ok false: taps on both
-// sides (an offset so small that rounding decides the side pixel by pixel) or out of range — the sweep declines.
+// pixel of the axis. side 0: every pixel reads itself alone. ok false: taps on both sides (an offset so small that rounding
+// decides the side pixel by pixel) or out of range — the sweep declines.
 struct TapSide { int side = 0, reach = 0; bool ok = false; };
 static TapSide prev_tap_side(int size, float off)
 {
     TapSide t;
-    if (!std::isfinite(off) || size <= 0) return t;
-    int lo = INT32_MAX, hi = INT32_MIN;
-    for (int c = 0; c < size; ++c) {
-        const float u = (((float) (uint32_t) c + 0.5f) / (float) size) + off;
-        float x = u * (float) size - 0.5f;
-        x = std::fmin(std::fmax(x, -0x1p30f), 0x1p30f);
-        const float fl = std::floor(x);
-        const float f = x - fl;
-        const int d = (int) fl - c;
-        lo = std::min(lo, d);
-        hi = std::max(hi, f != 0.0f ? d + 1 : d);
-    }
-    if (lo >= 0) { t.side = hi > 0 ? 1 : 0; t.reach = hi; t.ok = true; }
-    else if (hi <= 0) { t.side = -1; t.reach = -lo; t.ok = true; }
+    const TapScan s = scan_prev_taps(size, off);
+    if (!s.scanned) return t;
+    if (s.lo >= 0) { t.side = s.hi_nz > 0 ? 1 : 0; t.reach = s.hi_nz; t.ok = true; }
+    else if (s.hi_nz <= 0) { t.side = -1; t.reach = -s.lo; t.ok = true; }
     return t;
 }
 
@@ -66,14 +79,20 @@ static TapSide prev_tap_side(int size, float off)
 // of whole brick layers of the light volume. The two lights of a fused Change whose minor components have opposite signs
 // pull opposite ways: no tile order serves both, and the pass runs as TWO sweeps (SweepFit::two_way) if each light's reach
 // fits the hand-off wave and both fit the planes side by side.
-bool sweep_fit(const tbrm_resources* r, const tbrm_light_pass& pa, const tbrm_light_pass* pr, int mode, SweepFit& fit)
+//
+// Returns why not (tbrm_host_plan_light; diagnostics): 0 the pass fits, 1 previous-slice taps on both sides of the pixel along a plane
+// axis or an offset out of range, 2 taps more than 14 texels from the pixel, 3 more hand-off words per slice than a lane of the
+// hand-off wave carries, 4 a downward pass over a ragged depth of fewer than nine slices, 5 sweeps are off for the handle (tunable,
+// slab-resident, a failed sweep) or for this kind of pass
+static int sweep_fit_reason(const tbrm_resources* r, const tbrm_light_pass& pa, const tbrm_light_pass* pr, int mode, SweepFit& fit)
 {
-    if (tune(TUNE_LIGHT_SWEEP) == 0 || force_slice_kernel() || r->resident || r->sweep_failed_bits) return false;
-    const bool f32 = r->lv_fmt != FMT_U8; // (float light volumes: k_light_sweep<..., FMT_F32> — one-way passes of up to three words per lane)
-    if (mode != PASS_ADD && mode != PASS_CHANGE) return false;
+    if (tune(TUNE_LIGHT_SWEEP) == 0 || force_slice_kernel() || r->resident || r->sweep_failed_bits) return 5;
+    // (float light volumes: k_light_sweep<..., FMT_F32> — one-way passes of up to three words per lane)
+    const int max_halo_chunks = r->lv_fmt != FMT_U8 ? 3 : 6;
+    if (mode != PASS_ADD && mode != PASS_CHANGE) return 5;
     // (a depth that is no multiple of 8 is padded to whole brick layers: plan_pass_sweep; a downward pass then needs a second
     // layer behind the ragged one)
-    if (pa.td[2] % 8 != 0 && pa.dir < 0 && pa.td[2] < 9) return false;
+    if (pa.td[2] % 8 != 0 && pa.dir < 0 && pa.td[2] < 9) return 4;
     fit = SweepFit{};
     TapSide side[2][2];
     bool opposite = false;
@@ -81,7 +100,7 @@ bool sweep_fit(const tbrm_resources* r, const tbrm_light_pass& pa, const tbrm_li
     for (const tbrm_light_pass* q : {&pa, pr}) {
         if (!q) continue;
         const TapSide tx = prev_tap_side(q->td[0], q->prev_pixel_offset[0]), ty = prev_tap_side(q->td[1], q->prev_pixel_offset[1]);
-        if (!tx.ok || !ty.ok) return false;
+        if (!tx.ok || !ty.ok) return 1;
         side[n][0] = tx; side[n][1] = ty;
         ++n;
         opposite = opposite || tx.side * fit.sx < 0 || ty.side * fit.sy < 0;
@@ -90,34 +109,42 @@ bool sweep_fit(const tbrm_resources* r, const tbrm_light_pass& pa, const tbrm_li
         fit.hx = std::max(fit.hx, tx.reach);
         fit.hy = std::max(fit.hy, ty.reach);
     }
-    if (!opposite) return fit.hx <= 14 && fit.hy <= 14 && sweep_halo_chunks(fit.hx, fit.hy) <= (f32 ? 3 : 6);
-    if (tune(TUNE_LIGHT_SWEEP) == 2) return false; // (diagnostics: such passes take the chain, as before round 3's last week)
+    if (!opposite) {
+        if (fit.hx > 14 || fit.hy > 14) return 2;
+        return sweep_halo_chunks(fit.hx, fit.hy) > max_halo_chunks ? 3 : 0;
+    }
+    if (tune(TUNE_LIGHT_SWEEP) == 2) return 5; // (diagnostics: such passes take the chain, as before round 3's last week)
     fit.two_way = true;
     fit.sx = side[0][0].side; fit.hx = side[0][0].reach; fit.sy = side[0][1].side; fit.hy = side[0][1].reach;
     fit.r_sx = side[1][0].side; fit.r_hx = side[1][0].reach; fit.r_sy = side[1][1].side; fit.r_hy = side[1][1].reach;
     // the planes hold the tile, a guard ring and both lights' halos: the low sides' larger reach plus the high sides'
-    int room[2];
     for (int ax = 0; ax < 2; ++ax) {
         int lo = 0, hi = 0;
         for (int si = 0; si < 2; ++si) (side[si][ax].side < 0 ? lo : hi) = std::max(side[si][ax].side < 0 ? lo : hi, side[si][ax].reach);
-        room[ax] = lo + hi;
+        if (lo + hi > 14) return 2;
     }
-    return room[0] <= 14 && room[1] <= 14 && sweep_halo_chunks(fit.hx, fit.hy) <= (f32 ? 3 : 6) && sweep_halo_chunks(fit.r_hx, fit.r_hy) <= (f32 ? 3 : 6);
+    return sweep_halo_chunks(fit.hx, fit.hy) > max_halo_chunks || sweep_halo_chunks(fit.r_hx, fit.r_hy) > max_halo_chunks ? 3 : 0;
 }
 
-// Why sweep_fit declines a one-stream pass (tbrm_host_plan_light; diagnostics): 0 it does not, 1 previous-slice taps on both sides of
-// the pixel along a plane axis or an offset out of range, 2 taps more than 14 texels from the pixel, 3 more hand-off words per slice
-// than a lane of the hand-off wave carries, 4 a downward pass over a ragged depth of fewer than nine slices, 5 sweeps are off for
-// the handle (tunable, slab-resident, a failed sweep)
+bool sweep_fit(const tbrm_resources* r, const tbrm_light_pass& pa, const tbrm_light_pass* pr, int mode, SweepFit& fit)
+{
+    return sweep_fit_reason(r, pa, pr, mode, fit) == 0;
+}
+
+// Why sweep_fit declines a one-stream pass (sweep_fit_reason's codes)
 int sweep_decline_reason(const tbrm_resources* r, const tbrm_light_pass& pa)
 {
-    if (tune(TUNE_LIGHT_SWEEP) == 0 || force_slice_kernel() || r->resident || r->sweep_failed_bits) return 5;
-    if (pa.td[2] % 8 != 0 && pa.dir < 0 && pa.td[2] < 9) return 4;
-    const TapSide tx = prev_tap_side(pa.td[0], pa.prev_pixel_offset[0]), ty = prev_tap_side(pa.td[1], pa.prev_pixel_offset[1]);
-    if (!tx.ok || !ty.ok) return 1;
-    if (tx.reach > 14 || ty.reach > 14) return 2;
-    if (sweep_halo_chunks(tx.reach, ty.reach) > (r->lv_fmt != FMT_U8 ? 3 : 6)) return 3;
-    return 0;
+    SweepFit fit;
+    return sweep_fit_reason(r, pa, nullptr, PASS_ADD, fit);
+}
+
+// Would this single Add pass take the sweep? What sweep_fit asks of the pass, and what plan_pass_sweep asks of its padded depth
+// and of the tunables its occlusion depends on
+static bool sweep_takes(int padded_depth) { return padded_depth <= sweep_max_slices() && tune(TUNE_SPARSE_OCC) != 0 && tune(TUNE_OCC_LIST) != 0; }
+bool add_pass_on_sweep(const tbrm_resources* r, const tbrm_light_pass& q)
+{
+    SweepFit fit;
+    return sweep_fit(r, q, nullptr, PASS_ADD, fit) && sweep_takes(ceil_div(q.td[2], 8) * 8);
 }
 
 void release_sweep(tbrm_resources* r)
@@ -293,12 +320,6 @@ void fill_chunk_stream(ChunkStream& s, const tbrm_light_pass& p, int lv_fmt)
 thread_local const char* g_plan_note = "";
 int declined(const char* why) { g_plan_note = why; return TBRM_ERR_UNSUPPORTED; }
 
-// 72 x 48 LDS planes (tbrm_light_chain.h): the kernels that have them
-static int rect_planes_for(const tbrm_resources* r, int mode)
-{
-    return mode == PASS_ADD && r->lv_fmt == FMT_U8 && tune(TUNE_CHAIN_RECT_PLANES) != 0 ? 1 : 0;
-}
-
 // Chunk length of a pass (one stream: pr == null, else two) and the tap ranges its windows have to cover: the longest of
 // 16/8/4/2 slices whose window (tile + steps * growth) and staged occlusion fit in LDS. false: the chunk kernels decline.
 bool chunk_fit(const tbrm_resources* r, const tbrm_light_pass& pa, const tbrm_light_pass* pr, ChunkFit& fit, int mode)
@@ -321,7 +342,8 @@ bool chunk_fit(const tbrm_resources* r, const tbrm_light_pass& pa, const tbrm_li
     ty.lo = std::min(ty.lo, 0); ty.hi = std::max(ty.hi, 0);
     ChunkParams p{};
     p.dx_lo = tx.lo; p.dx_hi = tx.hi; p.dy_lo = ty.lo; p.dy_hi = ty.hi;
-    p.rect_planes = rect_planes_for(r, mode);
+    // 72 x 48 LDS planes (tbrm_light_chain.h): the kernels that have them
+    p.rect_planes = mode == PASS_ADD && r->lv_fmt == FMT_U8 && tune(TUNE_CHAIN_RECT_PLANES) != 0 ? 1 : 0;
     p.dir = pa.dir;
     p.j0 = pa.start;
     const int g = std::max(tx.hi - tx.lo, ty.hi - ty.lo);
@@ -340,11 +362,34 @@ bool chunk_fit(const tbrm_resources* r, const tbrm_light_pass& pa, const tbrm_li
     if (fit.M <= 0) return declined("the previous-slice taps reach too far for a 2-slice chunk"), false;
     fit.tx = tx;
     fit.ty = ty;
+    fit.rect_planes = p.rect_planes;
     return true;
 }
 
-// Returns TBRM_ERR_UNSUPPORTED (nothing enqueued) when the pass has to take the slice-per-launch path.
-// slab: the light-volume z range this handle owns (null: everything).
+// ---- slab-partitioned passes -----------------------------------------------------------------------------------------------
+int fail_slab_bounds(int nz, const tbrm_slab& slab)
+{
+    return fail(TBRM_ERR_INVALID_ARG, "slab [%d, %d) of a light volume %d deep: bounds and depth must be multiples of %d", slab.z_begin,
+                slab.z_end, nz, kChunkTile);
+}
+
+static int own_slab_only(const tbrm_resources* r, const tbrm_slab* slab)
+{
+    if (!r->resident || (slab && slab->z_begin == r->owned.z_begin && slab->z_end == r->owned.z_end)) return TBRM_OK;
+    return fail(TBRM_ERR_INVALID_ARG, "a slab-resident handle runs its own slab [%d, %d) only", r->owned.z_begin, r->owned.z_end);
+}
+
+// A pass along z over a slab: this handle advances its own slices [z_begin, z_end) from the planes the slab before handed on (or
+// the pass's initial value); the drivers order the slabs by first_chunk_of_pass, counted in chunks of `chunk` slices
+static void slab_run_along_z(PassPlan& plan, int dir, const tbrm_slab& slab, int nz, int chunk)
+{
+    const int before = dir > 0 ? slab.z_begin : nz - slab.z_end;
+    plan.D = slab.z_end - slab.z_begin;
+    plan.start = dir > 0 ? slab.z_begin : slab.z_end - 1;
+    plan.first_chunk_of_pass = before / chunk;
+    plan.pass_begins_here = before == 0; // (a chain chunk is shorter than kChunkTile, which divides the bounds: first_chunk_of_pass == 0 there)
+}
+
 // Rows of the slice plane (z, when the pass runs along x or y) a slice's previous-slice taps can lie from the pixel:
 // what a slab has to fetch from its neighbours after every slice of a slice-per-launch pass. < 0: offsets out of range.
 int slice_tap_reach(const tbrm_light_pass& pa, const tbrm_light_pass* pr)
@@ -365,9 +410,7 @@ int plan_pass_sliced(tbrm_resources* r, const PropParams& base, const tbrm_light
                      const tbrm_slab& slab, PassPlan& plan)
 {
     const int nz = r->lv_dims[2], D_pass = pa.td[2];
-    if (slab.z_begin < 0 || slab.z_end > nz || slab.z_begin >= slab.z_end || slab.z_begin % kChunkTile || slab.z_end % kChunkTile || nz % kChunkTile)
-        return fail(TBRM_ERR_INVALID_ARG, "slab [%d, %d) of a light volume %d deep: bounds and depth must be multiples of %d", slab.z_begin,
-                    slab.z_end, nz, kChunkTile);
+    if (!slab_bounds_ok(nz, slab)) return fail_slab_bounds(nz, slab);
     const int reach = slice_tap_reach(pa, pr);
     if (reach < 0) return declined("previous-slice offset out of range");
     plan = PassPlan{};
@@ -390,12 +433,8 @@ int plan_pass_sliced(tbrm_resources* r, const PropParams& base, const tbrm_light
     if (pr) fill_stream(p.r, *pr);
     p.row_block0 = 0;
     p.row_blocks = 0;
-    if (pa.axis == 2) {
-        plan.D = slab.z_end - slab.z_begin;
-        plan.start = pa.dir > 0 ? slab.z_begin : slab.z_end - 1;
-        plan.first_chunk_of_pass = pa.dir > 0 ? slab.z_begin : nz - slab.z_end;
-        plan.pass_begins_here = plan.first_chunk_of_pass == 0;
-    } else {
+    if (pa.axis == 2) slab_run_along_z(plan, pa.dir, slab, nz, 1);
+    else {
         if (reach > slab.z_end - slab.z_begin) return declined("a slice's taps reach beyond the neighbouring slab");
         plan.lateral = true;
         plan.halo_rows = reach;
@@ -403,34 +442,9 @@ int plan_pass_sliced(tbrm_resources* r, const PropParams& base, const tbrm_light
         p.row_blocks = (slab.z_end - slab.z_begin) / 16;
     }
     plan.n_chunks = plan.D;
-    if (r->resident) {
-        if (slab.z_begin != r->owned.z_begin || slab.z_end != r->owned.z_end)
-            return fail(TBRM_ERR_INVALID_ARG, "a slab-resident handle runs its own slab [%d, %d) only", r->owned.z_begin, r->owned.z_end);
-    }
-    if (plan.pass_begins_here) { // the buffers start from the light's initial value (LightingShaders.cpp:74-79)
-        const size_t npx = (size_t) pa.td[0] * pa.td[1];
-        const int ax = pa.axis;
-        if (!pr) {
-            HIP_TRY(launch_fill(r->d_buf[ax][0], r->lv_fmt, npx, pa.light_alpha, r->stream));
-            HIP_TRY(launch_fill(r->d_buf[ax][1], r->lv_fmt, npx, pa.light_alpha, r->stream));
-        } else {
-            HIP_TRY(launch_fill(r->d_buf[ax][0], r->lv_fmt, npx, pr->light_alpha, r->stream));
-            HIP_TRY(launch_fill(r->d_buf[ax][1], r->lv_fmt, npx, pr->light_alpha, r->stream));
-            HIP_TRY(launch_fill(r->d_buf[ax][2], r->lv_fmt, npx, pa.light_alpha, r->stream));
-            HIP_TRY(launch_fill(r->d_buf[ax][3], r->lv_fmt, npx, pa.light_alpha, r->stream));
-        }
-    }
+    if (int e = own_slab_only(r, &slab)) return e;
+    if (plan.pass_begins_here) return fill_pass_buffers(r, pa, pr);
     return TBRM_OK;
-}
-
-// the read buffer of stream si (0: a, 1: r) before this handle's slice number `boundary` (== n_chunks: what its last slice wrote)
-void* sliced_plane(const tbrm_resources* r, const PassPlan& plan, int boundary, int si)
-{
-    const int j = plan.start + boundary * plan.dir;
-    const int e = (j % 2 == 0) ? 0 : 1; // LightingShaders.cpp:149-156
-    const int ax = plan.p.axis;
-    if (plan.mode == PASS_ADD) return r->d_buf[ax][e];
-    return si == 0 ? r->d_buf[ax][2 + e] : r->d_buf[ax][e];
 }
 
 SpanRange span_range(const PassPlan& plan, int sp)
@@ -494,18 +508,15 @@ static int plan_pass_sweep(tbrm_resources* r, const PropParams& base, const tbrm
     SweepFit sfit;
     if (!sweep_fit(r, pa, pr, mode, sfit)) return TBRM_ERR_UNSUPPORTED;
     if (slab) {
-        const int nz = r->lv_dims[2];
         if (pa.axis != 2 || sfit.two_way) return TBRM_ERR_UNSUPPORTED; // (lateral slab passes need a hand-off per slice across handles: the chain)
-        if (slab->z_begin < 0 || slab->z_end > nz || slab->z_begin >= slab->z_end || slab->z_begin % kChunkTile || slab->z_end % kChunkTile || nz % kChunkTile)
-            return TBRM_ERR_UNSUPPORTED; // (the chain's planner words the error)
+        if (!slab_bounds_ok(r->lv_dims[2], *slab)) return TBRM_ERR_UNSUPPORTED; // (the chain's planner words the error)
     }
     // The pass over the light volume padded to whole brick layers along its axis (the bricked layout has the padding voxels):
     // D slices from `start`, of which the `pad` slices beyond the volume come last when the pass runs upwards — garbage in,
     // garbage out, into voxels nothing reads — and first when it runs downwards, where the last of them hands on the initial
     // plane (SweepParams::reinit_slice).
     const int D = slab ? slab->z_end - slab->z_begin : ceil_div(pa.td[2], 8) * 8, pad = slab ? 0 : D - pa.td[2];
-    const int start = slab ? (pa.dir > 0 ? slab->z_begin : slab->z_end - 1) : (pa.dir > 0 ? 0 : D - 1);
-    if (D > sweep_max_slices() || tune(TUNE_SPARSE_OCC) == 0 || tune(TUNE_OCC_LIST) == 0) return TBRM_ERR_UNSUPPORTED;
+    if (!sweep_takes(D)) return TBRM_ERR_UNSUPPORTED;
     if (int e = ensure_skipping(r)) return e; // (the work list needs the per-brick emptiness bits)
     if (int e = ensure_occ_stream(r)) return e;
     const bool change = pr != nullptr;
@@ -515,14 +526,12 @@ static int plan_pass_sweep(tbrm_resources* r, const PropParams& base, const tbrm
     fill_pass_params(r, base, pa, pr, b_added, 0.0f, plan);
     ChunkParams& p = plan.p;
     plan.D = D;
-    plan.start = start;
+    plan.start = pa.dir > 0 ? 0 : D - 1;
     plan.M = plan.S = D;
     plan.n_chunks = plan.n_spans = plan.chunks_of_pass = 1;
-    if (slab) { // (the drivers order the slabs by first_chunk_of_pass; chunk = this slab's depth)
-        const int nz = r->lv_dims[2], before = pa.dir > 0 ? slab->z_begin : nz - slab->z_end;
-        plan.chunks_of_pass = ceil_div(nz, D);
-        plan.first_chunk_of_pass = before / D;
-        plan.pass_begins_here = before == 0;
+    if (slab) { // (chunk = this slab's depth)
+        slab_run_along_z(plan, pa.dir, *slab, r->lv_dims[2], D);
+        plan.chunks_of_pass = ceil_div(r->lv_dims[2], D);
     }
     plan.sparse = plan.work_list = true;
     p.occ_groups = D / 8;
@@ -542,9 +551,9 @@ static int plan_pass_sweep(tbrm_resources* r, const PropParams& base, const tbrm
     FactorEntry *have_a = nullptr, *have_r = nullptr, *refill = nullptr;
     FactorKey key_a{};
     if (cache_on) {
-        key_a = factor_key(r, base, pa, mode == PASS_ADD, start, D);
+        key_a = factor_key(r, base, pa, mode == PASS_ADD, plan.start, D);
         have_a = kept_find(r, key_a);
-        if (change) have_r = kept_find(r, factor_key(r, base, *pr, false, start, D));
+        if (change) have_r = kept_find(r, factor_key(r, base, *pr, false, plan.start, D));
         // (the removed light alone is not computed: both are — and the added light's factors go into the entry that already
         // holds them, not into a second one with the same key)
         if (change && have_a && !have_r) { refill = have_a; have_a = nullptr; }
@@ -553,7 +562,7 @@ static int plan_pass_sweep(tbrm_resources* r, const PropParams& base, const tbrm
     // further use unless the light comes back: first in line when a buffer is needed (kept_new)
     auto retire = [&](const tbrm_light_pass& q) {
         for (int guard = 0; guard < 2; ++guard) {
-            const FactorKey k = factor_key(r, base, q, guard != 0, start, D);
+            const FactorKey k = factor_key(r, base, q, guard != 0, plan.start, D);
             for (FactorEntry* e : r->kept)
                 if (!memcmp(&e->key, &k, sizeof(k))) e->spent = true;
         }
@@ -611,7 +620,6 @@ static int plan_pass_sweep(tbrm_resources* r, const PropParams& base, const tbrm
     q.r_sx = sfit.r_sx; q.r_sy = sfit.r_sy; q.r_hx = sfit.r_hx; q.r_hy = sfit.r_hy;
     const size_t words = (size_t) D * p.tiles_x * p.tiles_y * (size_t) sweep_record_words(sfit.hx, sfit.hy) * (size_t) (r->lv_fmt != FMT_U8 && change && !sfit.two_way ? 2 : 1); // (float records: a granule per stream handed over)
     const size_t words1 = sfit.two_way ? (size_t) D * p.tiles_x * p.tiles_y * (size_t) sweep_record_words(sfit.r_hx, sfit.r_hy) : 0;
-    if (words >= ((size_t) 1 << 32) || words1 >= ((size_t) 1 << 32)) return declined("hand-off records too large");
     const size_t gw = r->lv_fmt != FMT_U8 ? 2 : 1; // 32-bit words per record word (float light volumes: {float, launch tag})
     if (words * gw >= ((size_t) 1 << 32) || words1 * gw >= ((size_t) 1 << 32)) return declined("hand-off records too large");
     if (int e = ensure_sweep(r, std::max<size_t>(words * gw, 1), words1 * gw)) return e;
@@ -630,6 +638,8 @@ static int plan_pass_sweep(tbrm_resources* r, const PropParams& base, const tbrm
     return TBRM_OK;
 }
 
+// Returns TBRM_ERR_UNSUPPORTED (nothing enqueued) when the pass has to take the slice-per-launch path.
+// slab: the light-volume z range this handle owns (null: everything).
 // pr == null: Add of pa (b_added = +-1). Else two streams: mode PASS_CHANGE (pa added, pr removed) or PASS_ADD2 (pa, then
 // pr, both added with b_added / b_added2).
 int plan_pass(tbrm_resources* r, const PropParams& base, const tbrm_light_pass& pa, const tbrm_light_pass* pr, float b_added,
@@ -656,22 +666,15 @@ int plan_pass(tbrm_resources* r, const PropParams& base, const tbrm_light_pass& 
     fill_pass_params(r, base, pa, pr, b_added, b_added2, plan);
     ChunkParams& p = plan.p;
     p.dx_lo = fit.tx.lo; p.dx_hi = fit.tx.hi; p.dy_lo = fit.ty.lo; p.dy_hi = fit.ty.hi;
-    p.rect_planes = rect_planes_for(r, mode);
+    p.rect_planes = fit.rect_planes;
     const int M = fit.M;
     plan.M = M;
     plan.chunks_of_pass = ceil_div(D_pass, M);
     if (slab) {
         const int nz = r->lv_dims[2];
-        if (slab->z_begin < 0 || slab->z_end > nz || slab->z_begin >= slab->z_end || slab->z_begin % kChunkTile || slab->z_end % kChunkTile ||
-            nz % kChunkTile)
-            return fail(TBRM_ERR_INVALID_ARG, "slab [%d, %d) of a light volume %d deep: bounds and depth must be multiples of %d",
-                        slab->z_begin, slab->z_end, nz, kChunkTile);
-        if (pa.axis == 2) { // the pass runs along the slab axis: this handle advances its own slices, planes are handed on
-            plan.D = slab->z_end - slab->z_begin;
-            plan.start = pa.dir > 0 ? slab->z_begin : slab->z_end - 1;
-            plan.first_chunk_of_pass = (pa.dir > 0 ? slab->z_begin : nz - slab->z_end) / M;
-            plan.pass_begins_here = plan.first_chunk_of_pass == 0;
-        } else { // z is the plane's row axis: the slab's tile rows, and the occlusion of every row their windows can reach
+        if (!slab_bounds_ok(nz, *slab)) return fail_slab_bounds(nz, *slab);
+        if (pa.axis == 2) slab_run_along_z(plan, pa.dir, *slab, nz, M); // the pass runs along the slab axis: planes are handed on
+        else { // z is the plane's row axis: the slab's tile rows, and the occlusion of every row their windows can reach
             plan.lateral = true;
             p.tile_row0 = slab->z_begin / kChunkTile;
             p.tiles_y = (slab->z_end - slab->z_begin) / kChunkTile;
@@ -679,9 +682,8 @@ int plan_pass(tbrm_resources* r, const PropParams& base, const tbrm_light_pass& 
             p.roi_by1 = std::min(ceil_div(slab->z_end + kChunkTile, 16), p.occ_blocks_y);
         }
     }
+    if (int e = own_slab_only(r, slab)) return e;
     if (r->resident) {
-        if (!slab || slab->z_begin != r->owned.z_begin || slab->z_end != r->owned.z_end)
-            return fail(TBRM_ERR_INVALID_ARG, "a slab-resident handle runs its own slab [%d, %d) only", r->owned.z_begin, r->owned.z_end);
         // every data texel the occlusion of this handle's rows / slices can sample has to be resident: z range of the taps of
         // light-volume slices [za, zb), with the kernel's own arithmetic (GetUVW + UVWOffset, texel split)
         const int za = plan.lateral ? std::max(slab->z_begin - kChunkTile, 0) : slab->z_begin;
@@ -690,10 +692,7 @@ int plan_pass(tbrm_resources* r, const PropParams& base, const tbrm_light_pass& 
         for (const tbrm_light_pass* q : {&pa, pr}) {
             if (!q) continue;
             for (int z : {za, zb - 1}) {
-                const float w = (((float) (uint32_t) z + 0.5f) / (float) (uint32_t) r->lv_dims[2]) + q->uvw_offset[2];
-                float x = w * (float) r->desc.dim_z - 0.5f;
-                x = std::fmin(std::fmax(x, -0x1p30f), 0x1p30f);
-                const int i0 = (int) std::floor(x);
+                const int i0 = (int) std::floor(tap_texel(z, r->lv_dims[2], q->uvw_offset[2], r->desc.dim_z));
                 lo = std::min(lo, i0);
                 hi = std::max(hi, i0 + 1);
             }

@@ -345,7 +345,7 @@ RelayoutParams relayout_params(const void* src, void* dst, const int dims[3], co
 // kernel's own fp32 sequence (texel_split of ((c+0.5)/size + offset)); hi includes the +1 tap.
 struct TapRange { int lo = 0, hi = 0; bool ok = false; };
 
-struct ChunkFit { int M = 0; TapRange tx, ty; };
+struct ChunkFit { int M = 0; TapRange tx, ty; int rect_planes = 0; }; // (rect_planes: ChunkParams::rect_planes of the pass)
 
 // One axis pass (Add: stream a only; Change: a = added, r = removed) as a plan: everything that is constant over the
 // pass, worked out once, and the chunks then enqueued one by one (plan_pass / enqueue_plan_chunk). A single-GPU pass
@@ -388,6 +388,12 @@ struct PassPlan {
 extern thread_local const char* g_plan_note; // why chunk_fit / plan_pass last declined a pass
 bool chunk_fit(const tbrm_resources* r, const tbrm_light_pass& pa, const tbrm_light_pass* pr, ChunkFit& fit, int mode = -1);
 int slice_tap_reach(const tbrm_light_pass& pa, const tbrm_light_pass* pr);
+// a slab of a light volume nz deep: inside it, not empty, bounds and depth whole tiles (fail_slab_bounds words the error)
+inline bool slab_bounds_ok(int nz, const tbrm_slab& s)
+{
+    return !(s.z_begin < 0 || s.z_end > nz || s.z_begin >= s.z_end || s.z_begin % kChunkTile || s.z_end % kChunkTile || nz % kChunkTile);
+}
+int fail_slab_bounds(int nz, const tbrm_slab& slab);
 int plan_pass(tbrm_resources* r, const PropParams& base, const tbrm_light_pass& pa, const tbrm_light_pass* pr, float b_added,
               const tbrm_slab* slab, PassPlan& plan, int two_stream_mode = PASS_CHANGE, float b_added2 = 0.0f);
 // two_way (fused Change only): the removed light's taps lie on the other side along some axis — its planes are swept first,
@@ -395,6 +401,7 @@ int plan_pass(tbrm_resources* r, const PropParams& base, const tbrm_light_pass& 
 struct SweepFit { int sx = 0, sy = 0, hx = 0, hy = 0; bool two_way = false; int r_sx = 0, r_sy = 0, r_hx = 0, r_hy = 0; };
 bool sweep_fit(const tbrm_resources* r, const tbrm_light_pass& pa, const tbrm_light_pass* pr, int mode, SweepFit& fit);
 int sweep_decline_reason(const tbrm_resources* r, const tbrm_light_pass& pa);
+bool add_pass_on_sweep(const tbrm_resources* r, const tbrm_light_pass& q); // would this single Add pass take the sweep?
 void release_sweep(tbrm_resources* r);
 int sweep_check(tbrm_resources* r);  // after the stream has drained: did a sweep kernel raise its error word? (+ the stamps' print-out)
 int sweep_failed(tbrm_resources* r); // latches the error word; TBRM_OK or the (sticky) error

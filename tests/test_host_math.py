@@ -169,3 +169,18 @@ def test_planner_alone_says_which_kernel_a_pass_takes():
     assert plan[0][0] == 0, plan                      # the major axis sweeps (its taps lie within a texel or two)
     assert plan[1][0] in (1, 2) and plan[1][3] in (2, 3), plan  # the second axis: reach beyond 14 texels / too many hand-off words
     assert abi.host_plan_light(abi.DirLightParams((0.0, 0.0, 0.0), 1.0), world, (64, 64, 64)) == []  # zero direction: no pass
+    # the fit and the reason come from one function: a pass is on the sweep exactly when its reason is 0, and each of the reasons
+    # 1 - 4 is reached: (dims, direction, pass) -> reason
+    reached = {((256, 256, 90), (1, 0, 0), 0): 1,        # taps on both sides of the pixel
+               ((512, 512, 64), (1e-9, 1, 0.5), 1): 2,   # reach beyond 14 texels
+               ((512, 512, 64), (1.0, 0.9, 0.95), 1): 3,  # more hand-off words than a lane carries
+               ((40, 32, 6), (0, 0, -1), 0): 4}          # a downward pass over a ragged depth of fewer than nine slices
+    seen = set()
+    for dims in ((64, 64, 64), (512, 512, 64), (40, 32, 6), (256, 256, 90)):
+        for d in ((1, 0, 0), (0, 0, -1), (1, 1, 0), (1e-9, 1, 0.5), (1.0, 0.9, 0.95), (0.3, 0.2, -1), (-1, 0.6, 0.4)):
+            for k, p in enumerate(abi.host_plan_light(abi.DirLightParams(d, 1.0), world, dims)):
+                assert (p[0] == 0) == (p[3] == 0), (dims, d, k, p)
+                if (dims, d, k) in reached:
+                    assert p[3] == reached[(dims, d, k)], (dims, d, k, p)
+                    seen.add(p[3])
+    assert seen == {1, 2, 3, 4}, seen
