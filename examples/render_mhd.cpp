@@ -5,11 +5,13 @@
 //
 //   g++ -std=c++17 -O2 -I include examples/render_mhd.cpp -o render_mhd -L tbraymarcherplugin_amd/lib -ltbrm -lz
 //       (plus -Wl,-rpath,$PWD/tbraymarcherplugin_amd/lib -Wl,-rpath,/opt/rocm/lib to run it in place)
-//   ./render_mhd volume.mhd out.ppm [width height steps]
+//   ./render_mhd volume.mhd out.ppm [width height steps] [--light-color r,g,b]
+//       --light-color: the key light's colour (components in [0, 1]) on an RGB light volume (include/tbrm_color_lights.h); the fill stays white
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "tbrm_volume_io.hpp" // includes tbrm_plugin.hpp
@@ -18,14 +20,25 @@ using namespace tbrm_plugin;
 
 int main(int argc, char** argv)
 {
+    float key_color[3] = {1.0f, 1.0f, 1.0f};
+    bool colored = false;
+    for (int i = 1; i + 1 < argc; ++i) // the option and its value leave the positional arguments
+        if (!std::strcmp(argv[i], "--light-color")) {
+            if (std::sscanf(argv[i + 1], "%f,%f,%f", &key_color[0], &key_color[1], &key_color[2]) != 3) { argc = 0; break; }
+            colored = true;
+            for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
+            argc -= 2;
+            break;
+        }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s volume.mhd out.ppm [width height steps]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s volume.mhd out.ppm [width height steps] [--light-color r,g,b]\n", argv[0]);
         return 2;
     }
     const int width = argc > 3 ? std::atoi(argv[3]) : 512, height = argc > 4 ? std::atoi(argv[4]) : 512;
     const float steps = argc > 5 ? (float) std::atof(argv[5]) : 256.0f;
 
     ARaymarchVolume volume;
+    volume.bColoredLights = colored; // (read when the resources are initialised: before the volume is loaded)
     FVolumeInfo info;
     if (!LoadMHDFileIntoVolumeNormalized(volume, argv[1], &info)) { // RaymarchVolume.cpp:596-612
         std::fprintf(stderr, "could not load %s: %s\n", argv[1], tbrm_last_error());
@@ -41,6 +54,7 @@ int main(int argc, char** argv)
     ARaymarchLight key, fill;
     key.ForwardVector = FVector{1, 0.35, -0.5};
     key.LightIntensity = 0.7f;
+    for (int c = 0; c < 3; ++c) key.LightColor[c] = key_color[c];
     fill.ForwardVector = FVector{-0.4, 1, -0.3};
     fill.LightIntensity = 0.3f;
     volume.LightsArray = {&key, &fill};

@@ -16,6 +16,7 @@
 
 #include "tbrm.h"
 #include "tbrm_labels.h"
+#include "tbrm_color_lights.h"
 
 #include <algorithm>
 #include <cmath>
@@ -44,11 +45,19 @@ inline bool TransformEquals(const FTransform& a, const FTransform& b)
 struct FDirLightParameters { // RaymarchTypes.h:20-41
     FVector LightDirection{0, 0, 0};
     float LightIntensity = 0;
+    // Not in the reference (Readme.md:165: "not a RGB light volume to accomodate for colored lights"): the light's colour, white
+    // unless set; only a volume with bColoredLights looks at it (include/tbrm_color_lights.h)
+    float LightColor[3] = {1.0f, 1.0f, 1.0f};
     FDirLightParameters() = default;
     FDirLightParameters(FVector LightDir, float LightInt) : LightDirection(LightDir), LightIntensity(LightInt) {}
-    bool operator==(const FDirLightParameters& rhs) const { return LightDirection == rhs.LightDirection && LightIntensity == rhs.LightIntensity; }
+    bool operator==(const FDirLightParameters& rhs) const
+    {
+        return LightDirection == rhs.LightDirection && LightIntensity == rhs.LightIntensity && LightColor[0] == rhs.LightColor[0] &&
+               LightColor[1] == rhs.LightColor[1] && LightColor[2] == rhs.LightColor[2];
+    }
     bool operator!=(const FDirLightParameters& rhs) const { return !(*this == rhs); }
     tbrm_dir_light_params abi() const { return tbrm_dir_light_params{LightDirection, LightIntensity, 0}; }
+    tbrm_color_dir_light color_abi() const { return tbrm_color_dir_light{abi(), {LightColor[0], LightColor[1], LightColor[2]}, 0}; }
 };
 
 struct FClippingPlaneParameters { // RaymarchTypes.h:45-71
@@ -139,6 +148,26 @@ struct URaymarchUtils { // RaymarchUtils.h:33-93; all static, like the Blueprint
         tbrm_change_dir_light(Resources.Handle, &o, &n, &w, &flag, bGPUSync ? 1 : 0);
         LightAdded = flag != 0;
     }
+    // Not in the reference: the two operators with the lights' colours, on a volume with bColoredLights (tbrm_color_lights.h)
+    static void AddColorDirLightToSingleVolume(const FBasicRaymarchRenderingResources& Resources, const FDirLightParameters& LightParameters,
+                                               const bool Added, const FRaymarchWorldParameters WorldParameters, bool& LightAdded)
+    {
+        const tbrm_color_dir_light l = LightParameters.color_abi();
+        const tbrm_world_params w = WorldParameters.abi();
+        int flag = 0;
+        tbrm_add_color_dir_light(Resources.Handle, &l, Added ? 1 : 0, &w, &flag);
+        LightAdded = flag != 0;
+    }
+    static void ChangeColorDirLightInSingleVolume(FBasicRaymarchRenderingResources& Resources, const FDirLightParameters OldLightParameters,
+                                                  const FDirLightParameters NewLightParameters, const FRaymarchWorldParameters WorldParameters,
+                                                  bool& LightAdded)
+    {
+        const tbrm_color_dir_light o = OldLightParameters.color_abi(), n = NewLightParameters.color_abi();
+        const tbrm_world_params w = WorldParameters.abi();
+        int flag = 0;
+        tbrm_change_color_dir_light(Resources.Handle, &o, &n, &w, &flag);
+        LightAdded = flag != 0;
+    }
     // RaymarchUtils.cpp:94-102
     static bool GenerateOctree(FBasicRaymarchRenderingResources& Resources)
     {
@@ -205,8 +234,15 @@ struct URaymarchUtils { // RaymarchUtils.h:33-93; all static, like the Blueprint
 struct ARaymarchLight { // direction = actor forward vector (RaymarchLight.cpp:28-31)
     FVector ForwardVector{1, 0, 0};
     float LightIntensity = 1.0f;
+    float LightColor[3] = {1.0f, 1.0f, 1.0f}; // (not in the reference) every component in [0, 1]; a change is a Change, like an intensity's
     std::string Name = "RaymarchLight";
-    FDirLightParameters GetCurrentParameters() const { return FDirLightParameters(ForwardVector, LightIntensity); }
+    FDirLightParameters GetCurrentParameters() const
+    {
+        FDirLightParameters p(ForwardVector, LightIntensity);
+        for (int c = 0; c < 3; ++c) p.LightColor[c] = LightColor[c];
+        return p;
+    }
+    tbrm_color_dir_light GetCurrentColorParameters() const { return GetCurrentParameters().color_abi(); }
 };
 
 struct ARaymarchClipPlane { // (location, -up) (RaymarchClipPlane.cpp:32-35)
@@ -233,6 +269,9 @@ public:
     int DataAddressMode = TBRM_ADDRESS_WRAP;
     bool bRecordLightsOnReset = false; // see ResetAllLights
     bool bBatchLightsOnReset = false;  // ResetAllLights adds all lights with one batched call (UNORM8 result may differ by one code at fp32 ties)
+    // (not in the reference) an RGB light volume lit by the lights' LightColor; read when the resources are initialised
+    // (SetVolumeAsset). false: a mono handle, and LightColor is ignored. The batched reset has no colour form: light by light.
+    bool bColoredLights = false;
 
     struct FStats { int Resets = 0, LightAdds = 0, LightChanges = 0, Frames = 0; } Stats; // what Tick decided (test hook)
 
@@ -348,7 +387,7 @@ public:
         URaymarchUtils::ClearResourceLightVolumes(RaymarchResources, 0);
         ++Stats.Resets;
         bool bResetWasSuccessful = true;
-        if (bBatchLightsOnReset) {
+        if (bBatchLightsOnReset && !ColoredHandle()) {
             std::vector<FDirLightParameters> All;
             for (ARaymarchLight* Light : LightsArray)
                 if (Light) All.push_back(Light->GetCurrentParameters());
@@ -363,7 +402,8 @@ public:
         }
         for (ARaymarchLight* Light : LightsArray) {
             if (!Light) continue;
-            URaymarchUtils::AddDirLightToSingleVolume(RaymarchResources, Light->GetCurrentParameters(), true, WorldParameters, bResetWasSuccessful, bFastShader);
+            if (ColoredHandle()) URaymarchUtils::AddColorDirLightToSingleVolume(RaymarchResources, Light->GetCurrentParameters(), true, WorldParameters, bResetWasSuccessful);
+            else URaymarchUtils::AddDirLightToSingleVolume(RaymarchResources, Light->GetCurrentParameters(), true, WorldParameters, bResetWasSuccessful, bFastShader);
             ++Stats.LightAdds;
             if (!bResetWasSuccessful) { std::fprintf(stderr, "Error. Could not add/remove light %s.\n", Light->Name.c_str()); return; }
             // The reference leaves LightParametersMap untouched here (:418-451): a light that moved before a reset is
@@ -377,7 +417,8 @@ public:
     void UpdateSingleLight(ARaymarchLight* UpdatedLight) // :453-465
     {
         bool bLightAddWasSuccessful = false;
-        URaymarchUtils::ChangeDirLightInSingleVolume(RaymarchResources, LightParametersMap[UpdatedLight], UpdatedLight->GetCurrentParameters(), WorldParameters, bLightAddWasSuccessful);
+        if (ColoredHandle()) URaymarchUtils::ChangeColorDirLightInSingleVolume(RaymarchResources, LightParametersMap[UpdatedLight], UpdatedLight->GetCurrentParameters(), WorldParameters, bLightAddWasSuccessful);
+        else URaymarchUtils::ChangeDirLightInSingleVolume(RaymarchResources, LightParametersMap[UpdatedLight], UpdatedLight->GetCurrentParameters(), WorldParameters, bLightAddWasSuccessful);
         ++Stats.LightChanges;
         if (!bLightAddWasSuccessful) std::fprintf(stderr, "Error. Could not change light %s.\n", UpdatedLight->Name.c_str());
     }
@@ -444,6 +485,7 @@ public:
 private:
     std::map<ARaymarchLight*, FDirLightParameters> LightParametersMap;
     bool bHasTF = false;
+    bool ColoredHandle() const { return RaymarchResources.Handle && tbrm_resources_light_channels(RaymarchResources.Handle) == 3; }
 
     void InitializeRaymarchResources(int X, int Y, int Z, int Format) // :821-920
     {
@@ -456,7 +498,7 @@ private:
         d.device = Device;
         d.data_address_mode = DataAddressMode;
         d.border_mode = TBRM_BORDER_ENGINE_8BIT;
-        if (tbrm_resources_create(&d, &RaymarchResources.Handle) != TBRM_OK) {
+        if ((bColoredLights ? tbrm_resources_create_rgb(&d, &RaymarchResources.Handle) : tbrm_resources_create(&d, &RaymarchResources.Handle)) != TBRM_OK) {
             std::fprintf(stderr, "Tried to initialize Raymarch resources: %s\n", tbrm_last_error());
             RaymarchResources.Handle = nullptr;
             return;

@@ -46,6 +46,13 @@ class DirLightParams(C.Structure):  # FDirLightParameters
         super().__init__(Vec3d(*direction), float(intensity), 0)
 
 
+class ColorDirLight(C.Structure):  # tbrm_color_dir_light (include/tbrm_color_lights.h)
+    _fields_ = [("light", DirLightParams), ("color", C.c_float * 3), ("_pad", C.c_int32)]
+
+    def __init__(self, direction=(0.0, 0.0, 0.0), intensity=0.0, color=(1.0, 1.0, 1.0)):
+        super().__init__(DirLightParams(direction, intensity), (C.c_float * 3)(*[float(c) for c in color]), 0)
+
+
 class ClippingPlaneParams(C.Structure):  # FClippingPlaneParameters
     _fields_ = [("center", Vec3d), ("direction", Vec3d)]
 
@@ -138,6 +145,14 @@ LABEL_SYMBOLS = [
 ]
 
 LABELS_ABI_VERSION = 1  # TBRM_LABELS_ABI_VERSION of include/tbrm_labels.h
+
+# every symbol include/tbrm_color_lights.h declares (coloured lights; tests/test_color_lights_abi.py checks the header against this list)
+COLOR_LIGHT_SYMBOLS = [
+    "tbrm_color_lights_abi_version", "tbrm_resources_create_rgb", "tbrm_resources_light_channels", "tbrm_add_color_dir_light",
+    "tbrm_change_color_dir_light", "tbrm_download_light_channel", "tbrm_upload_light_channel",
+]
+
+COLOR_LIGHTS_ABI_VERSION = 1  # TBRM_COLOR_LIGHTS_ABI_VERSION of include/tbrm_color_lights.h
 
 _lib = None
 
@@ -237,6 +252,16 @@ def load():
     lib.tbrm_set_label_colors.argtypes = [vp, vp]
     lib.tbrm_release_label_volume.argtypes = [vp]
     lib.tbrm_has_label_volume.argtypes = [vp]
+    have = lib.tbrm_color_lights_abi_version() if hasattr(lib, "tbrm_color_lights_abi_version") else -1
+    if have != COLOR_LIGHTS_ABI_VERSION:
+        raise ImportError(f"{LIB_PATH} has colour-light ABI version {have}, this binding is written against {COLOR_LIGHTS_ABI_VERSION}: "
+                          "rebuild it (`python tbraymarcherplugin_amd/build.py --force`)")
+    lib.tbrm_resources_create_rgb.argtypes = [P(ResourcesDesc), P(vp)]
+    lib.tbrm_resources_light_channels.argtypes = [vp]
+    lib.tbrm_add_color_dir_light.argtypes = [vp, P(ColorDirLight), C.c_int, P(WorldParams), P(C.c_int)]
+    lib.tbrm_change_color_dir_light.argtypes = [vp, P(ColorDirLight), P(ColorDirLight), P(WorldParams), P(C.c_int)]
+    lib.tbrm_download_light_channel.argtypes = [vp, C.c_int, vp, C.c_size_t]
+    lib.tbrm_upload_light_channel.argtypes = [vp, C.c_int, vp, C.c_size_t]
     _lib = lib
     return lib
 
@@ -368,14 +393,19 @@ class Resources:
     """Owns one tbrm_resources handle (FBasicRaymarchRenderingResources)."""
 
     def __init__(self, dims, data_format, light_32bit=False, half_res=False, device=0,
-                 data_address_mode=ADDRESS_WRAP, border_mode=BORDER_ENGINE_8BIT, owned=None):
-        """owned: a Slab -> a slab-resident handle (tbrm_resources_create_slab) that holds only its part of the volumes"""
+                 data_address_mode=ADDRESS_WRAP, border_mode=BORDER_ENGINE_8BIT, owned=None, rgb=False):
+        """owned: a Slab -> a slab-resident handle (tbrm_resources_create_slab) that holds only its part of the volumes;
+        rgb: a colour handle (tbrm_resources_create_rgb, include/tbrm_color_lights.h): a light volume of three channels"""
         self.lib = load()
         self.desc = ResourcesDesc(int(dims[0]), int(dims[1]), int(dims[2]), int(data_format), int(bool(light_32bit)),
                                   int(bool(half_res)), int(device), int(data_address_mode), int(border_mode), 0)
         self.handle = C.c_void_p()
         self.owned = owned
-        if owned is None:
+        if rgb:
+            if owned is not None:
+                raise TbrmError(ERR_UNSUPPORTED, "there is no colour form of a slab-resident handle")
+            check(self.lib.tbrm_resources_create_rgb(C.byref(self.desc), C.byref(self.handle)))
+        elif owned is None:
             check(self.lib.tbrm_resources_create(C.byref(self.desc), C.byref(self.handle)))
         else:
             check(self.lib.tbrm_resources_create_slab(C.byref(self.desc), C.byref(owned), C.byref(self.handle)))
@@ -472,6 +502,30 @@ class Resources:
         flag = C.c_int(0)
         check(self.lib.tbrm_change_dir_light(self.handle, C.byref(old), C.byref(new), C.byref(world), C.byref(flag), int(gpu_sync)))
         return bool(flag.value)
+
+    # coloured lights (include/tbrm_color_lights.h)
+    def light_channels(self):
+        return int(self.lib.tbrm_resources_light_channels(self.handle))
+
+    def add_color_dir_light(self, light, added, world):
+        flag = C.c_int(0)
+        check(self.lib.tbrm_add_color_dir_light(self.handle, C.byref(light), int(bool(added)), C.byref(world), C.byref(flag)))
+        return bool(flag.value)
+
+    def change_color_dir_light(self, old, new, world):
+        flag = C.c_int(0)
+        check(self.lib.tbrm_change_color_dir_light(self.handle, C.byref(old), C.byref(new), C.byref(world), C.byref(flag)))
+        return bool(flag.value)
+
+    def download_light_channel(self, channel):
+        out = np.empty(self.light_dims[::-1], dtype=self.light_dtype)
+        check(self.lib.tbrm_download_light_channel(self.handle, int(channel), out.ctypes.data, out.nbytes))
+        return out
+
+    def upload_light_channel(self, channel, lv):
+        lv = np.ascontiguousarray(lv, dtype=self.light_dtype)
+        assert lv.shape == self.light_dims[::-1]
+        check(self.lib.tbrm_upload_light_channel(self.handle, int(channel), lv.ctypes.data, lv.nbytes))
 
     def clear_light_volume(self, value=0.0):
         check(self.lib.tbrm_clear_light_volume(self.handle, float(value)))

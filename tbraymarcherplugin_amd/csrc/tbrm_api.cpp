@@ -257,6 +257,59 @@ int ensure_skipping(tbrm_resources* r)
 
 } // namespace tbrm_host
 
+namespace tbrm_host {
+
+int refuse_color(const tbrm_resources* r, const char* what)
+{
+    if (!r || r->light_channels == 1) return TBRM_OK;
+    return fail(TBRM_ERR_UNSUPPORTED, "colour handle (tbrm_resources_create_rgb): no %s", what);
+}
+
+// the mono entry points on a colour handle (include/tbrm_color_lights.h)
+static tbrm_color_dir_light white(const tbrm_dir_light_params& l) { return tbrm_color_dir_light{l, {1.0f, 1.0f, 1.0f}, 0}; }
+
+static int light_channel_args(const tbrm_resources* r, int channel, const void* host, size_t n_bytes)
+{
+    if (!r || !host) return fail(TBRM_ERR_INVALID_ARG, "null argument");
+    if (r->resident) return fail(TBRM_ERR_UNSUPPORTED, "slab-resident handle: its light volume moves slice by slice");
+    if (channel < 0 || channel >= r->light_channels) return fail(TBRM_ERR_INVALID_ARG, "channel %d of a light volume of %d", channel, r->light_channels);
+    if (n_bytes != r->light_bytes) return fail(TBRM_ERR_INVALID_ARG, "light volume is %zu bytes, got %zu", r->light_bytes, n_bytes);
+    return TBRM_OK;
+}
+
+int download_light_channel(tbrm_resources* r, int channel, void* host_out, size_t n_bytes)
+{
+    if (int e = light_channel_args(r, channel, host_out, n_bytes)) return e;
+    if (int e = bind(r)) return e;
+    void* staging = nullptr;
+    HIP_TRY(hipMalloc(&staging, n_bytes));
+    const int dims[3] = {r->lv_dims[0], r->lv_dims[1], r->lv_dims[2]};
+    hipError_t e1 = launch_relayout(relayout_params(r->light_channel(channel), staging, dims, r->lbn, r->lv_fmt == FMT_U8 ? 1 : 4, false), r->stream);
+    if (e1 == hipSuccess) e1 = hipMemcpyAsync(host_out, staging, n_bytes, hipMemcpyDeviceToHost, r->stream);
+    if (e1 == hipSuccess) e1 = hipStreamSynchronize(r->stream);
+    (void) hipFree(staging);
+    HIP_TRY(e1);
+    return sweep_failed(r); // (the slices of a light volume a failed sweep left undefined are not handed out as good)
+}
+
+int upload_light_channel(tbrm_resources* r, int channel, const void* host_in, size_t n_bytes)
+{
+    if (int e = light_channel_args(r, channel, host_in, n_bytes)) return e;
+    if (int e = bind(r)) return e;
+    void* staging = nullptr;
+    HIP_TRY(hipMalloc(&staging, n_bytes));
+    const int dims[3] = {r->lv_dims[0], r->lv_dims[1], r->lv_dims[2]};
+    hipError_t e1 = hipMemcpyAsync(staging, host_in, n_bytes, hipMemcpyHostToDevice, r->stream);
+    if (e1 == hipSuccess) e1 = launch_relayout(relayout_params(staging, r->light_channel(channel), dims, r->lbn, r->lv_fmt == FMT_U8 ? 1 : 4, true), r->stream);
+    if (e1 == hipSuccess) e1 = hipStreamSynchronize(r->stream);
+    (void) hipFree(staging);
+    HIP_TRY(e1);
+    sweep_failure_cleared(r); // (the light volume is defined again)
+    return TBRM_OK;
+}
+
+} // namespace tbrm_host
+
 // ---------------------------------------------------------------------------------------------------------------
 
 extern "C" {
@@ -276,15 +329,16 @@ int tbrm_device_count(int* out_count)
     return TBRM_OK;
 }
 
-static int create_impl(const tbrm_resources_desc* desc, const tbrm_slab* owned, tbrm_resources** out);
-int tbrm_resources_create(const tbrm_resources_desc* desc, tbrm_resources** out) { return create_impl(desc, nullptr, out); }
+static int create_impl(const tbrm_resources_desc* desc, const tbrm_slab* owned, int light_channels, tbrm_resources** out);
+int tbrm_resources_create(const tbrm_resources_desc* desc, tbrm_resources** out) { return create_impl(desc, nullptr, 1, out); }
 int tbrm_resources_create_slab(const tbrm_resources_desc* desc, const tbrm_slab* owned, tbrm_resources** out)
 {
     if (!owned) return fail(TBRM_ERR_INVALID_ARG, "null argument");
-    return create_impl(desc, owned, out);
+    return create_impl(desc, owned, 1, out);
 }
 
-static int create_impl(const tbrm_resources_desc* desc, const tbrm_slab* owned, tbrm_resources** out)
+// light_channels: 1, or 3 (tbrm_resources_create_rgb: not slab-resident)
+static int create_impl(const tbrm_resources_desc* desc, const tbrm_slab* owned, int light_channels, tbrm_resources** out)
 {
     if (!desc || !out) return fail(TBRM_ERR_INVALID_ARG, "null argument");
     *out = nullptr;
@@ -298,6 +352,7 @@ static int create_impl(const tbrm_resources_desc* desc, const tbrm_slab* owned, 
     tbrm_resources* r = new (std::nothrow) tbrm_resources();
     if (!r) return fail(TBRM_ERR_OUT_OF_MEMORY, "host allocation failed");
     r->desc = *desc;
+    r->light_channels = light_channels;
     // RaymarchVolume.cpp:850-861
     r->lv_dims[0] = desc->light_volume_half_resolution ? (desc->dim_x + 1) / 2 : desc->dim_x;
     r->lv_dims[1] = desc->light_volume_half_resolution ? (desc->dim_y + 1) / 2 : desc->dim_y;
@@ -385,7 +440,8 @@ static int create_impl(const tbrm_resources_desc* desc, const tbrm_slab* owned, 
     CREATE_TRY(hipMalloc((void**) &r->d_tf, 256 * sizeof(float4)));
     {
         tbrm_resources::Residency& q = r->res_light;
-        CREATE_TRY(hipMalloc(&q.alloc, (size_t) (q.hi - q.lo + (q.wrap_src >= 0 ? 1 : 0)) * q.layer_bytes));
+        // (a colour handle: its channels one behind the other, each a whole mono volume — light_bricked_bytes)
+        CREATE_TRY(hipMalloc(&q.alloc, (size_t) (q.hi - q.lo + (q.wrap_src >= 0 ? 1 : 0)) * q.layer_bytes * (size_t) r->light_channels));
         r->d_light = (char*) q.alloc - (size_t) q.lo * q.layer_bytes;
     }
     // XYZReadWriteBuffers: 4 buffers per axis in the light volume's format (RaymarchVolume.cpp:864-866,:889-891)
@@ -420,7 +476,7 @@ static int create_impl(const tbrm_resources_desc* desc, const tbrm_slab* owned, 
     for (int k = 0; k < 2; ++k)
         for (int e = 0; e < 2; ++e) CREATE_TRY(hipEventCreate(&r->ev[k][e]));
     // the light volume render target starts cleared
-    CREATE_TRY(hipMemsetAsync(r->res_light.alloc, 0, (size_t) (r->res_light.hi - r->res_light.lo + (r->res_light.wrap_src >= 0 ? 1 : 0)) * r->res_light.layer_bytes, r->stream));
+    CREATE_TRY(hipMemsetAsync(r->res_light.alloc, 0, (size_t) (r->res_light.hi - r->res_light.lo + (r->res_light.wrap_src >= 0 ? 1 : 0)) * r->res_light.layer_bytes * (size_t) r->light_channels, r->stream));
 #undef CREATE_TRY
     *out = r;
     return TBRM_OK;
@@ -576,7 +632,8 @@ int tbrm_add_dir_light(tbrm_resources* r, const tbrm_dir_light_params* light, in
     if (light_added) *light_added = 1;
     if (int e = bind(r)) return e;
     if (int e = begin_timed(r, 0)) return e;
-    const int e = enqueue_add(r, *light, added != 0, *world);
+    // (a colour handle: the light is white — include/tbrm_color_lights.h)
+    const int e = r->light_channels == 1 ? enqueue_add(r, *light, added != 0, *world) : enqueue_color_add(r, white(*light), added != 0, *world);
     const int e2 = end_timed(r, 0); // also after a failure: the events then bracket whatever was enqueued
     return e ? e : e2;
 }
@@ -585,6 +642,7 @@ int tbrm_add_dir_lights(tbrm_resources* r, const tbrm_dir_light_params* lights, 
                         int32_t* schedule, int32_t* n_entries)
 {
     if (r && r->resident) return fail(TBRM_ERR_UNSUPPORTED, "slab-resident handle: light operators run through tbrm_slab_*");
+    if (int e = refuse_color(r, "tbrm_add_dir_lights")) return e;
     if (n_entries) *n_entries = 0;
     if (!r || !world || (n_lights > 0 && !lights) || n_lights < 0) return fail(TBRM_ERR_INVALID_ARG, "null argument");
     if (!initialized(r)) return fail(TBRM_ERR_NOT_INITIALIZED, "resources have no volume or transfer function");
@@ -606,7 +664,8 @@ int tbrm_change_dir_light(tbrm_resources* r, const tbrm_dir_light_params* old_li
     if (light_added) *light_added = 1;
     if (int e = bind(r)) return e;
     if (int e = begin_timed(r, 0)) return e;
-    const int e = enqueue_change(r, *old_light, *new_light, *world);
+    const int e = r->light_channels == 1 ? enqueue_change(r, *old_light, *new_light, *world)
+                                         : enqueue_color_change(r, white(*old_light), white(*new_light), *world);
     const int e2 = end_timed(r, 0);
     return e ? e : e2;
 }
@@ -619,7 +678,7 @@ int tbrm_clear_light_volume(tbrm_resources* r, float clear_value)
     sweep_failure_cleared(r); // (a sweep that failed left the light volume undefined: this call defines it again)
     if (int e = begin_timed(r, 0)) return e;
     const tbrm_resources::Residency& q = r->res_light; // (all layers of an ordinary handle); padding voxels are never sampled
-    const size_t n = (size_t) r->lbn[0] * r->lbn[1] * 512 * (size_t) (q.hi - q.lo + (q.wrap_src >= 0 ? 1 : 0));
+    const size_t n = (size_t) r->lbn[0] * r->lbn[1] * 512 * (size_t) (q.hi - q.lo + (q.wrap_src >= 0 ? 1 : 0)) * (size_t) r->light_channels;
     HIP_TRY(launch_fill(q.alloc, r->lv_fmt, n, clear_value, r->stream));
     return end_timed(r, 0);
 }
@@ -627,41 +686,23 @@ int tbrm_clear_light_volume(tbrm_resources* r, float clear_value)
 int tbrm_download_light_volume(tbrm_resources* r, void* host_out, size_t n_bytes)
 {
     if (r && r->resident) return fail(TBRM_ERR_UNSUPPORTED, "slab-resident handle: read its slices with tbrm_download_light_slices");
-    if (!r || !host_out) return fail(TBRM_ERR_INVALID_ARG, "null argument");
-    if (n_bytes != r->light_bytes) return fail(TBRM_ERR_INVALID_ARG, "light volume is %zu bytes, got %zu", r->light_bytes, n_bytes);
-    if (int e = bind(r)) return e;
-    void* staging = nullptr;
-    HIP_TRY(hipMalloc(&staging, n_bytes));
-    const int dims[3] = {r->lv_dims[0], r->lv_dims[1], r->lv_dims[2]};
-    hipError_t e1 = launch_relayout(relayout_params(r->d_light, staging, dims, r->lbn, r->lv_fmt == FMT_U8 ? 1 : 4, false), r->stream);
-    if (e1 == hipSuccess) e1 = hipMemcpyAsync(host_out, staging, n_bytes, hipMemcpyDeviceToHost, r->stream);
-    if (e1 == hipSuccess) e1 = hipStreamSynchronize(r->stream);
-    (void) hipFree(staging);
-    HIP_TRY(e1);
-    return sweep_failed(r); // (the slices of a light volume a failed sweep left undefined are not handed out as good)
+    if (int e = refuse_color(r, "tbrm_download_light_volume (tbrm_download_light_channel)")) return e;
+    if (!r) return fail(TBRM_ERR_INVALID_ARG, "null argument");
+    return download_light_channel(r, 0, host_out, n_bytes);
 }
 
 int tbrm_upload_light_volume(tbrm_resources* r, const void* host_in, size_t n_bytes)
 {
     if (r && r->resident) return fail(TBRM_ERR_UNSUPPORTED, "slab-resident handle: the light volume is written by tbrm_slab_* only");
-    if (!r || !host_in) return fail(TBRM_ERR_INVALID_ARG, "null argument");
-    if (n_bytes != r->light_bytes) return fail(TBRM_ERR_INVALID_ARG, "light volume is %zu bytes, got %zu", r->light_bytes, n_bytes);
-    if (int e = bind(r)) return e;
-    void* staging = nullptr;
-    HIP_TRY(hipMalloc(&staging, n_bytes));
-    const int dims[3] = {r->lv_dims[0], r->lv_dims[1], r->lv_dims[2]};
-    hipError_t e1 = hipMemcpyAsync(staging, host_in, n_bytes, hipMemcpyHostToDevice, r->stream);
-    if (e1 == hipSuccess) e1 = launch_relayout(relayout_params(staging, r->d_light, dims, r->lbn, r->lv_fmt == FMT_U8 ? 1 : 4, true), r->stream);
-    if (e1 == hipSuccess) e1 = hipStreamSynchronize(r->stream);
-    (void) hipFree(staging);
-    HIP_TRY(e1);
-    sweep_failure_cleared(r); // (the light volume is defined again)
-    return TBRM_OK;
+    if (int e = refuse_color(r, "tbrm_upload_light_volume (tbrm_upload_light_channel)")) return e;
+    if (!r) return fail(TBRM_ERR_INVALID_ARG, "null argument");
+    return upload_light_channel(r, 0, host_in, n_bytes);
 }
 
 int tbrm_light_volume_device_ptr(tbrm_resources* r, void** out_ptr, size_t* out_bytes)
 {
     if (r && r->resident) return fail(TBRM_ERR_UNSUPPORTED, "slab-resident handle: exchange its boundary layers with tbrm_slab_light_halo");
+    if (int e = refuse_color(r, "tbrm_light_volume_device_ptr")) return e;
     if (!r || !out_ptr) return fail(TBRM_ERR_INVALID_ARG, "null argument");
     *out_ptr = r->d_light; // bricked layout (DESIGN.md "Data layout")
     if (out_bytes) *out_bytes = r->light_bricked_bytes;
@@ -866,3 +907,10 @@ int tbrm_host_world_to_local(const tbrm_transform* t, float out_m[12])
 }
 
 } // extern "C"
+
+namespace tbrm_host {
+int create_handle(const tbrm_resources_desc* desc, const tbrm_slab* owned, int light_channels, tbrm_resources** out)
+{
+    return create_impl(desc, owned, light_channels, out);
+}
+} // namespace tbrm_host

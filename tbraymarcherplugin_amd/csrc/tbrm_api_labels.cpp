@@ -150,6 +150,7 @@ int tbrm_make_default_label_colors(float* out)
 int tbrm_upload_label_volume(tbrm_resources* r, const uint8_t* host_labels, size_t n_bytes)
 {
     if (r && r->resident) return fail(TBRM_ERR_UNSUPPORTED, "slab-resident handle: label volumes are not supported");
+    if (int e = refuse_color(r, "tbrm_upload_label_volume")) return e;
     if (!r || !host_labels) return fail(TBRM_ERR_INVALID_ARG, "null argument");
     if (n_bytes != label_voxels(r)) return fail(TBRM_ERR_INVALID_ARG, "label volume is %zu bytes, expected %zu", n_bytes, label_voxels(r));
     if (int e = bind(r)) return e;

@@ -82,7 +82,12 @@ int tbrm_raymarch_lit_device(tbrm_resources* r, const tbrm_camera* cam, const tb
     }
     if (int e = label_ray_params(r, p)) return e; // (tbrm_labels.h: the label step, when a label volume shows something)
     if (int e = begin_timed(r, 1)) return e;
-    HIP_TRY(launch_raymarch(p, r->stream));
+    if (r->light_channels == 3) { // (tbrm_color_lights.h: ColorSample.rgb x LightVolume.rgb; a colour handle has no label volume)
+        p.light = r->light_channel(0);
+        p.light_g = r->light_channel(1);
+        p.light_b = r->light_channel(2);
+        HIP_TRY(launch_raymarch_rgb(p, r->stream));
+    } else HIP_TRY(launch_raymarch(p, r->stream));
     ++r->launches[2];
     return end_timed(r, 1);
 }
@@ -91,6 +96,7 @@ int tbrm_raymarch_lit_slab_device(tbrm_resources* r, const tbrm_camera* cam, con
                                   const tbrm_world_params* world, const float* device_scene_depth, float* device_state_rgba,
                                   const tbrm_slab* slab, int direction)
 {
+    if (int e = refuse_color(r, "tbrm_raymarch_lit_slab_device")) return e;
     if (!r || !cam || !tile || !rp || !world || !device_state_rgba || !slab) return fail(TBRM_ERR_INVALID_ARG, "null argument");
     if (r->d_labels) return fail(TBRM_ERR_UNSUPPORTED, "the slab stage of the lit march has no label step: release the label volume first");
     if (!initialized(r)) return fail(TBRM_ERR_NOT_INITIALIZED, "resources have no volume or transfer function");

@@ -17,6 +17,7 @@ extern "C" {
 int tbrm_slab_light_begin(tbrm_resources* r, const tbrm_dir_light_params* removed, const tbrm_dir_light_params* light, int added,
                           const tbrm_world_params* world, const tbrm_slab* slab, int32_t* n_passes)
 {
+    if (int e = refuse_color(r, "tbrm_slab_light_begin")) return e;
     if (!r || !light || !world || !slab || !n_passes) return fail(TBRM_ERR_INVALID_ARG, "null argument");
     if (!initialized(r)) return fail(TBRM_ERR_NOT_INITIALIZED, "resources have no volume or transfer function");
     *n_passes = 0;
@@ -76,6 +77,7 @@ int tbrm_slab_light_begin(tbrm_resources* r, const tbrm_dir_light_params* remove
 
 int tbrm_slab_pass_begin(tbrm_resources* r, int32_t pass, tbrm_slab_pass* out)
 {
+    if (int e = refuse_color(r, "tbrm_slab_pass_begin")) return e;
     if (!r || !out) return fail(TBRM_ERR_INVALID_ARG, "null argument");
     if (!r->slab_op || pass < 0 || pass >= r->slab_op->n) return fail(TBRM_ERR_INVALID_ARG, "no such pass (tbrm_slab_light_begin first)");
     if (int e = bind(r)) return e;
@@ -109,6 +111,7 @@ int tbrm_slab_pass_begin(tbrm_resources* r, int32_t pass, tbrm_slab_pass* out)
 
 int tbrm_slab_pass_chunk(tbrm_resources* r, int32_t chunk)
 {
+    if (int e = refuse_color(r, "tbrm_slab_pass_chunk")) return e;
     if (!r || !r->slab_op || r->slab_op->current < 0) return fail(TBRM_ERR_INVALID_ARG, "no pass in flight (tbrm_slab_pass_begin first)");
     const PassPlan& pl = r->slab_op->plan;
     if (chunk < 0 || chunk >= pl.n_chunks) return fail(TBRM_ERR_INVALID_ARG, "chunk %d of %d", chunk, pl.n_chunks);
@@ -118,6 +121,7 @@ int tbrm_slab_pass_chunk(tbrm_resources* r, int32_t chunk)
 
 int tbrm_slab_pass_plane(tbrm_resources* r, int32_t boundary, int32_t stream, void** device_plane)
 {
+    if (int e = refuse_color(r, "tbrm_slab_pass_plane")) return e;
     if (!r || !device_plane || !r->slab_op || r->slab_op->current < 0) return fail(TBRM_ERR_INVALID_ARG, "no pass in flight");
     const PassPlan& pl = r->slab_op->plan;
     if (boundary < 0 || boundary > pl.n_chunks || stream < 0 || stream >= (pl.two_streams() ? 2 : 1))
@@ -140,6 +144,7 @@ char* layer_address(const tbrm_resources::Residency& q, int layer)
 
 int tbrm_slab_resident_slices(const tbrm_resources* r, int32_t data[3], int32_t light[3])
 {
+    if (int e = refuse_color(r, "tbrm_slab_resident_slices")) return e;
     if (!r || !data || !light) return fail(TBRM_ERR_INVALID_ARG, "null argument");
     const tbrm_resources::Residency* q[2] = {&r->res_data, &r->res_light};
     const int depth[2] = {r->desc.dim_z, r->lv_dims[2]};
@@ -186,6 +191,7 @@ int tbrm_upload_volume_slices(tbrm_resources* r, int32_t z_begin, int32_t z_coun
 
 int tbrm_download_light_slices(tbrm_resources* r, int32_t z_begin, int32_t z_count, void* host_out, size_t n_bytes)
 {
+    if (int e = refuse_color(r, "tbrm_download_light_slices")) return e;
     if (!r || !host_out) return fail(TBRM_ERR_INVALID_ARG, "null argument");
     const int nz = r->lv_dims[2];
     const size_t esz = r->lv_fmt == FMT_U8 ? 1 : 4, slice = (size_t) r->lv_dims[0] * r->lv_dims[1] * esz;
@@ -215,6 +221,7 @@ int tbrm_download_light_slices(tbrm_resources* r, int32_t z_begin, int32_t z_cou
 
 int tbrm_slab_light_halo(tbrm_resources* r, int32_t side, void** send_layer, void** recv_layer, size_t* layer_bytes)
 {
+    if (int e = refuse_color(r, "tbrm_slab_light_halo")) return e;
     if (!r || !send_layer || !recv_layer || !layer_bytes) return fail(TBRM_ERR_INVALID_ARG, "null argument");
     if (!r->resident) return fail(TBRM_ERR_INVALID_ARG, "not a slab-resident handle");
     if (side != 0 && side != 1) return fail(TBRM_ERR_INVALID_ARG, "side is 0 (towards z = 0) or 1");

@@ -269,6 +269,8 @@ struct RayParams {
     float oct_depth0;           // depth of octree level 0 (the z coordinate is rescaled by data depth / this)
     const uint8_t* labels;      // k_raymarch_lit LABELS: the label volume, bricked on the data volume's grid (null: no label step)
     const float4* lab_colors;   // ... its colour table (256 x RGBA float)
+    const void* light_g;        // k_raymarch_lit RGB (colour handles, tbrm_color_lights.h): the G and B channels of the light volume,
+    const void* light_b;        // laid out like `light` (then the R channel); null: a mono light volume
 };
 
 struct BrickParams {
@@ -384,6 +386,7 @@ hipError_t launch_light_sweep_chain(const SweepChainArgs& c, int mode, hipStream
 hipError_t launch_fill(void* dst, int fmt, size_t n, float value, hipStream_t s);
 hipError_t launch_propagate_slice(const PropParams& p, bool change, hipStream_t s);
 hipError_t launch_raymarch(const RayParams& p, hipStream_t s);
+hipError_t launch_raymarch_rgb(const RayParams& p, hipStream_t s); // (colour handles: tbrm_kernels.hip compiled as the RGB unit)
 hipError_t launch_raymarch_intensity(const RayParams& p, hipStream_t s);
 hipError_t launch_raymarch_octree(const RayParams& p, hipStream_t s);
 hipError_t launch_octree_level(const OctreeParams& p, bool base, hipStream_t s);

@@ -14,6 +14,12 @@
 
 namespace tbrm {
 
+// Compiled twice (build.py): as it stands, and with -DTBRM_RAY_RGB_UNIT=1 for k_raymarch_lit's RGB-light form alone
+// (launch_raymarch_rgb), so that the two sets of instantiations build side by side.
+#ifdef TBRM_RAY_RGB_UNIT
+#undef TBRM_RAY_STATS // (the diagnostics build counts in the mono unit alone)
+#endif
+#ifndef TBRM_RAY_RGB_UNIT
 // ------------------------------------------------------------------------------------------------------------
 // fill
 
@@ -41,6 +47,7 @@ hipError_t launch_fill(void* dst, int fmt, size_t n, float value, hipStream_t s)
     hipLaunchKernelGGL(k_fill<FMT_F32>, dim3(grid), dim3(block), 0, s, dst, n, value);
     return hipGetLastError();
 }
+#endif // !TBRM_RAY_RGB_UNIT
 
 // ------------------------------------------------------------------------------------------------------------
 // raymarch
@@ -176,9 +183,16 @@ extern "C" __attribute__((visibility("default"))) int tbrm_debug_ray_stats(unsig
 // and the early-exit test. The full step's (rgb * a', a') of every colour-table entry is computed once per workgroup into LDS
 // (dynamic, behind the tables: LABELS = false keeps the static layout); the fractional step computes its own. The host passes the
 // skipping distance field that has the label occupancy merged in (tbrm_api_labels.cpp), so skipped samples stay exact no-ops.
-template <int DFMT, int LFMT, int DMODE, int kRayLanes, bool SLAB = false, bool TAB = false, bool LABELS = false>
+//
+// RGB: the light volume of a colour handle (include/tbrm_color_lights.h): three channels p.light / p.light_g / p.light_b of one
+// layout, so one set of tap offsets and one set of weights serves all three (the data taps' where same_grid holds). The light is
+// needed only behind a_sat != 0: the channels are fetched and filtered there, one after the other — three sets of raw taps beside
+// the data taps do not fit the 80 registers of six waves per SIMD. The sample is ((cs.r l_r) a, (cs.g l_g) a, (cs.b l_b) a, a);
+// nothing else of the march sees the light.
+template <int DFMT, int LFMT, int DMODE, int kRayLanes, bool SLAB = false, bool TAB = false, bool LABELS = false, bool RGB = false>
 __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6 waves per SIMD (80 VGPRs): measured 3-8 % faster than 5 or 8
 {
+    static_assert(!(RGB && (SLAB || LABELS)), "colour handles have no slab stage and no label step");
     static_assert(kRayLanes == 4 || kRayLanes == 8, "instantiated for 4 and 8 lanes per ray");
     static_assert(!(TAB && SLAB), "slab stages keep the arithmetic path (relocated layers)");
     static_assert(!(LABELS && SLAB), "slab stages have no label step");
@@ -351,6 +365,7 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
         if (live) {
             RawTaps<DFMT> dtaps;
             RawTaps<LFMT> ltaps;
+            [[maybe_unused]] TapOffsets lt{}; // RGB: the light taps' offsets, shared by the three channels
             float gx, gy, gz;
             TapOffsets dt;
             if constexpr (TAB) dt = tab_dt;
@@ -366,13 +381,15 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
             const float sp0 = saturate_(q0), sp1 = saturate_(q1), sp2 = saturate_(q2);
             if (same_grid && sp0 == q0 && sp1 == q1 && sp2 == q2) {
                 gx = fx; gy = fy; gz = fz;
-                ltaps.issue(p.light, dt);
+                if constexpr (RGB) lt = dt;
+                else ltaps.issue(p.light, dt);
             } else {
                 int lx, ly, lz; // (saturated coordinates: in [0, 1], or NaN -> 0)
                 texel_split_bounded(sp0, lnx, lx, gx);
                 texel_split_bounded(sp1, lny, ly, gy);
                 texel_split_bounded(sp2, lnz, lz, gz);
-                ltaps.issue(p.light, tap_offsets<ADDR_WRAP, SLAB>(lightv, lx, ly, lz));
+                if constexpr (RGB) lt = tap_offsets<ADDR_WRAP, SLAB>(lightv, lx, ly, lz);
+                else ltaps.issue(p.light, tap_offsets<ADDR_WRAP, SLAB>(lightv, lx, ly, lz));
             }
             const float v = dtaps.filter(fx, fy, fz);
             // SampleWindowedTransferFunction (WindowedSampling.usf:20-37)
@@ -384,8 +401,18 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
                     // (a_sat in (0, 1]; the step is 100 / steps or 100 x a fraction in (0, 1): >= 0 unless the host passed a negative
                     // step count, which build_ray_params rejects — pow01_ is pow_ on that domain, bit for bit)
                     const float a = one_minus_pow01_(1.0f - a_sat, step);
-                    const float l = ltaps.filter(gx, gy, gz);
-                    x = make_float4((cs.x * l) * a, (cs.y * l) * a, (cs.z * l) * a, a);
+                    if constexpr (RGB) {
+                        ltaps.issue(p.light, lt);
+                        const float lr = ltaps.filter(gx, gy, gz);
+                        ltaps.issue(p.light_g, lt);
+                        const float lg = ltaps.filter(gx, gy, gz);
+                        ltaps.issue(p.light_b, lt);
+                        const float lb = ltaps.filter(gx, gy, gz);
+                        x = make_float4((cs.x * lr) * a, (cs.y * lg) * a, (cs.z * lb) * a, a);
+                    } else {
+                        const float l = ltaps.filter(gx, gy, gz);
+                        x = make_float4((cs.x * l) * a, (cs.y * l) * a, (cs.z * l) * a, a);
+                    }
                 }
             }
             if constexpr (LABELS) {
@@ -482,7 +509,7 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
     if ((SLAB ? mine : valid) && b == 0) reinterpret_cast<float4*>(p.out)[(size_t) j * p.tile_w + i] = make_float4(le0, le1, le2, le3);
 }
 
-template <int DFMT, int LFMT, int RL, bool LABELS>
+template <int DFMT, int LFMT, int RL, bool LABELS, bool RGB>
 static hipError_t launch_ray3(const RayParams& p, hipStream_t s)
 {
     constexpr int BW = 8, BH = RL == 4 ? 8 : 4; // 4 waves of 4x4 / 4x2 rays
@@ -490,7 +517,7 @@ static hipError_t launch_ray3(const RayParams& p, hipStream_t s)
     // LABELS: the colour-table contributions and the exchanged label bytes, behind the tables (4.5 KiB)
     constexpr size_t lab_bytes = LABELS ? 256 * sizeof(float4) + 256 * sizeof(short) : 0;
     if (p.slab_on) {
-        if constexpr (LABELS) return hipErrorInvalidValue; // (the host refuses slab stages while labels are attached)
+        if constexpr (LABELS || RGB) return hipErrorInvalidValue; // (the host refuses slab stages while labels are attached, and on colour handles)
         else {
             if (p.data_addr_mode == ADDR_CLAMP) hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_CLAMP, RL, true>), grid, block, 0, s, p);
             else hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_WRAP, RL, true>), grid, block, 0, s, p);
@@ -502,15 +529,15 @@ static hipError_t launch_ray3(const RayParams& p, hipStream_t s)
     const size_t tab_bytes = (size_t) ((p.data.nx + p.data.ny + p.data.nz + 12 + 1) & ~1) * sizeof(uint2);
     const bool tab = p.tab != nullptr && tune(TUNE_RAY_TABLES) != 0 && (float) std::max(p.data.nx, std::max(p.data.ny, p.data.nz)) <= p.steps && tab_bytes <= 16 * 1024;
     if (tab) {
-        if (p.data_addr_mode == ADDR_CLAMP) hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_CLAMP, RL, false, true, LABELS>), grid, block, tab_bytes + lab_bytes, s, p);
-        else hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_WRAP, RL, false, true, LABELS>), grid, block, tab_bytes + lab_bytes, s, p);
+        if (p.data_addr_mode == ADDR_CLAMP) hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_CLAMP, RL, false, true, LABELS, RGB>), grid, block, tab_bytes + lab_bytes, s, p);
+        else hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_WRAP, RL, false, true, LABELS, RGB>), grid, block, tab_bytes + lab_bytes, s, p);
         return hipGetLastError();
     }
-    if (p.data_addr_mode == ADDR_CLAMP) hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_CLAMP, RL, false, false, LABELS>), grid, block, lab_bytes, s, p);
-    else hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_WRAP, RL, false, false, LABELS>), grid, block, lab_bytes, s, p);
+    if (p.data_addr_mode == ADDR_CLAMP) hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_CLAMP, RL, false, false, LABELS, RGB>), grid, block, lab_bytes, s, p);
+    else hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_WRAP, RL, false, false, LABELS, RGB>), grid, block, lab_bytes, s, p);
     return hipGetLastError();
 }
-template <int DFMT, int LFMT>
+template <int DFMT, int LFMT, bool RGB>
 static hipError_t launch_ray2(const RayParams& p, hipStream_t s)
 {
     // Lanes per ray, measured on MI355X (ms per frame; 2 lanes: 0.85 / 0.64 / 0.27, 16 lanes: 0.80 / 1.50 / 0.15):
@@ -523,23 +550,33 @@ static hipError_t launch_ray2(const RayParams& p, hipStream_t s)
     const double load = (double) p.tile_w * (double) p.tile_h * 512.0 / (double) (p.steps > 1.0f ? p.steps : 1.0f);
     const int forced = tune(TUNE_RAY_LANES);
     const int rl = forced ? forced : (load <= 700000.0 ? 8 : 4);
-    if (p.labels) return rl == 8 ? launch_ray3<DFMT, LFMT, 8, true>(p, s) : launch_ray3<DFMT, LFMT, 4, true>(p, s);
-    return rl == 8 ? launch_ray3<DFMT, LFMT, 8, false>(p, s) : launch_ray3<DFMT, LFMT, 4, false>(p, s);
+    if constexpr (RGB) {
+        if (p.labels || !p.light_g || !p.light_b) return hipErrorInvalidValue; // (the host refuses label volumes on colour handles)
+        return rl == 8 ? launch_ray3<DFMT, LFMT, 8, false, true>(p, s) : launch_ray3<DFMT, LFMT, 4, false, true>(p, s);
+    } else {
+        if (p.labels) return rl == 8 ? launch_ray3<DFMT, LFMT, 8, true, false>(p, s) : launch_ray3<DFMT, LFMT, 4, true, false>(p, s);
+        return rl == 8 ? launch_ray3<DFMT, LFMT, 8, false, false>(p, s) : launch_ray3<DFMT, LFMT, 4, false, false>(p, s);
+    }
 }
-template <int DFMT>
+template <int DFMT, bool RGB>
 static hipError_t launch_ray1(const RayParams& p, hipStream_t s)
 {
-    return p.lv_fmt == FMT_U8 ? launch_ray2<DFMT, FMT_U8>(p, s) : launch_ray2<DFMT, FMT_F32>(p, s);
+    return p.lv_fmt == FMT_U8 ? launch_ray2<DFMT, FMT_U8, RGB>(p, s) : launch_ray2<DFMT, FMT_F32, RGB>(p, s);
 }
-hipError_t launch_raymarch(const RayParams& p, hipStream_t s)
+template <bool RGB>
+static hipError_t launch_ray0(const RayParams& p, hipStream_t s)
 {
     if (p.tile_w <= 0 || p.tile_h <= 0) return hipSuccess;
     switch (p.data.fmt) {
-        case FMT_U8: return launch_ray1<FMT_U8>(p, s);
-        case FMT_U16: return launch_ray1<FMT_U16>(p, s);
-        default: return launch_ray1<FMT_F32>(p, s);
+        case FMT_U8: return launch_ray1<FMT_U8, RGB>(p, s);
+        case FMT_U16: return launch_ray1<FMT_U16, RGB>(p, s);
+        default: return launch_ray1<FMT_F32, RGB>(p, s);
     }
 }
+#ifdef TBRM_RAY_RGB_UNIT
+hipError_t launch_raymarch_rgb(const RayParams& p, hipStream_t s) { return launch_ray0<true>(p, s); }
+#else
+hipError_t launch_raymarch(const RayParams& p, hipStream_t s) { return launch_ray0<false>(p, s); }
 
 // ---- self-test of the division-free window position (tf_position_fast against the IEEE quotient, every float in [0, 1]) --------------
 __global__ __launch_bounds__(256) void k_selftest_window_division(WindowDev w, unsigned long long* mismatches)
@@ -776,5 +813,7 @@ hipError_t launch_count_samples(const RayParams& p, hipStream_t s)
     hipLaunchKernelGGL(k_count_samples, grid, block, 0, s, p);
     return hipGetLastError();
 }
+
+#endif // TBRM_RAY_RGB_UNIT
 
 } // namespace tbrm

@@ -42,9 +42,21 @@ struct HostProbe {
     ~HostProbe() { if (on) fprintf(stderr, "[tbrm host] %s:%s\n", what, line.c_str()); }
 };
 
+// A further light channel of a coloured operator (tbrm_color_lights.h): the operator's passes once more — the same geometry, this
+// channel's intensities — over this channel's light volume.
+struct ChannelPasses {
+    void* light = nullptr;
+    std::vector<PassSpec> specs;
+};
+
 // partner (optional, one entry per spec): the spec that is swept TOGETHER with this one (enqueue_sweep_pair), -1: none. The
 // partner's own turn is skipped.
-static int run_passes(tbrm_resources* r, const PropParams& base, std::vector<PassSpec> specs, std::vector<int> partner = {})
+// more (optional): the passes are planned ONCE and enqueued once per channel — base.light with `specs`, then every entry of `more`.
+// Occlusion does not depend on intensity: what the first channel's sweep passes sampled (scratch buffers, cache entries) is what the
+// other channels' sweeps read, so a coloured operator launches the occlusion a mono operator launches. A pass on the chunked chain or
+// the slice-per-launch path, whose occlusion is part of the pass, samples it again for every channel.
+static int run_passes(tbrm_resources* r, const PropParams& base, std::vector<PassSpec> specs, std::vector<int> partner = {},
+                      const std::vector<ChannelPasses>& more = {})
 {
     if (int e = sweep_failed(r)) return e; // (an earlier sweep left the light volume undefined: nothing to build on)
     if (int e = ensure_reserved(r)) return e; // (a handle nobody reserved: once, with the defaults — tbrm_resources_reserve)
@@ -63,7 +75,7 @@ static int run_passes(tbrm_resources* r, const PropParams& base, std::vector<Pas
         const PassSpec q = specs[i];
         PassPlan plan;
         const int e = plan_pass(r, base, q.a, q.two ? &q.r : nullptr, q.b_added, nullptr, plan, q.mode, q.b_added2);
-        if (e == TBRM_ERR_UNSUPPORTED && q.mode == PASS_ADD2) { // the pair has no chunked form: light a's pass, then light b's
+        if (e == TBRM_ERR_UNSUPPORTED && q.mode == PASS_ADD2 && more.empty()) { // the pair has no chunked form: light a's pass, then light b's
             PassSpec first = q, second = q;
             first.two = second.two = false;
             first.mode = second.mode = PASS_ADD;
@@ -106,10 +118,12 @@ static int run_passes(tbrm_resources* r, const PropParams& base, std::vector<Pas
     if (any_pair) // (a group of two lights: four passes, four scratch buffers — every occlusion can go first)
         for (size_t k = 0; k < specs.size(); ++k)
             if (int e = occlusion_of(k)) return e;
+    void* channel_light = base.light; // (the channel being enqueued)
     auto run_single = [&](size_t i) -> int {
         const PassSpec& q = specs[i];
         if (!chunked[i]) {
             PropParams p = base;
+            p.light = channel_light;
             p.b_added = q.b_added;
             if (int e = enqueue_pass_sliced(r, p, q.a, q.two ? &q.r : nullptr)) return e;
             ++r->passes[2];
@@ -135,44 +149,56 @@ static int run_passes(tbrm_resources* r, const PropParams& base, std::vector<Pas
         return pl.sweep && (pl.mode == PASS_ADD || pl.mode == PASS_CHANGE) && !pl.sq.r_from_records && !pl.sq.lv_f32 && !(pl.sq.debug & 1) &&
                sweep_halo_chunks(pl.sq.hx, pl.sq.hy) <= 3;
     };
-    for (size_t i = 0; i < specs.size(); ++i) {
-        if (is_second[i]) continue; // (took its turn with its partner)
-        if (chain_max >= 2 && chainable(i)) {
-            size_t len = 1;
-            while ((int) len < chain_max && chainable(i + len) && plans[i + len].mode == plans[i].mode) {
-                // A launch waits for the occlusion of ALL its passes: a pass whose factors are still to be computed joins only the
-                // pass it shares its occlusion launch with (the two passes of a light, dual_fit) — the occlusion of the light after
-                // runs beside this launch instead of in front of it (measured, cold reset of four lights: 3.18 ms light by light,
-                // 3.25 with two lights' occlusion in front of one launch of four passes)
-                const PassPlan& nx = plans[i + len];
-                if (nx.occ_mode >= 0 && !nx.occ_enqueued && !dual_fit(plans[i + len - 1], nx)) break;
-                bool fresh_buffer = true; // (every pass of a launch reads its own scratch buffer)
-                for (size_t k = 0; k < len; ++k) fresh_buffer = fresh_buffer && plans[i + k].f_buf != plans[i + len].f_buf;
-                if (!fresh_buffer) break;
-                ++len;
+    auto enqueue_channel = [&]() -> int { // every pass, over channel_light
+        for (size_t i = 0; i < specs.size(); ++i) {
+            if (is_second[i]) continue; // (took its turn with its partner)
+            if (chain_max >= 2 && chainable(i)) {
+                size_t len = 1;
+                while ((int) len < chain_max && chainable(i + len) && plans[i + len].mode == plans[i].mode) {
+                    // A launch waits for the occlusion of ALL its passes: a pass whose factors are still to be computed joins only the
+                    // pass it shares its occlusion launch with (the two passes of a light, dual_fit) — the occlusion of the light after
+                    // runs beside this launch instead of in front of it (measured, cold reset of four lights: 3.18 ms light by light,
+                    // 3.25 with two lights' occlusion in front of one launch of four passes)
+                    const PassPlan& nx = plans[i + len];
+                    if (nx.occ_mode >= 0 && !nx.occ_enqueued && !dual_fit(plans[i + len - 1], nx)) break;
+                    bool fresh_buffer = true; // (every pass of a launch reads its own scratch buffer)
+                    for (size_t k = 0; k < len; ++k) fresh_buffer = fresh_buffer && plans[i + k].f_buf != plans[i + len].f_buf;
+                    if (!fresh_buffer) break;
+                    ++len;
+                }
+                if (len >= 2) {
+                    if (int e = enqueue_sweep_chain(r, &plans[i], (int) len)) { quiesce_occ_stream(r); return e; }
+                    r->passes[0] += len;
+                    probe.lap("chain");
+                    i += len - 1;
+                    continue;
+                }
             }
-            if (len >= 2) {
-                if (int e = enqueue_sweep_chain(r, &plans[i], (int) len)) { quiesce_occ_stream(r); return e; }
-                r->passes[0] += len;
-                probe.lap("chain");
-                i += len - 1;
+            if (partner[i] >= 0) {
+                const size_t j = (size_t) partner[i];
+                SweepFit fit;
+                if (pair_sweeps[i] && sweep_fit(r, specs[i].a, &specs[j].a, PASS_CHANGE, fit) && !fit.two_way) {
+                    if (int e = enqueue_sweep_pair(r, plans[i], plans[j], fit)) { quiesce_occ_stream(r); return e; }
+                    r->passes[0] += 2;
+                    probe.lap("pair");
+                    continue;
+                }
+                if (int e = run_single(i)) return e; // (no shared sweep after all: the same two passes, in the same order)
+                if (int e = run_single(j)) return e;
                 continue;
             }
+            if (int e = run_single(i)) return e;
         }
-        if (partner[i] >= 0) {
-            const size_t j = (size_t) partner[i];
-            SweepFit fit;
-            if (pair_sweeps[i] && sweep_fit(r, specs[i].a, &specs[j].a, PASS_CHANGE, fit) && !fit.two_way) {
-                if (int e = enqueue_sweep_pair(r, plans[i], plans[j], fit)) { quiesce_occ_stream(r); return e; }
-                r->passes[0] += 2;
-                probe.lap("pair");
-                continue;
-            }
-            if (int e = run_single(i)) return e; // (no shared sweep after all: the same two passes, in the same order)
-            if (int e = run_single(j)) return e;
-            continue;
-        }
-        if (int e = run_single(i)) return e;
+        return TBRM_OK;
+    };
+    if (int e = enqueue_channel()) return e;
+    for (const ChannelPasses& m : more) { // the same plans, bound to the next channel's light volume and intensities
+        if (m.specs.size() != specs.size()) return fail(TBRM_ERR_INVALID_ARG, "a channel of %zu passes beside one of %zu", m.specs.size(), specs.size());
+        channel_light = m.light;
+        specs = m.specs;
+        for (size_t i = 0; i < specs.size(); ++i)
+            if (chunked[i]) rebind_light_channel(r, plans[i], m.light, specs[i].a, specs[i].two ? &specs[i].r : nullptr);
+        if (int e = enqueue_channel()) return e;
     }
     if (r->occ_stream) { // "this operator's sweeps are done" (wait_for_readers)
         const int k = (int) (r->op_serial % tbrm_resources::kOpEvents);
@@ -366,21 +392,20 @@ int enqueue_add_batch(tbrm_resources* r, const tbrm_dir_light_params* lights, in
     return run_passes(r, base, specs);
 }
 
-// ChangeDirLightInSingleLightVolume_RenderThread (LightingShaders.cpp:168-326)
-int enqueue_change(tbrm_resources* r, const tbrm_dir_light_params& removed, const tbrm_dir_light_params& added_light,
-                   const tbrm_world_params& world)
+// the axis passes of ChangeDirLightInSingleLightVolume_RenderThread (LightingShaders.cpp:168-326) appended to `specs`; false: a
+// zero direction, the operator does nothing (:173-179)
+static bool change_light_specs(const tbrm_resources* r, const tbrm_dir_light_params& removed, const tbrm_dir_light_params& added_light,
+                               const tbrm_world_params& world, std::vector<PassSpec>& specs)
 {
     tbrm_light_pass rp[2], ap[2];
     int rn = 0, an = 0;
     const bool r_ok = host_light_passes(removed, world, r->lv_dims, r->desc.border_mode, rp, &rn);
     const bool a_ok = host_light_passes(added_light, world, r->lv_dims, r->desc.border_mode, ap, &an);
-    if (!r_ok || !a_ok) return TBRM_OK; // :173-179
-    const PropParams base = base_prop_params(r, world);
-    std::vector<PassSpec> specs;
+    if (!r_ok || !a_ok) return false;
     if (rp[0].face != ap[0].face || rp[1].face != ap[1].face) { // :192-198: remove the old light, add the new one
         add_light_specs(r, removed, false, world, specs);
         add_light_specs(r, added_light, true, world, specs);
-        return run_passes(r, base, specs);
+        return true;
     }
     for (int i = 0; i < 2; ++i) { // no break on weight 0 (:238)
         // Both streams dark (weight 0 on this axis for old and new light): buffers and borders are 0, every
@@ -394,7 +419,86 @@ int enqueue_change(tbrm_resources* r, const tbrm_dir_light_params& removed, cons
         q.mode = PASS_CHANGE;
         specs.push_back(q);
     }
-    return run_passes(r, base, specs);
+    return true;
+}
+
+// ChangeDirLightInSingleLightVolume_RenderThread (LightingShaders.cpp:168-326)
+int enqueue_change(tbrm_resources* r, const tbrm_dir_light_params& removed, const tbrm_dir_light_params& added_light,
+                   const tbrm_world_params& world)
+{
+    std::vector<PassSpec> specs;
+    if (!change_light_specs(r, removed, added_light, world, specs)) return TBRM_OK;
+    return run_passes(r, base_prop_params(r, world), specs);
+}
+
+// ---- coloured lights (include/tbrm_color_lights.h) -------------------------------------------------------------------------------------
+// The rule, stated once: a coloured operator on a colour handle is the mono operator on every LIVE channel c, run on that channel's
+// volume (three mono-layout volumes in one allocation: tbrm_resources::light_channel) with the light's intensity replaced by
+// I_c = light_intensity * color[c], one float32 product — so a channel is, bit for bit, what a mono handle computes, on whichever
+// path the planner picks. A channel is live unless every intensity the operator propagates on it is 0: the shaders then write
+// nothing (|L| > 1e-3 never holds, AddDirLightShader.usf:123; a Change 0 -> 0 likewise).
+// Occlusion depends on volume, transfer function, window, clip plane and direction, not on intensity: the live channels' passes are
+// one list of passes that differ in intensity alone, planned once and enqueued channel after channel (run_passes, ChannelPasses), so
+// the operator's sweep passes sample occlusion — or find it in the factor cache — once, whether the cache is on or off. A pass on
+// the chunked chain or the slice-per-launch path, whose occlusion is part of the pass, samples it per channel.
+static tbrm_dir_light_params channel_light(const tbrm_color_dir_light& l, int c)
+{
+    tbrm_dir_light_params q = l.light;
+    q.light_intensity = l.light.light_intensity * l.color[c];
+    return q;
+}
+
+// specs_of(c): the mono operator's passes on channel c; empty: the channel is dead, or the operator does nothing (a zero direction)
+template <class SpecsOf>
+static int run_color_passes(tbrm_resources* r, const tbrm_world_params& world, SpecsOf specs_of)
+{
+    std::vector<ChannelPasses> live;
+    for (int c = 0; c < r->light_channels; ++c) {
+        ChannelPasses ch{r->light_channel(c), specs_of(c)};
+        if (!ch.specs.empty()) live.push_back(std::move(ch));
+    }
+    if (live.empty()) return TBRM_OK;
+    PropParams base = base_prop_params(r, world);
+    // One list of passes for all channels — unless a channel's list is shorter: a Change drops an axis pass on which both of ITS
+    // streams are dark, which a channel with one intensity 0 can be where another is not. Then every channel runs on its own.
+    bool one_list = true;
+    for (const ChannelPasses& ch : live) {
+        one_list = one_list && ch.specs.size() == live[0].specs.size();
+        for (size_t i = 0; one_list && i < ch.specs.size(); ++i) {
+            const PassSpec &x = ch.specs[i], &y = live[0].specs[i];
+            one_list = x.a.face == y.a.face && x.two == y.two && x.mode == y.mode && x.b_added == y.b_added && (!x.two || x.r.face == y.r.face);
+        }
+    }
+    if (one_list) {
+        base.light = live[0].light;
+        return run_passes(r, base, live[0].specs, {}, std::vector<ChannelPasses>(live.begin() + 1, live.end()));
+    }
+    for (const ChannelPasses& ch : live) {
+        base.light = ch.light;
+        if (int e = run_passes(r, base, ch.specs)) return e;
+    }
+    return TBRM_OK;
+}
+
+int enqueue_color_add(tbrm_resources* r, const tbrm_color_dir_light& light, bool added, const tbrm_world_params& world)
+{
+    return run_color_passes(r, world, [&](int c) {
+        std::vector<PassSpec> specs;
+        const tbrm_dir_light_params l = channel_light(light, c);
+        if (l.light_intensity != 0.0f) add_light_specs(r, l, added, world, specs);
+        return specs;
+    });
+}
+
+int enqueue_color_change(tbrm_resources* r, const tbrm_color_dir_light& removed, const tbrm_color_dir_light& added_light,
+                         const tbrm_world_params& world)
+{
+    return run_color_passes(r, world, [&](int c) {
+        std::vector<PassSpec> specs;
+        const tbrm_dir_light_params o = channel_light(removed, c), n = channel_light(added_light, c);
+        if (o.light_intensity != 0.0f || n.light_intensity != 0.0f) (void) change_light_specs(r, o, n, world, specs);
+        return specs;
+    });
 }
 
 } // namespace tbrm_host

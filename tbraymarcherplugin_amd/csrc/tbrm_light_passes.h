@@ -29,6 +29,7 @@ int ensure_sweep(tbrm_resources* r, size_t words, size_t words1 = 0, size_t chai
 int next_sweep_epoch(tbrm_resources* r, uint32_t& epoch, uint32_t launches = 1);
 float through_light_format(int lv_fmt, float v);
 void fill_chunk_stream(ChunkStream& s, const tbrm_light_pass& p, int lv_fmt);
+void rebind_light_channel(tbrm_resources* r, PassPlan& plan, void* light, const tbrm_light_pass& pa, const tbrm_light_pass* pr);
 int plan_pass_sliced(tbrm_resources* r, const PropParams& base, const tbrm_light_pass& pa, const tbrm_light_pass* pr, float b_added,
                      const tbrm_slab& slab, PassPlan& plan);
 SpanRange span_range(const PassPlan& plan, int sp);

@@ -744,6 +744,18 @@ int plan_pass(tbrm_resources* r, const PropParams& base, const tbrm_light_pass& 
     return TBRM_OK;
 }
 
+// A planned pass once more over another light channel of a colour handle: pa / pr are the planned passes with that channel's
+// intensities (same light directions: same geometry, tiles, taps and occlusion). What a plan holds of the light's intensity is
+// each stream's border and initial value; a sweep plan's occlusion is enqueued by then and its factors are read again, a
+// chunked-chain plan is a new pass to the occlusion buffers (they are labelled with the plan's serial).
+void rebind_light_channel(tbrm_resources* r, PassPlan& plan, void* light, const tbrm_light_pass& pa, const tbrm_light_pass* pr)
+{
+    plan.p.light = light;
+    fill_chunk_stream(plan.p.a, pa, r->lv_fmt);
+    if (pr) fill_chunk_stream(plan.p.r, *pr, r->lv_fmt);
+    if (!plan.sweep) plan.serial = ++r->plan_serial;
+}
+
 // The plane holding the propagated light of stream `si` (0: a, 1: r) BEFORE chunk `boundary` (boundary = n_chunks: after
 // the last one): chunk c reads the planes of parity c & 1 and writes the others.
 float* plan_plane(const tbrm_resources* r, int boundary, int si) { return r->d_plane[2 * si + (boundary & 1)] + kPlaneGuard; }

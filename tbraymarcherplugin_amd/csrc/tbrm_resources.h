@@ -4,6 +4,7 @@
 #pragma once
 
 #include "../../include/tbrm.h"
+#include "../../include/tbrm_color_lights.h"
 #include "tbrm_host_math.h"
 #include "tbrm_internal.h"
 
@@ -196,7 +197,11 @@ struct tbrm_resources {
 
     tbrm_windowing_params win{0.5f, 1.0f, 1, 1};
 
-    void* d_light = nullptr;
+    void* d_light = nullptr;       // the light volume; a colour handle's channel 0 (light_channel)
+    // colour handles (tbrm_resources_create_rgb, include/tbrm_color_lights.h): three mono-layout bricked volumes R, G, B in ONE
+    // allocation, light_bricked_bytes apart — every propagation kernel runs on a channel by its base pointer, unchanged
+    int light_channels = 1;
+    void* light_channel(int c) const { return (char*) res_light.alloc + (size_t) c * light_bricked_bytes; } // (not slab-resident)
     size_t light_bytes = 0;        // linear size (what download/upload exchange)
     size_t light_bricked_bytes = 0;
     size_t data_bricked_bytes = 0;
@@ -326,6 +331,12 @@ inline int clamp_int(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi 
 
 // ---- handle helpers (tbrm_api.cpp) ------------------------------------------------------------------------------------
 int bind(const tbrm_resources* r);
+int create_handle(const tbrm_resources_desc* desc, const tbrm_slab* owned, int light_channels, tbrm_resources** out);
+// colour handles refuse what has no RGB form (include/tbrm_color_lights.h "Not available"): TBRM_ERR_UNSUPPORTED, else TBRM_OK
+int refuse_color(const tbrm_resources* r, const char* what);
+// one channel of the light volume, dense and x fastest (tbrm_download_light_volume / tbrm_upload_light_volume: channel 0 of a mono handle)
+int download_light_channel(tbrm_resources* r, int channel, void* host_out, size_t n_bytes);
+int upload_light_channel(tbrm_resources* r, int channel, const void* host_in, size_t n_bytes);
 bool initialized(const tbrm_resources* r);
 VolumeDev data_view(const tbrm_resources* r);
 WindowDev window_dev(const tbrm_resources* r);
@@ -434,6 +445,10 @@ int enqueue_add_batch(tbrm_resources* r, const tbrm_dir_light_params* lights, in
                       int32_t* schedule, int32_t* n_entries);
 int enqueue_change(tbrm_resources* r, const tbrm_dir_light_params& removed, const tbrm_dir_light_params& added_light,
                    const tbrm_world_params& world);
+// coloured lights (include/tbrm_color_lights.h): the operator per live channel of a colour handle
+int enqueue_color_add(tbrm_resources* r, const tbrm_color_dir_light& light, bool added, const tbrm_world_params& world);
+int enqueue_color_change(tbrm_resources* r, const tbrm_color_dir_light& removed, const tbrm_color_dir_light& added_light,
+                         const tbrm_world_params& world);
 
 } // namespace tbrm_host
 
