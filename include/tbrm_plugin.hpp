@@ -17,6 +17,7 @@
 #include "tbrm.h"
 #include "tbrm_labels.h"
 #include "tbrm_color_lights.h"
+#include "tbrm_volume_region.h"
 
 #include <algorithm>
 #include <cmath>
@@ -310,6 +311,17 @@ public:
         tbrm_set_tf_lut(RaymarchResources.Handle, lut.data());
         bHasTF = true;
         bRequestedRecompute = true;
+    }
+
+    // A sub-box of the data volume (include/tbrm_volume_region.h; the reference can only set the whole asset again): dense, x
+    // fastest, in the asset's format. The light volume was propagated through the old voxels, so the next Tick runs
+    // ResetAllLights, as after SetVolumeAsset, and the octree is rebuilt before it is marched again.
+    bool UpdateVolumeRegion(const int32_t Origin[3], const int32_t Extent[3], const void* Voxels, size_t NumBytes)
+    {
+        if (!RaymarchResources.Handle || tbrm_update_volume_region(RaymarchResources.Handle, Origin, Extent, Voxels, NumBytes) != TBRM_OK) return false;
+        bRequestedRecompute = true;
+        bRequestedOctreeRebuild = true;
+        return true;
     }
 
     // Label overlay (include/tbrm_labels.h; no counterpart in the reference's actor): thin forwards to the C-ABI. Labels change

@@ -154,6 +154,14 @@ COLOR_LIGHT_SYMBOLS = [
 
 COLOR_LIGHTS_ABI_VERSION = 1  # TBRM_COLOR_LIGHTS_ABI_VERSION of include/tbrm_color_lights.h
 
+# every symbol include/tbrm_volume_region.h declares (data-volume region updates; tests/test_volume_region_abi.py checks the header against this list)
+VOLUME_REGION_SYMBOLS = [
+    "tbrm_volume_region_abi_version", "tbrm_update_volume_region", "tbrm_update_volume_region_device", "tbrm_download_volume_region",
+    "tbrm_volume_region_counters", "tbrm_volume_skipping_digest",
+]
+
+VOLUME_REGION_ABI_VERSION = 1  # TBRM_VOLUME_REGION_ABI_VERSION of include/tbrm_volume_region.h
+
 _lib = None
 
 
@@ -262,6 +270,15 @@ def load():
     lib.tbrm_change_color_dir_light.argtypes = [vp, P(ColorDirLight), P(ColorDirLight), P(WorldParams), P(C.c_int)]
     lib.tbrm_download_light_channel.argtypes = [vp, C.c_int, vp, C.c_size_t]
     lib.tbrm_upload_light_channel.argtypes = [vp, C.c_int, vp, C.c_size_t]
+    have = lib.tbrm_volume_region_abi_version() if hasattr(lib, "tbrm_volume_region_abi_version") else -1
+    if have != VOLUME_REGION_ABI_VERSION:
+        raise ImportError(f"{LIB_PATH} has volume-region ABI version {have}, this binding is written against {VOLUME_REGION_ABI_VERSION}: "
+                          "rebuild it (`python tbraymarcherplugin_amd/build.py --force`)")
+    lib.tbrm_update_volume_region.argtypes = [vp, P(C.c_int32 * 3), P(C.c_int32 * 3), vp, C.c_size_t]
+    lib.tbrm_update_volume_region_device.argtypes = [vp, P(C.c_int32 * 3), P(C.c_int32 * 3), vp, C.c_size_t]
+    lib.tbrm_download_volume_region.argtypes = [vp, P(C.c_int32 * 3), P(C.c_int32 * 3), vp, C.c_size_t]
+    lib.tbrm_volume_region_counters.argtypes = [vp, P(C.c_uint64 * 4)]
+    lib.tbrm_volume_skipping_digest.argtypes = [vp, P(C.c_uint64 * 4)]
     _lib = lib
     return lib
 
@@ -475,6 +492,42 @@ class Resources:
 
     def has_label_volume(self):
         return bool(self.lib.tbrm_has_label_volume(self.handle))
+
+    # data-volume region updates (include/tbrm_volume_region.h): boxes are [ez, ey, ex] in the handle's data format
+    def update_volume_region(self, origin, block):
+        """writes `block` ([ez, ey, ex], the volume's dtype) at voxel `origin` (x, y, z) of the uploaded data volume"""
+        block = np.ascontiguousarray(block)
+        assert DTYPE_FMT[block.dtype] == self.desc.data_format and block.ndim == 3
+        o = (C.c_int32 * 3)(*[int(v) for v in origin])
+        e = (C.c_int32 * 3)(block.shape[2], block.shape[1], block.shape[0])
+        check(self.lib.tbrm_update_volume_region(self.handle, C.byref(o), C.byref(e), block.ctypes.data, block.nbytes))
+
+    def update_volume_region_device(self, origin, extent, ptr, nbytes):
+        """the same from device memory: `extent` (ex, ey, ez) voxels, dense and x fastest, at address `ptr`"""
+        o = (C.c_int32 * 3)(*[int(v) for v in origin])
+        e = (C.c_int32 * 3)(*[int(v) for v in extent])
+        check(self.lib.tbrm_update_volume_region_device(self.handle, C.byref(o), C.byref(e), C.c_void_p(ptr), nbytes))
+
+    def download_volume_region(self, origin, extent):
+        """the box `extent` (ex, ey, ez) at voxel `origin` (x, y, z) of the data volume, as an [ez, ey, ex] array"""
+        o = (C.c_int32 * 3)(*[int(v) for v in origin])
+        e = (C.c_int32 * 3)(*[int(v) for v in extent])
+        out = np.empty((int(extent[2]), int(extent[1]), int(extent[0])), dtype=FMT_DTYPE[self.desc.data_format])
+        check(self.lib.tbrm_download_volume_region(self.handle, C.byref(o), C.byref(e), out.ctypes.data, out.nbytes))
+        return out
+
+    VOLUME_REGION_COUNTERS = ("updates", "voxels_written", "bricks_refreshed", "minmax_rebuilds")
+
+    def volume_region_counters(self):
+        out = (C.c_uint64 * 4)()
+        check(self.lib.tbrm_volume_region_counters(self.handle, C.byref(out)))
+        return {k: int(out[i]) for i, k in enumerate(self.VOLUME_REGION_COUNTERS)}
+
+    def skipping_digest(self):
+        """tbrm_volume_skipping_digest (a test hook): (bricks, empty bricks, hash of the value ranges, hash of the distance field)"""
+        out = (C.c_uint64 * 4)()
+        check(self.lib.tbrm_volume_skipping_digest(self.handle, C.byref(out)))
+        return tuple(int(v) for v in out)
 
     def is_initialized(self):
         return bool(self.lib.tbrm_resources_is_initialized(self.handle))

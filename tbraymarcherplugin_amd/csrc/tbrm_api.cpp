@@ -206,14 +206,21 @@ namespace tbrm_host {
 int ensure_skipping(tbrm_resources* r)
 {
     const int nb = r->bn[0] * r->bn[1] * r->bn[2];
-    if (!r->minmax_valid) {
+    if (!r->minmax_valid || !r->dirty_boxes.empty()) {
         // a brick's range covers its +1 apron: of a slab-resident volume the last resident layer has none (unless it is the
         // volume's last layer and the apron clamps onto it, or wraps onto a resident layer 0)
         const tbrm_resources::Residency& q = r->res_data;
         const bool clamp = r->desc.data_address_mode == TBRM_ADDRESS_CLAMP;
         const int bz1 = (q.hi == r->bn[2] && (clamp || q.lo == 0)) ? q.hi : q.hi - 1;
         BrickParams bp{data_view(r), clamp ? ADDR_CLAMP : ADDR_WRAP, r->bn[0], r->bn[1], r->bn[2], r->d_minmax, q.lo, bz1};
-        HIP_TRY(launch_brick_minmax(bp, r->stream));
+        // region updates since the ranges were last valid (tbrm_volume_region.h): only the bricks their boxes reach
+        if (r->minmax_valid)
+            if (int e = refresh_dirty_minmax(r, bp)) return e;
+        if (!r->minmax_valid) {
+            HIP_TRY(launch_brick_minmax(bp, r->stream));
+            ++r->region_counters[3];
+        }
+        r->dirty_boxes.clear();
         r->minmax_valid = true;
         r->empty_valid = false;
     }

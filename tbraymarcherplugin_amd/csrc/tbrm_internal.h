@@ -426,4 +426,21 @@ hipError_t launch_label_live(const LabelLiveParams& p, hipStream_t s);
 hipError_t launch_label_merge(const LabelMergeParams& p, int addr_mode, hipStream_t s);
 hipError_t launch_label_region(const LabelRegionParams& p, hipStream_t s);
 
+// data-volume region updates (tbrm_api_volume_region.cpp, tbrm_volume_kernels.hip)
+struct VolumeRegionParams {
+    const void* box;       // the sub-box [origin, origin + extent), dense, x fastest (written when to_bricks is 0)
+    void* bricked;         // the bricked volume (read when to_bricks is 0)
+    int origin[3], extent[3];
+    int bnx, bnxy;
+    int elem_bytes;
+    int to_bricks;         // 1: box -> bricked (voxels outside the box are left alone); 0: bricked -> box
+};
+// the bricks whose k_brick_minmax range a box can have changed: per axis [lo, hi] and, for i beyond that range, `last`
+struct BrickReach {
+    int lo[3], hi[3], last[3];
+    int n[3];              // bricks per axis: hi - lo + 1, + 1 when `last` is reached as well and lies outside [lo, hi]
+};
+hipError_t launch_volume_region(const VolumeRegionParams& p, hipStream_t s);
+hipError_t launch_brick_minmax_region(const BrickParams& p, const BrickReach& q, hipStream_t s);
+
 } // namespace tbrm

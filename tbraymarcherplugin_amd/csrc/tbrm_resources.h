@@ -318,6 +318,11 @@ struct tbrm_resources {
     uint32_t lab_alive[8]{};         // labels whose colour alpha is > 0
     bool lab_skip_valid = false;     // d_empty_lab / d_dist_lab hold the merge of the current label occupancy ...
     uint64_t lab_empty_gen = 0;      // ... with this empty_gen's d_empty
+
+    // data-volume region updates (tbrm_api_volume_region.cpp; include/tbrm_volume_region.h)
+    struct DirtyBox { int origin[3], extent[3]; };
+    std::vector<DirtyBox> dirty_boxes; // boxes written while minmax_valid held: ensure_skipping recomputes the bricks they reach
+    uint64_t region_counters[4]{};   // tbrm_volume_region_counters
 };
 
 
@@ -345,6 +350,9 @@ void fill_stream(PropStream& s, const tbrm_light_pass& p);
 int begin_timed(tbrm_resources* r, int kind);
 int end_timed(tbrm_resources* r, int kind);
 int ensure_skipping(tbrm_resources* r);
+// data-volume region updates (tbrm_api_volume_region.cpp): d_minmax of the bricks the pending dirty boxes reach, or — too many
+// boxes, or as many bricks as the volume has — minmax_valid dropped so that ensure_skipping rebuilds all of it
+int refresh_dirty_minmax(tbrm_resources* r, const BrickParams& whole);
 int raymarch_clip_mode(const float cc[3], const float cd[3]);
 // label overlay (tbrm_api_labels.cpp)
 int label_ray_params(tbrm_resources* r, RayParams& p); // the lit march's label step, when one is due (after the skipping metadata)

@@ -15,9 +15,8 @@ namespace tbrm {
 // Per brick b: min/max of every voxel a sample whose base tap lies in b can touch: [8b, 8b+8] per axis,
 // addressed like the raymarch sampler. NaN voxels poison the range to [-inf, +inf] (never skipped).
 template <int FMT, int MODE>
-__global__ __launch_bounds__(64) void k_brick_minmax(const BrickParams p)
+__device__ __forceinline__ void brick_minmax(const BrickParams& p, const int b)
 {
-    const int b = blockIdx.x;
     const int bx = b % p.bnx, by = (b / p.bnx) % p.bny, bz = b / (p.bnx * p.bny);
     if (bz < p.bz0 || bz >= p.bz1) { // slab-resident volumes: not held here
         if (threadIdx.x == 0) p.minmax[b] = make_float2(-__builtin_inff(), __builtin_inff());
@@ -47,20 +46,57 @@ __global__ __launch_bounds__(64) void k_brick_minmax(const BrickParams p)
     if (threadIdx.x == 0) p.minmax[b] = nan ? make_float2(-__builtin_inff(), __builtin_inff()) : make_float2(mn, mx);
 }
 
+template <int FMT, int MODE>
+__global__ __launch_bounds__(64) void k_brick_minmax(const BrickParams p)
+{
+    brick_minmax<FMT, MODE>(p, blockIdx.x);
+}
+
+// The same body over the bricks a region update can have changed the range of (tbrm_api_volume_region.cpp): per axis the bricks
+// [lo, hi] and, when `last` is set, the axis' last brick as well (wrap addressing: its +8 tap is texel 0).
+template <int FMT, int MODE>
+__global__ __launch_bounds__(64) void k_brick_minmax_region(const BrickParams p, const BrickReach q)
+{
+    int c[3], k = blockIdx.x;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const int i = k % q.n[a];
+        k /= q.n[a];
+        c[a] = i <= q.hi[a] - q.lo[a] ? q.lo[a] + i : q.last[a];
+    }
+    brick_minmax<FMT, MODE>(p, (c[2] * p.bny + c[1]) * p.bnx + c[0]);
+}
+
+#define TBRM_BM_DISPATCH(p)                                                                                \
+    do {                                                                                                   \
+        const bool clamp = (p).addr_mode == ADDR_CLAMP;                                                    \
+        switch ((p).data.fmt) {                                                                            \
+            case FMT_U8: if (clamp) TBRM_BM(FMT_U8, ADDR_CLAMP); else TBRM_BM(FMT_U8, ADDR_WRAP); break;   \
+            case FMT_U16: if (clamp) TBRM_BM(FMT_U16, ADDR_CLAMP); else TBRM_BM(FMT_U16, ADDR_WRAP); break; \
+            default: if (clamp) TBRM_BM(FMT_F32, ADDR_CLAMP); else TBRM_BM(FMT_F32, ADDR_WRAP); break;     \
+        }                                                                                                  \
+    } while (0)
+
 hipError_t launch_brick_minmax(const BrickParams& p, hipStream_t s)
 {
     const int n = p.bnx * p.bny * p.bnz;
     if (n == 0) return hipSuccess;
 #define TBRM_BM(F, M) hipLaunchKernelGGL((k_brick_minmax<F, M>), dim3(n), dim3(64), 0, s, p)
-    const bool clamp = p.addr_mode == ADDR_CLAMP;
-    switch (p.data.fmt) {
-        case FMT_U8: if (clamp) TBRM_BM(FMT_U8, ADDR_CLAMP); else TBRM_BM(FMT_U8, ADDR_WRAP); break;
-        case FMT_U16: if (clamp) TBRM_BM(FMT_U16, ADDR_CLAMP); else TBRM_BM(FMT_U16, ADDR_WRAP); break;
-        default: if (clamp) TBRM_BM(FMT_F32, ADDR_CLAMP); else TBRM_BM(FMT_F32, ADDR_WRAP); break;
-    }
+    TBRM_BM_DISPATCH(p);
 #undef TBRM_BM
     return hipGetLastError();
 }
+
+hipError_t launch_brick_minmax_region(const BrickParams& p, const BrickReach& q, hipStream_t s)
+{
+    const long n = (long) q.n[0] * q.n[1] * q.n[2];
+    if (n <= 0) return hipSuccess;
+#define TBRM_BM(F, M) hipLaunchKernelGGL((k_brick_minmax_region<F, M>), dim3((unsigned) n), dim3(64), 0, s, p, q)
+    TBRM_BM_DISPATCH(p);
+#undef TBRM_BM
+    return hipGetLastError();
+}
+#undef TBRM_BM_DISPATCH
 
 // A brick is empty when every value in [min,max] maps to corrected opacity 0: the TF position is monotone in
 // the value (width > 0), so it suffices that the part of [pos(min), pos(max)] that survives the cutoffs only
@@ -364,6 +400,78 @@ hipError_t launch_relayout(const RelayoutParams& p, hipStream_t s)
     if (p.elem_bytes == 1) hipLaunchKernelGGL(k_relayout<uint8_t>, dim3(n), dim3(256), 0, s, p);
     else if (p.elem_bytes == 2) hipLaunchKernelGGL(k_relayout<uint16_t>, dim3(n), dim3(256), 0, s, p);
     else hipLaunchKernelGGL(k_relayout<uint32_t>, dim3(n), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+// ---- data-volume region updates (tbrm_api_volume_region.cpp; include/tbrm_volume_region.h) --------------------------------------
+// A dense x-fastest sub-box <-> its place in the bricked volume. As k_relayout, one workgroup moves a run of up to 16 bricks along
+// x through LDS, here a run of the bricks the box touches: the box side goes row by row (consecutive lanes on consecutive voxels
+// of a box row), the bricked side in 16-byte pieces. Scatter (to_bricks): a piece that lies inside the box whole is one 16-byte
+// store from LDS — every piece of a brick the box covers, so such bricks are written as the contiguous 512-element runs they are;
+// a piece the box cuts is written voxel by voxel, and only the voxels inside the box, so the rest of a cut brick and the zero
+// padding of a ragged edge brick (never inside a box: the box lies inside the volume) are not touched. Gather: the run is read
+// whole with 16-byte loads and the rows hand out what lies inside the box.
+template <typename E>
+__global__ __launch_bounds__(256) void k_volume_region(const VolumeRegionParams p)
+{
+    __shared__ __attribute__((aligned(16))) E s_run[kRelayoutSeg * 512];
+    const int bx_lo = p.origin[0] >> 3, by_lo = p.origin[1] >> 3, bz_lo = p.origin[2] >> 3;
+    const int nbx = ((p.origin[0] + p.extent[0] - 1) >> 3) - bx_lo + 1, nby = ((p.origin[1] + p.extent[1] - 1) >> 3) - by_lo + 1;
+    const int segs = (nbx + kRelayoutSeg - 1) / kRelayoutSeg;
+    const int b = blockIdx.x;
+    const int seg = b % segs, by = by_lo + (b / segs) % nby, bz = bz_lo + b / (segs * nby);
+    const int bx0 = bx_lo + seg * kRelayoutSeg, nb = min(kRelayoutSeg, bx_lo + nbx - bx0);
+    E* bricked = (E*) p.bricked + ((size_t) bz * p.bnxy + (size_t) by * p.bnx + bx0) * 512;
+    E* box = (E*) p.box;
+    constexpr int V = 16 / (int) sizeof(E); // voxels per 16-byte access
+    const int run = nb * 512;
+    const int x_end = p.origin[0] + p.extent[0], y_end = p.origin[1] + p.extent[1], z_end = p.origin[2] + p.extent[2];
+    if (!p.to_bricks) { // bricked -> LDS
+        for (int i = threadIdx.x * V; i < run; i += 256 * V) *(uint4*) (s_run + i) = *(const uint4*) (bricked + i);
+        __syncthreads();
+    }
+    for (int i = threadIdx.x; i < 64 * 128; i += 256) { // row (y, z) of the run, voxel xl along it
+        const int row = i >> 7, xl = i & 127;
+        const int x = bx0 * 8 + xl, y = by * 8 + (row & 7), z = bz * 8 + (row >> 3);
+        if ((xl >> 3) >= nb) continue;
+        if (x < p.origin[0] || x >= x_end || y < p.origin[1] || y >= y_end || z < p.origin[2] || z >= z_end) continue;
+        const size_t li = ((size_t) (z - p.origin[2]) * p.extent[1] + (size_t) (y - p.origin[1])) * (size_t) p.extent[0] + (size_t) (x - p.origin[0]);
+        const int si = (xl >> 3) * 512 + (row << 3) + (xl & 7);
+        if (p.to_bricks) s_run[si] = box[li];
+        else box[li] = s_run[si];
+    }
+    if (p.to_bricks) { // LDS -> bricked
+        __syncthreads();
+        for (int i = threadIdx.x * V; i < run; i += 256 * V) { // a piece: V voxels of one brick, x fastest (whole brick rows, or half of one)
+            const int in_brick = i & 511;
+            const int x0 = (bx0 + (i >> 9)) * 8 + (in_brick & 7), y0 = by * 8 + ((in_brick >> 3) & 7), z = bz * 8 + (in_brick >> 6);
+            constexpr int XS = V < 8 ? V : 8, YS = V < 8 ? 1 : V / 8; // its extent along x and y
+            const bool z_in = z >= p.origin[2] && z < z_end;
+            if (z_in && x0 >= p.origin[0] && x0 + XS <= x_end && y0 >= p.origin[1] && y0 + YS <= y_end) {
+                *(uint4*) (bricked + i) = *(const uint4*) (s_run + i);
+                continue;
+            }
+            if (!z_in) continue;
+#pragma unroll
+            for (int v = 0; v < V; ++v) {
+                const int x = x0 + (v & (XS - 1)), y = y0 + v / XS;
+                if (x >= p.origin[0] && x < x_end && y >= p.origin[1] && y < y_end) bricked[i + v] = s_run[i + v];
+            }
+        }
+    }
+}
+
+hipError_t launch_volume_region(const VolumeRegionParams& p, hipStream_t s)
+{
+    long n = 1;
+    for (int c = 0; c < 3; ++c) {
+        if (p.extent[c] <= 0) return hipSuccess;
+        const int bricks = ((p.origin[c] + p.extent[c] - 1) >> 3) - (p.origin[c] >> 3) + 1;
+        n *= c == 0 ? (bricks + kRelayoutSeg - 1) / kRelayoutSeg : bricks;
+    }
+    if (p.elem_bytes == 1) hipLaunchKernelGGL(k_volume_region<uint8_t>, dim3((unsigned) n), dim3(256), 0, s, p);
+    else if (p.elem_bytes == 2) hipLaunchKernelGGL(k_volume_region<uint16_t>, dim3((unsigned) n), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(k_volume_region<uint32_t>, dim3((unsigned) n), dim3(256), 0, s, p);
     return hipGetLastError();
 }
 
