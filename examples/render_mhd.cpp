@@ -5,8 +5,10 @@
 //
 //   g++ -std=c++17 -O2 -I include examples/render_mhd.cpp -o render_mhd -L tbraymarcherplugin_amd/lib -ltbrm -lz
 //       (plus -Wl,-rpath,$PWD/tbraymarcherplugin_amd/lib -Wl,-rpath,/opt/rocm/lib to run it in place)
-//   ./render_mhd volume.mhd out.ppm [width height steps] [--light-color r,g,b]
+//   ./render_mhd volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]]
 //       --light-color: the key light's colour (components in [0, 1]) on an RGB light volume (include/tbrm_color_lights.h); the fill stays white
+//       --auto-window: the window comes from the data (ARaymarchVolume::AutoWindow, include/tbrm_volume_stats.h): the span between
+//                      the LOW and HIGH percentiles of the value histogram, 0.01,0.99 when not given
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -21,7 +23,16 @@ using namespace tbrm_plugin;
 int main(int argc, char** argv)
 {
     float key_color[3] = {1.0f, 1.0f, 1.0f};
-    bool colored = false;
+    bool colored = false, auto_window = false;
+    float auto_low = 0.01f, auto_high = 0.99f;
+    for (int i = 1; i < argc; ++i) // --auto-window[=LOW,HIGH] is one word
+        if (!std::strncmp(argv[i], "--auto-window", 13)) {
+            if (argv[i][13] == '=' ? std::sscanf(argv[i] + 14, "%f,%f", &auto_low, &auto_high) != 2 : argv[i][13] != 0) { argc = 0; break; }
+            auto_window = true;
+            for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
+            argc -= 1;
+            break;
+        }
     for (int i = 1; i + 1 < argc; ++i) // the option and its value leave the positional arguments
         if (!std::strcmp(argv[i], "--light-color")) {
             if (std::sscanf(argv[i + 1], "%f,%f,%f", &key_color[0], &key_color[1], &key_color[2]) != 3) { argc = 0; break; }
@@ -31,7 +42,7 @@ int main(int argc, char** argv)
             break;
         }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s volume.mhd out.ppm [width height steps] [--light-color r,g,b]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]]\n", argv[0]);
         return 2;
     }
     const int width = argc > 3 ? std::atoi(argv[3]) : 512, height = argc > 4 ? std::atoi(argv[4]) : 512;
@@ -49,6 +60,14 @@ int main(int argc, char** argv)
     // window the upper half of the value range (window units are the file's units: FVolumeInfo::NormalizeValue / Range)
     volume.SetWindowCenter(info.NormalizeValue(info.MinValue + 0.6f * (info.MaxValue - info.MinValue)));
     volume.SetWindowWidth(info.NormalizeRange(0.8f * (info.MaxValue - info.MinValue)));
+    if (auto_window) { // ... or the window the data proposes; before the lights are set up, so that the first Tick propagates them through it
+        if (!volume.AutoWindow(auto_low, auto_high)) {
+            std::fprintf(stderr, "auto window failed: %s\n", tbrm_last_error());
+            return 1;
+        }
+        std::printf("auto window %g .. %g percentile: center %g, width %g\n", auto_low, auto_high,
+                    volume.RaymarchResources.WindowingParameters.Center, volume.RaymarchResources.WindowingParameters.Width);
+    }
     volume.SetRaymarchSteps(steps);
 
     ARaymarchLight key, fill;

@@ -18,6 +18,7 @@
 #include "tbrm_labels.h"
 #include "tbrm_color_lights.h"
 #include "tbrm_volume_region.h"
+#include "tbrm_volume_stats.h"
 
 #include <algorithm>
 #include <cmath>
@@ -111,6 +112,7 @@ struct FBasicRaymarchRenderingResources {
     bool LightVolumeHalfResolution = false;
     FWindowingParameters WindowingParameters;
     int SizeX = 0, SizeY = 0, SizeZ = 0; // DataVolumeTextureRef->GetSizeX/Y/Z()
+    int DataFormat = TBRM_FMT_G8;        // DataVolumeTextureRef->GetPixelFormat(): what Handle was created with
 };
 using FRaymarchResources = FBasicRaymarchRenderingResources;
 
@@ -324,6 +326,40 @@ public:
         return true;
     }
 
+    // Volume statistics (include/tbrm_volume_stats.h; no counterpart in the reference): computed on the device, where the voxels are.
+    // The value histogram of the whole asset in NumBins (1 .. 4096) equal bins, in stored units: over the full code range for the
+    // UNORM formats, over [global min, global max] (tbrm_label_statistics) for float data.
+    bool ComputeHistogram(int NumBins, std::vector<uint64_t>& Out)
+    {
+        double Lo = 0.0, Hi = 0.0;
+        return HistogramWithRange(NumBins, Out, Lo, Hi);
+    }
+    // Per label 0 .. 255 (without a label volume: everything under label 0) the voxel count, sum, minimum and maximum.
+    bool GetLabelStatistics(std::vector<tbrm_label_stat>& Out)
+    {
+        Out.assign(256, tbrm_label_stat{});
+        return RaymarchResources.Handle && tbrm_label_statistics(RaymarchResources.Handle, nullptr, nullptr, Out.data()) == TBRM_OK;
+    }
+    // A window from the data instead of the default centre 0.5 / width 1: the span between the two percentiles of the value
+    // histogram (256 bins for UNORM8, 1024 for UNORM16 and float; tbrm_host_window_from_histogram has the rule), both cut-offs on.
+    // It goes through the setters, so the windowing change reaches the handle and requests the light recompute exactly as a
+    // user's slider does. Window units: normalised value for UNORM data, the value itself for float data.
+    bool AutoWindow(float LowPercentile = 0.01f, float HighPercentile = 0.99f)
+    {
+        std::vector<uint64_t> Counts;
+        double Lo = 0.0, Hi = 0.0;
+        if (!HistogramWithRange(RaymarchResources.DataFormat == TBRM_FMT_G8 ? 256 : 1024, Counts, Lo, Hi)) return false;
+        double LoEdge = Lo, HiEdge = Hi;
+        if (RaymarchResources.DataFormat != TBRM_FMT_R32_FLOAT) { LoEdge = 0.0; HiEdge = (Hi + 1.0) / Hi; } // bins of codes 0 .. max, in units of code / max
+        tbrm_windowing_params w{};
+        if (tbrm_host_window_from_histogram(Counts.data(), (int32_t) Counts.size(), LoEdge, HiEdge, LowPercentile, HighPercentile, &w) != TBRM_OK) return false;
+        SetWindowCenter(w.center);
+        SetWindowWidth(w.width);
+        SetLowCutoff(w.low_cutoff != 0);
+        SetHighCutoff(w.high_cutoff != 0);
+        return true;
+    }
+
     // Label overlay (include/tbrm_labels.h; no counterpart in the reference's actor): thin forwards to the C-ABI. Labels change
     // neither the illumination nor the skipping metadata of the light operators, so none of these requests a recompute; the
     // Intensity and Octree renderers ignore them.
@@ -497,6 +533,29 @@ public:
 private:
     std::map<ARaymarchLight*, FDirLightParameters> LightParametersMap;
     bool bHasTF = false;
+    // the histogram of ComputeHistogram and the value range [Lo, Hi] its bins cover (stored units)
+    bool HistogramWithRange(int NumBins, std::vector<uint64_t>& Out, double& Lo, double& Hi)
+    {
+        Out.clear();
+        if (!RaymarchResources.Handle || NumBins < 1 || NumBins > TBRM_HISTOGRAM_MAX_BINS) return false;
+        tbrm_histogram_desc d{};
+        d.n_bins = NumBins;
+        if (RaymarchResources.DataFormat == TBRM_FMT_R32_FLOAT) {
+            std::vector<tbrm_label_stat> Stats;
+            if (!GetLabelStatistics(Stats)) return false;
+            Lo = INFINITY; Hi = -INFINITY;
+            for (const tbrm_label_stat& s : Stats) { Lo = std::min(Lo, s.min); Hi = std::max(Hi, s.max); }
+            if (!std::isfinite(Lo) || !std::isfinite(Hi)) return false; // no finite voxel, or infinite ones: no range to bin
+            if (!(Lo < Hi)) Hi = (double) std::nextafter((float) Lo, INFINITY); // a constant volume: one value wide
+        } else { Lo = 0.0; Hi = RaymarchResources.DataFormat == TBRM_FMT_G8 ? 255.0 : 65535.0; }
+        d.lo = Lo;
+        d.hi = Hi;
+        Out.assign((size_t) NumBins, 0);
+        uint64_t Tally[4] = {0, 0, 0, 0};
+        if (tbrm_volume_histogram(RaymarchResources.Handle, &d, Out.data(), Tally) == TBRM_OK) return true;
+        Out.clear();
+        return false;
+    }
     bool ColoredHandle() const { return RaymarchResources.Handle && tbrm_resources_light_channels(RaymarchResources.Handle) == 3; }
 
     void InitializeRaymarchResources(int X, int Y, int Z, int Format) // :821-920
@@ -516,6 +575,7 @@ private:
             return;
         }
         RaymarchResources.SizeX = X; RaymarchResources.SizeY = Y; RaymarchResources.SizeZ = Z;
+        RaymarchResources.DataFormat = Format;
         ReservedLights = 0;
         ReserveForLights();
     }

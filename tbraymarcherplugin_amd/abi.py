@@ -162,6 +162,24 @@ VOLUME_REGION_SYMBOLS = [
 
 VOLUME_REGION_ABI_VERSION = 1  # TBRM_VOLUME_REGION_ABI_VERSION of include/tbrm_volume_region.h
 
+# every symbol include/tbrm_volume_stats.h declares (volume statistics; tests/test_volume_stats_abi.py checks the header against this list)
+VOLUME_STATS_SYMBOLS = [
+    "tbrm_volume_stats_abi_version", "tbrm_volume_histogram", "tbrm_volume_histogram_device", "tbrm_label_statistics",
+    "tbrm_host_window_from_histogram", "tbrm_volume_stats_counters",
+]
+
+VOLUME_STATS_ABI_VERSION = 1  # TBRM_VOLUME_STATS_ABI_VERSION of include/tbrm_volume_stats.h
+HISTOGRAM_MAX_BINS = 4096
+
+
+class HistogramDesc(C.Structure):  # tbrm_histogram_desc
+    _fields_ = [("origin", C.c_int32 * 3), ("extent", C.c_int32 * 3), ("n_bins", C.c_int32), ("use_label_mask", C.c_int32),
+                ("lo", C.c_double), ("hi", C.c_double), ("label_mask", C.c_uint32 * 8)]
+
+
+# tbrm_label_stat, as a numpy record
+LABEL_STAT_DTYPE = np.dtype([("count", np.uint64), ("nan_count", np.uint64), ("sum", np.float64), ("min", np.float64), ("max", np.float64)])
+
 _lib = None
 
 
@@ -279,6 +297,15 @@ def load():
     lib.tbrm_download_volume_region.argtypes = [vp, P(C.c_int32 * 3), P(C.c_int32 * 3), vp, C.c_size_t]
     lib.tbrm_volume_region_counters.argtypes = [vp, P(C.c_uint64 * 4)]
     lib.tbrm_volume_skipping_digest.argtypes = [vp, P(C.c_uint64 * 4)]
+    have = lib.tbrm_volume_stats_abi_version() if hasattr(lib, "tbrm_volume_stats_abi_version") else -1
+    if have != VOLUME_STATS_ABI_VERSION:
+        raise ImportError(f"{LIB_PATH} has volume-statistics ABI version {have}, this binding is written against {VOLUME_STATS_ABI_VERSION}: "
+                          "rebuild it (`python tbraymarcherplugin_amd/build.py --force`)")
+    lib.tbrm_volume_histogram.argtypes = [vp, P(HistogramDesc), vp, P(C.c_uint64 * 4)]
+    lib.tbrm_volume_histogram_device.argtypes = [vp, P(HistogramDesc), vp]
+    lib.tbrm_label_statistics.argtypes = [vp, P(C.c_int32 * 3), P(C.c_int32 * 3), vp]
+    lib.tbrm_host_window_from_histogram.argtypes = [vp, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, P(WindowingParams)]
+    lib.tbrm_volume_stats_counters.argtypes = [vp, P(C.c_uint64 * 4)]
     _lib = lib
     return lib
 
@@ -359,6 +386,16 @@ def color_curve_to_lut(keys):
 def make_default_tf_lut():
     out = np.empty((256, 4), dtype=np.float32)
     check(load().tbrm_make_default_tf_lut(out.ctypes.data))
+    return out
+
+
+def window_from_histogram(counts, lo_edge, hi_edge, p_low=0.01, p_high=0.99):
+    """tbrm_host_window_from_histogram: the percentile window of a histogram whose bins span [lo_edge, hi_edge) in the window's
+    units (include/tbrm_volume_stats.h has the rule). Host arithmetic: needs no device."""
+    counts = np.ascontiguousarray(counts, dtype=np.uint64)
+    out = WindowingParams()
+    check(load().tbrm_host_window_from_histogram(counts.ctypes.data, int(counts.size), float(lo_edge), float(hi_edge), float(p_low), float(p_high),
+                                                 C.byref(out)))
     return out
 
 
@@ -528,6 +565,53 @@ class Resources:
         out = (C.c_uint64 * 4)()
         check(self.lib.tbrm_volume_skipping_digest(self.handle, C.byref(out)))
         return tuple(int(v) for v in out)
+
+    # volume statistics (include/tbrm_volume_stats.h): stored units — codes for the UNORM formats, the float itself for float data
+    HISTOGRAM_TALLY = ("below", "above", "nan", "visited")
+
+    def histogram_desc(self, n_bins, lo, hi, origin=None, extent=None, labels=None):
+        """origin / extent (x, y, z): a box, both None: the whole volume; labels: the label values that count (None: no mask)"""
+        d = HistogramDesc()
+        if extent is not None:
+            d.origin[:] = [int(v) for v in (origin if origin is not None else (0, 0, 0))]
+            d.extent[:] = [int(v) for v in extent]
+        d.n_bins, d.lo, d.hi = int(n_bins), float(lo), float(hi)
+        if labels is not None:
+            d.use_label_mask = 1
+            for l in labels:
+                d.label_mask[int(l) >> 5] |= 1 << (int(l) & 31)
+        return d
+
+    def volume_histogram(self, n_bins, lo, hi, origin=None, extent=None, labels=None):
+        """(counts uint64[n_bins], {"below", "above", "nan", "visited"})"""
+        d = self.histogram_desc(n_bins, lo, hi, origin, extent, labels)
+        counts = np.zeros(max(int(n_bins), 1), dtype=np.uint64)
+        tally = (C.c_uint64 * 4)()
+        check(self.lib.tbrm_volume_histogram(self.handle, C.byref(d), counts.ctypes.data, C.byref(tally)))
+        return counts, {k: int(tally[i]) for i, k in enumerate(self.HISTOGRAM_TALLY)}
+
+    def volume_histogram_device(self, ptr, n_bins, lo, hi, origin=None, extent=None, labels=None):
+        """adds the bins and the four tallies to the n_bins + 4 uint32 words at device address `ptr`; returns once enqueued"""
+        d = self.histogram_desc(n_bins, lo, hi, origin, extent, labels)
+        check(self.lib.tbrm_volume_histogram_device(self.handle, C.byref(d), C.c_void_p(ptr)))
+
+    def label_statistics(self, origin=None, extent=None):
+        """a record array of 256 (LABEL_STAT_DTYPE): per label count, nan_count, sum, min, max over the box / the whole volume"""
+        out = np.zeros(256, dtype=LABEL_STAT_DTYPE)
+        if extent is None:
+            check(self.lib.tbrm_label_statistics(self.handle, None, None, out.ctypes.data))
+        else:
+            o = (C.c_int32 * 3)(*[int(v) for v in (origin if origin is not None else (0, 0, 0))])
+            e = (C.c_int32 * 3)(*[int(v) for v in extent])
+            check(self.lib.tbrm_label_statistics(self.handle, C.byref(o), C.byref(e), out.ctypes.data))
+        return out
+
+    VOLUME_STATS_COUNTERS = ("histograms", "label_statistics", "whole_bricks", "cut_bricks")
+
+    def volume_stats_counters(self):
+        out = (C.c_uint64 * 4)()
+        check(self.lib.tbrm_volume_stats_counters(self.handle, C.byref(out)))
+        return {k: int(out[i]) for i, k in enumerate(self.VOLUME_STATS_COUNTERS)}
 
     def is_initialized(self):
         return bool(self.lib.tbrm_resources_is_initialized(self.handle))

@@ -381,6 +381,8 @@ int reserve_resources(tbrm_resources* r, int n_lights, unsigned flags)
         if (first < ((size_t) 1 << 32))
             if (int e = ensure_sweep(r, std::max<size_t>(first, 1), words, (size_t) tiles)) return e;
     }
+    if (eager && !r->resident) // (tbrm_volume_stats.h: a reserved handle's statistics calls allocate nothing; slab-resident handles refuse them)
+        if (int e = ensure_stats_scratch(r, false)) return e;
     // ordering events and block lists for n_lights lights' passes
     const size_t want_events = (size_t) 16 * n_lights + 32;
     while (r->event_pool.size() < want_events) {

@@ -364,6 +364,8 @@ enum Tunable : int {
     TUNE_RAY_XCD_ROWS,       // k_raymarch_lit: rows of pixel blocks per band dealt to one XCD (0: blocks in launch order, i.e. round-robin)
     TUNE_RAY_LABELS,         // 1: the lit march takes the label step whenever a label volume is attached, even when no label present in
                              // it has a colour alpha > 0 (a test hook: the same frame by the other kernel); 0: only when one does
+    TUNE_STATS_GROUPS,       // > 0: the statistics kernels (tbrm_stats_kernels.hip) launch at most this many workgroups, so that a wave
+                             // takes many bricks of even a small volume (a test hook and an A/B switch); 0: sized to the device
     TUNE_COUNT
 };
 int tune(Tunable t);
@@ -442,5 +444,27 @@ struct BrickReach {
 };
 hipError_t launch_volume_region(const VolumeRegionParams& p, hipStream_t s);
 hipError_t launch_brick_minmax_region(const BrickParams& p, const BrickReach& q, hipStream_t s);
+
+// volume statistics (tbrm_api_volume_stats.cpp, tbrm_stats_kernels.hip; include/tbrm_volume_stats.h)
+constexpr int kStatsMaxBins = 4096;
+constexpr int kStatsLabelWords = 256 * 6; // the label records: count, nan, ~min key, max key (256 uint32 each), then 256 8-byte sums
+struct StatsParams {
+    const void* data;      // bricked data volume
+    const uint8_t* labels; // bricked label volume on the same grid (null: none)
+    int fmt;
+    int bnx, bnxy;
+    int origin[3], end[3]; // the box [origin, end), inside the volume
+    int b0[3], nb[3];      // the bricks it touches: nb[c] from b0[c] on
+    // histogram: the binning rule of tbrm_volume_stats.h
+    uint32_t n_bins;
+    uint32_t lo_code, hi_code;
+    uint32_t div_mul, div_shift; // floor(n / (hi_code - lo_code + 1)) = mulhi(n, div_mul) >> div_shift for n < 2^28 (stats_divisor)
+    float lo_f, hi_f, scale;
+    uint32_t copies;       // LDS copies of the histogram per workgroup (a power of two, copies * n_bins <= kStatsMaxBins)
+    uint32_t mask[8];      // MASKED: the labels that count
+    uint32_t* out;         // histogram: n_bins + 4 words, added to; label statistics: kStatsLabelWords words, zeroed, added to
+};
+hipError_t launch_volume_histogram(const StatsParams& p, bool masked, int grid, hipStream_t s);
+hipError_t launch_label_statistics(const StatsParams& p, int grid, hipStream_t s);
 
 } // namespace tbrm

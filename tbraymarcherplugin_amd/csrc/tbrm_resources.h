@@ -323,6 +323,11 @@ struct tbrm_resources {
     struct DirtyBox { int origin[3], extent[3]; };
     std::vector<DirtyBox> dirty_boxes; // boxes written while minmax_valid held: ensure_skipping recomputes the bricks they reach
     uint64_t region_counters[4]{};   // tbrm_volume_region_counters
+
+    // volume statistics (tbrm_api_volume_stats.cpp; include/tbrm_volume_stats.h)
+    uint32_t* d_stats = nullptr;       // the scratch: histogram bins and tallies, then the 256 label records (ensure_stats_scratch)
+    std::vector<uint32_t> stats_host;  // ... and where the host forms read it back to
+    uint64_t stats_counters[4]{};      // tbrm_volume_stats_counters
 };
 
 
@@ -354,6 +359,8 @@ int ensure_skipping(tbrm_resources* r);
 // boxes, or as many bricks as the volume has — minmax_valid dropped so that ensure_skipping rebuilds all of it
 int refresh_dirty_minmax(tbrm_resources* r, const BrickParams& whole);
 int raymarch_clip_mode(const float cc[3], const float cd[3]);
+// volume statistics (tbrm_api_volume_stats.cpp): the scratch of the statistics calls, taken once (counted: tbrm_path_counters [12])
+int ensure_stats_scratch(tbrm_resources* r, bool counted = true);
 // label overlay (tbrm_api_labels.cpp)
 int label_ray_params(tbrm_resources* r, RayParams& p); // the lit march's label step, when one is due (after the skipping metadata)
 void release_labels(tbrm_resources* r);                // (the stream must be idle)
