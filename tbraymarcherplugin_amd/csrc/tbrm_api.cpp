@@ -275,6 +275,30 @@ int refuse_color(const tbrm_resources* r, const char* what)
 // the mono entry points on a colour handle (include/tbrm_color_lights.h)
 static tbrm_color_dir_light white(const tbrm_dir_light_params& l) { return tbrm_color_dir_light{l, {1.0f, 1.0f, 1.0f}, 0}; }
 
+// A light operator between the handle's timing events (tbrm_last_gpu_time_ms kind 0). end_timed runs after a failed enqueue too:
+// the events then bracket whatever was enqueued. The first error is the call's.
+template <class Enqueue> static int timed_light_op(tbrm_resources* r, Enqueue&& enqueue)
+{
+    if (int e = begin_timed(r, 0)) return e;
+    const int e = enqueue();
+    const int e2 = end_timed(r, 0);
+    return e ? e : e2;
+}
+
+// the selftests that count on the device: a zeroed counter handed to `launch`, read back
+template <class Launch> static int count_mismatches(Launch&& launch, uint64_t* out_mismatches)
+{
+    DeviceScratch scratch;
+    if (int e = scratch.make(sizeof(unsigned long long))) return e;
+    unsigned long long* const d = (unsigned long long*) scratch.p;
+    HIP_TRY(hipMemset(d, 0, sizeof(unsigned long long)));
+    HIP_TRY(launch(d));
+    unsigned long long bad = 0;
+    HIP_TRY(hipMemcpy(&bad, d, sizeof(bad), hipMemcpyDeviceToHost));
+    *out_mismatches = bad;
+    return TBRM_OK;
+}
+
 static int light_channel_args(const tbrm_resources* r, int channel, const void* host, size_t n_bytes)
 {
     if (!r || !host) return fail(TBRM_ERR_INVALID_ARG, "null argument");
@@ -288,14 +312,11 @@ int download_light_channel(tbrm_resources* r, int channel, void* host_out, size_
 {
     if (int e = light_channel_args(r, channel, host_out, n_bytes)) return e;
     if (int e = bind(r)) return e;
-    void* staging = nullptr;
-    HIP_TRY(hipMalloc(&staging, n_bytes));
-    const int dims[3] = {r->lv_dims[0], r->lv_dims[1], r->lv_dims[2]};
-    hipError_t e1 = launch_relayout(relayout_params(r->light_channel(channel), staging, dims, r->lbn, r->lv_fmt == FMT_U8 ? 1 : 4, false), r->stream);
-    if (e1 == hipSuccess) e1 = hipMemcpyAsync(host_out, staging, n_bytes, hipMemcpyDeviceToHost, r->stream);
-    if (e1 == hipSuccess) e1 = hipStreamSynchronize(r->stream);
-    (void) hipFree(staging);
-    HIP_TRY(e1);
+    DeviceScratch staging;
+    if (int e = staging.make(n_bytes)) return e;
+    HIP_TRY(launch_relayout(relayout_params(r->light_channel(channel), staging.p, r->lv_dims, r->lbn, r->light_elem(), false), r->stream));
+    HIP_TRY(hipMemcpyAsync(host_out, staging.p, n_bytes, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
     return sweep_failed(r); // (the slices of a light volume a failed sweep left undefined are not handed out as good)
 }
 
@@ -303,14 +324,11 @@ int upload_light_channel(tbrm_resources* r, int channel, const void* host_in, si
 {
     if (int e = light_channel_args(r, channel, host_in, n_bytes)) return e;
     if (int e = bind(r)) return e;
-    void* staging = nullptr;
-    HIP_TRY(hipMalloc(&staging, n_bytes));
-    const int dims[3] = {r->lv_dims[0], r->lv_dims[1], r->lv_dims[2]};
-    hipError_t e1 = hipMemcpyAsync(staging, host_in, n_bytes, hipMemcpyHostToDevice, r->stream);
-    if (e1 == hipSuccess) e1 = launch_relayout(relayout_params(staging, r->light_channel(channel), dims, r->lbn, r->lv_fmt == FMT_U8 ? 1 : 4, true), r->stream);
-    if (e1 == hipSuccess) e1 = hipStreamSynchronize(r->stream);
-    (void) hipFree(staging);
-    HIP_TRY(e1);
+    DeviceScratch staging;
+    if (int e = staging.make(n_bytes)) return e;
+    HIP_TRY(hipMemcpyAsync(staging.p, host_in, n_bytes, hipMemcpyHostToDevice, r->stream));
+    HIP_TRY(launch_relayout(relayout_params(staging.p, r->light_channel(channel), r->lv_dims, r->lbn, r->light_elem(), true), r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
     sweep_failure_cleared(r); // (the light volume is defined again)
     return TBRM_OK;
 }
@@ -366,7 +384,7 @@ static int create_impl(const tbrm_resources_desc* desc, const tbrm_slab* owned, 
     r->lv_dims[2] = desc->light_volume_half_resolution ? (desc->dim_z + 1) / 2 : desc->dim_z;
     r->lv_fmt = desc->light_volume_32bit ? FMT_F32 : FMT_U8;
     r->data_bytes = (size_t) desc->dim_x * desc->dim_y * desc->dim_z * format_bytes(desc->data_format);
-    const size_t lv_elem = desc->light_volume_32bit ? 4 : 1;
+    const size_t lv_elem = r->light_elem();
     r->light_bytes = (size_t) r->lv_dims[0] * r->lv_dims[1] * r->lv_dims[2] * lv_elem;
     for (int c = 0; c < 3; ++c) {
         const int d = c == 0 ? desc->dim_x : (c == 1 ? desc->dim_y : desc->dim_z);
@@ -437,18 +455,17 @@ static int create_impl(const tbrm_resources_desc* desc, const tbrm_slab* owned, 
     }
     {
         tbrm_resources::Residency& q = r->res_data;
-        const size_t bytes = (size_t) (q.hi - q.lo + (q.wrap_src >= 0 ? 1 : 0)) * q.layer_bytes;
-        CREATE_TRY(hipMalloc(&q.alloc, bytes));
+        CREATE_TRY(hipMalloc(&q.alloc, q.bytes()));
         r->d_data = (char*) q.alloc - (size_t) q.lo * q.layer_bytes;
         // a slab-resident handle is filled layer by layer (tbrm_upload_volume_slices): what has not arrived yet reads as 0,
         // not as whatever the allocation held
-        if (r->resident) CREATE_TRY(hipMemsetAsync(q.alloc, 0, bytes, r->stream));
+        if (r->resident) CREATE_TRY(hipMemsetAsync(q.alloc, 0, q.bytes(), r->stream));
     }
     CREATE_TRY(hipMalloc((void**) &r->d_tf, 256 * sizeof(float4)));
     {
         tbrm_resources::Residency& q = r->res_light;
         // (a colour handle: its channels one behind the other, each a whole mono volume — light_bricked_bytes)
-        CREATE_TRY(hipMalloc(&q.alloc, (size_t) (q.hi - q.lo + (q.wrap_src >= 0 ? 1 : 0)) * q.layer_bytes * (size_t) r->light_channels));
+        CREATE_TRY(hipMalloc(&q.alloc, q.bytes() * (size_t) r->light_channels));
         r->d_light = (char*) q.alloc - (size_t) q.lo * q.layer_bytes;
     }
     // XYZReadWriteBuffers: 4 buffers per axis in the light volume's format (RaymarchVolume.cpp:864-866,:889-891)
@@ -483,7 +500,7 @@ static int create_impl(const tbrm_resources_desc* desc, const tbrm_slab* owned, 
     for (int k = 0; k < 2; ++k)
         for (int e = 0; e < 2; ++e) CREATE_TRY(hipEventCreate(&r->ev[k][e]));
     // the light volume render target starts cleared
-    CREATE_TRY(hipMemsetAsync(r->res_light.alloc, 0, (size_t) (r->res_light.hi - r->res_light.lo + (r->res_light.wrap_src >= 0 ? 1 : 0)) * r->res_light.layer_bytes * (size_t) r->light_channels, r->stream));
+    CREATE_TRY(hipMemsetAsync(r->res_light.alloc, 0, r->res_light.bytes() * (size_t) r->light_channels, r->stream));
 #undef CREATE_TRY
     *out = r;
     return TBRM_OK;
@@ -553,18 +570,12 @@ int tbrm_upload_volume(tbrm_resources* r, const void* host_voxels, size_t n_byte
     if (n_bytes != r->data_bytes) return fail(TBRM_ERR_INVALID_ARG, "volume is %zu bytes, expected %zu", n_bytes, r->data_bytes);
     if (int e = bind(r)) return e;
     quiesce_occ_stream(r); // (nothing on the second stream may still be reading the volume)
-    void* staging = nullptr; // linear copy in HBM, re-laid out into bricks by the GPU
-    HIP_TRY(hipMalloc(&staging, n_bytes));
-    const int dims[3] = {r->desc.dim_x, r->desc.dim_y, r->desc.dim_z};
-    hipError_t e1 = hipMemcpyAsync(staging, host_voxels, n_bytes, hipMemcpyHostToDevice, r->stream);
-    if (e1 == hipSuccess) e1 = launch_relayout(relayout_params(staging, r->d_data, dims, r->dbn, format_bytes(r->desc.data_format), true), r->stream);
-    if (e1 == hipSuccess) e1 = hipStreamSynchronize(r->stream); // the caller may free its buffer on return
-    (void) hipFree(staging);
-    HIP_TRY(e1);
-    r->has_volume = true;
-    r->octree_valid = false;
-    r->minmax_valid = false;
-    ++r->data_gen;
+    DeviceScratch staging; // linear copy in HBM, re-laid out into bricks by the GPU
+    if (int e = staging.make(n_bytes)) return e;
+    HIP_TRY(hipMemcpyAsync(staging.p, host_voxels, n_bytes, hipMemcpyHostToDevice, r->stream));
+    HIP_TRY(launch_relayout(relayout_params(staging.p, r->d_data, r->data_dims(), r->dbn, format_bytes(r->desc.data_format), true), r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream)); // the caller may free its buffer on return
+    r->volume_rewritten();
     return TBRM_OK;
 }
 
@@ -575,13 +586,9 @@ int tbrm_upload_volume_device(tbrm_resources* r, const void* device_voxels, size
     if (n_bytes != r->data_bytes) return fail(TBRM_ERR_INVALID_ARG, "volume is %zu bytes, expected %zu", n_bytes, r->data_bytes);
     if (int e = bind(r)) return e;
     quiesce_occ_stream(r);
-    const int dims[3] = {r->desc.dim_x, r->desc.dim_y, r->desc.dim_z};
-    HIP_TRY(launch_relayout(relayout_params(device_voxels, r->d_data, dims, r->dbn, format_bytes(r->desc.data_format), true), r->stream));
+    HIP_TRY(launch_relayout(relayout_params(device_voxels, r->d_data, r->data_dims(), r->dbn, format_bytes(r->desc.data_format), true), r->stream));
     HIP_TRY(hipStreamSynchronize(r->stream));
-    r->has_volume = true;
-    r->octree_valid = false;
-    r->minmax_valid = false;
-    ++r->data_gen;
+    r->volume_rewritten();
     return TBRM_OK;
 }
 
@@ -639,11 +646,9 @@ int tbrm_add_dir_light(tbrm_resources* r, const tbrm_dir_light_params* light, in
     if (!initialized(r)) return fail(TBRM_ERR_NOT_INITIALIZED, "resources have no volume or transfer function"); // :39-45
     if (light_added) *light_added = 1;
     if (int e = bind(r)) return e;
-    if (int e = begin_timed(r, 0)) return e;
-    // (a colour handle: the light is white — include/tbrm_color_lights.h)
-    const int e = r->light_channels == 1 ? enqueue_add(r, *light, added != 0, *world) : enqueue_color_add(r, white(*light), added != 0, *world);
-    const int e2 = end_timed(r, 0); // also after a failure: the events then bracket whatever was enqueued
-    return e ? e : e2;
+    return timed_light_op(r, [&] { // (a colour handle: the light is white — include/tbrm_color_lights.h)
+        return r->light_channels == 1 ? enqueue_add(r, *light, added != 0, *world) : enqueue_color_add(r, white(*light), added != 0, *world);
+    });
 }
 
 int tbrm_add_dir_lights(tbrm_resources* r, const tbrm_dir_light_params* lights, int32_t n_lights, int added, const tbrm_world_params* world,
@@ -655,10 +660,7 @@ int tbrm_add_dir_lights(tbrm_resources* r, const tbrm_dir_light_params* lights, 
     if (!r || !world || (n_lights > 0 && !lights) || n_lights < 0) return fail(TBRM_ERR_INVALID_ARG, "null argument");
     if (!initialized(r)) return fail(TBRM_ERR_NOT_INITIALIZED, "resources have no volume or transfer function");
     if (int e = bind(r)) return e;
-    if (int e = begin_timed(r, 0)) return e;
-    const int e = enqueue_add_batch(r, lights, n_lights, added != 0, *world, schedule, n_entries);
-    const int e2 = end_timed(r, 0);
-    return e ? e : e2;
+    return timed_light_op(r, [&] { return enqueue_add_batch(r, lights, n_lights, added != 0, *world, schedule, n_entries); });
 }
 
 int tbrm_change_dir_light(tbrm_resources* r, const tbrm_dir_light_params* old_light, const tbrm_dir_light_params* new_light,
@@ -671,11 +673,10 @@ int tbrm_change_dir_light(tbrm_resources* r, const tbrm_dir_light_params* old_li
     if (!initialized(r)) return fail(TBRM_ERR_NOT_INITIALIZED, "resources have no volume or transfer function"); // :74-80
     if (light_added) *light_added = 1;
     if (int e = bind(r)) return e;
-    if (int e = begin_timed(r, 0)) return e;
-    const int e = r->light_channels == 1 ? enqueue_change(r, *old_light, *new_light, *world)
-                                         : enqueue_color_change(r, white(*old_light), white(*new_light), *world);
-    const int e2 = end_timed(r, 0);
-    return e ? e : e2;
+    return timed_light_op(r, [&] {
+        return r->light_channels == 1 ? enqueue_change(r, *old_light, *new_light, *world)
+                                      : enqueue_color_change(r, white(*old_light), white(*new_light), *world);
+    });
 }
 
 int tbrm_clear_light_volume(tbrm_resources* r, float clear_value)
@@ -686,7 +687,7 @@ int tbrm_clear_light_volume(tbrm_resources* r, float clear_value)
     sweep_failure_cleared(r); // (a sweep that failed left the light volume undefined: this call defines it again)
     if (int e = begin_timed(r, 0)) return e;
     const tbrm_resources::Residency& q = r->res_light; // (all layers of an ordinary handle); padding voxels are never sampled
-    const size_t n = (size_t) r->lbn[0] * r->lbn[1] * 512 * (size_t) (q.hi - q.lo + (q.wrap_src >= 0 ? 1 : 0)) * (size_t) r->light_channels;
+    const size_t n = (size_t) r->lbn[0] * r->lbn[1] * 512 * (size_t) q.layers() * (size_t) r->light_channels;
     HIP_TRY(launch_fill(q.alloc, r->lv_fmt, n, clear_value, r->stream));
     return end_timed(r, 0);
 }
@@ -721,13 +722,12 @@ int tbrm_selftest_unorm_decode(int device, float* out_u8_256, float* out_u16_655
 {
     if (!out_u8_256 || !out_u16_65536) return fail(TBRM_ERR_INVALID_ARG, "null argument");
     HIP_TRY(hipSetDevice(device));
-    float* d = nullptr;
-    HIP_TRY(hipMalloc((void**) &d, (256 + 65536) * sizeof(float)));
-    hipError_t e = launch_selftest_decode(d, d + 256, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(out_u8_256, d, 256 * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(out_u16_65536, d + 256, 65536 * sizeof(float), hipMemcpyDeviceToHost);
-    (void) hipFree(d);
-    HIP_TRY(e);
+    DeviceScratch scratch;
+    if (int e = scratch.make((256 + 65536) * sizeof(float))) return e;
+    float* const d = (float*) scratch.p;
+    HIP_TRY(launch_selftest_decode(d, d + 256, nullptr));
+    HIP_TRY(hipMemcpy(out_u8_256, d, 256 * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_u16_65536, d + 256, 65536 * sizeof(float), hipMemcpyDeviceToHost));
     return TBRM_OK;
 }
 
@@ -736,13 +736,12 @@ int tbrm_selftest_unorm8_roundtrip(int device, const float* in, size_t n, float*
     if (!in || !out) return fail(TBRM_ERR_INVALID_ARG, "null argument");
     if (n == 0) return TBRM_OK;
     HIP_TRY(hipSetDevice(device));
-    float* d = nullptr;
-    HIP_TRY(hipMalloc((void**) &d, 2 * n * sizeof(float)));
-    hipError_t e = hipMemcpy(d, in, n * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = launch_selftest_roundtrip(d, d + n, n, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(out, d + n, n * sizeof(float), hipMemcpyDeviceToHost);
-    (void) hipFree(d);
-    HIP_TRY(e);
+    DeviceScratch scratch;
+    if (int e = scratch.make(2 * n * sizeof(float))) return e;
+    float* const d = (float*) scratch.p;
+    HIP_TRY(hipMemcpy(d, in, n * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(launch_selftest_roundtrip(d, d + n, n, nullptr));
+    HIP_TRY(hipMemcpy(out, d + n, n * sizeof(float), hipMemcpyDeviceToHost));
     return TBRM_OK;
 }
 
@@ -754,16 +753,7 @@ int tbrm_selftest_window_division(int device, float center, float width, uint64_
     if (out_fast_path) *out_fast_path = w.fast_div;
     *out_mismatches = 0;
     if (!w.fast_div) return TBRM_OK; // (the kernels divide for this window: nothing to compare)
-    unsigned long long* d = nullptr;
-    HIP_TRY(hipMalloc((void**) &d, sizeof(unsigned long long)));
-    hipError_t e = hipMemset(d, 0, sizeof(unsigned long long));
-    if (e == hipSuccess) e = launch_selftest_window_division(w, d, nullptr);
-    unsigned long long bad = 0;
-    if (e == hipSuccess) e = hipMemcpy(&bad, d, sizeof(bad), hipMemcpyDeviceToHost);
-    (void) hipFree(d);
-    HIP_TRY(e);
-    *out_mismatches = bad;
-    return TBRM_OK;
+    return count_mismatches([&](unsigned long long* d) { return launch_selftest_window_division(w, d, nullptr); }, out_mismatches);
 }
 
 int tbrm_selftest_opacity_correction(int device, float step0, float step1, uint64_t* out_mismatches)
@@ -771,16 +761,7 @@ int tbrm_selftest_opacity_correction(int device, float step0, float step1, uint6
     if (!out_mismatches) return fail(TBRM_ERR_INVALID_ARG, "null argument");
     if (!(step0 >= 0.0f) || !(step1 >= 0.0f) || std::isinf(step0) || std::isinf(step1)) return fail(TBRM_ERR_INVALID_ARG, "the short form is used for finite step sizes >= 0 only");
     HIP_TRY(hipSetDevice(device));
-    unsigned long long* d = nullptr;
-    HIP_TRY(hipMalloc((void**) &d, sizeof(unsigned long long)));
-    hipError_t e = hipMemset(d, 0, sizeof(unsigned long long));
-    if (e == hipSuccess) e = launch_selftest_opacity_correction(step0, step1, d, nullptr);
-    unsigned long long bad = 0;
-    if (e == hipSuccess) e = hipMemcpy(&bad, d, sizeof(bad), hipMemcpyDeviceToHost);
-    (void) hipFree(d);
-    HIP_TRY(e);
-    *out_mismatches = bad;
-    return TBRM_OK;
+    return count_mismatches([&](unsigned long long* d) { return launch_selftest_opacity_correction(step0, step1, d, nullptr); }, out_mismatches);
 }
 
 int tbrm_launch_counters(const tbrm_resources* r, uint64_t out[3])

@@ -170,14 +170,11 @@ int tbrm_upload_label_volume(tbrm_resources* r, const uint8_t* host_labels, size
         default_label_colors(r->lab_colors);
         if (int e2 = put_colors(r, r->lab_colors)) { release_labels(r); return e2; }
     }
-    void* staging = nullptr; // linear copy in HBM, re-laid out into bricks by the GPU (k_relayout, 1-byte elements)
-    HIP_TRY(hipMalloc(&staging, n_bytes));
-    const int dims[3] = {r->desc.dim_x, r->desc.dim_y, r->desc.dim_z};
-    hipError_t e1 = hipMemcpyAsync(staging, host_labels, n_bytes, hipMemcpyHostToDevice, r->stream);
-    if (e1 == hipSuccess) e1 = launch_relayout(relayout_params(staging, r->d_labels, dims, r->dbn, 1, true), r->stream);
-    if (e1 == hipSuccess) e1 = hipStreamSynchronize(r->stream); // the caller may free its buffer on return
-    (void) hipFree(staging);
-    HIP_TRY(e1);
+    DeviceScratch staging; // linear copy in HBM, re-laid out into bricks by the GPU (k_relayout, 1-byte elements)
+    if (int e = staging.make(n_bytes)) return e;
+    HIP_TRY(hipMemcpyAsync(staging.p, host_labels, n_bytes, hipMemcpyHostToDevice, r->stream));
+    HIP_TRY(launch_relayout(relayout_params(staging.p, r->d_labels, r->data_dims(), r->dbn, 1, true), r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream)); // the caller may free its buffer on return
     const int b0[3] = {0, 0, 0}, b1[3] = {r->dbn[0], r->dbn[1], r->dbn[2]};
     if (int e = brick_masks(r, b0, b1)) return e;
     return refresh_live(r);
@@ -187,7 +184,7 @@ int tbrm_update_label_region(tbrm_resources* r, const int32_t origin[3], const i
 {
     if (!r || !origin || !extent || !host_labels) return fail(TBRM_ERR_INVALID_ARG, "null argument");
     if (!r->d_labels) return fail(TBRM_ERR_NOT_INITIALIZED, "no label volume: upload one with tbrm_upload_label_volume");
-    const int dims[3] = {r->desc.dim_x, r->desc.dim_y, r->desc.dim_z};
+    const tbrm_resources::Dims dims = r->data_dims();
     size_t n = 1;
     for (int c = 0; c < 3; ++c) {
         if (origin[c] < 0 || extent[c] <= 0 || extent[c] > dims[c] - origin[c])
@@ -196,19 +193,17 @@ int tbrm_update_label_region(tbrm_resources* r, const int32_t origin[3], const i
     }
     if (n_bytes != n) return fail(TBRM_ERR_INVALID_ARG, "region is %zu bytes, expected %zu", n_bytes, n);
     if (int e = bind(r)) return e;
-    void* staging = nullptr;
-    HIP_TRY(hipMalloc(&staging, n_bytes));
+    DeviceScratch staging;
+    if (int e = staging.make(n_bytes)) return e;
     LabelRegionParams rp{};
-    rp.src = (const uint8_t*) staging;
+    rp.src = (const uint8_t*) staging.p;
     rp.dst = r->d_labels;
     for (int c = 0; c < 3; ++c) { rp.origin[c] = origin[c]; rp.extent[c] = extent[c]; }
     rp.bnx = r->dbn[0];
     rp.bnxy = r->dbn[0] * r->dbn[1];
-    hipError_t e1 = hipMemcpyAsync(staging, host_labels, n_bytes, hipMemcpyHostToDevice, r->stream);
-    if (e1 == hipSuccess) e1 = launch_label_region(rp, r->stream);
-    if (e1 == hipSuccess) e1 = hipStreamSynchronize(r->stream);
-    (void) hipFree(staging);
-    HIP_TRY(e1);
+    HIP_TRY(hipMemcpyAsync(staging.p, host_labels, n_bytes, hipMemcpyHostToDevice, r->stream));
+    HIP_TRY(launch_label_region(rp, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
     int b0[3], b1[3]; // the bricks the box touches
     for (int c = 0; c < 3; ++c) { b0[c] = origin[c] / kBrick; b1[c] = (origin[c] + extent[c] - 1) / kBrick + 1; }
     if (int e = brick_masks(r, b0, b1)) return e;
@@ -221,14 +216,11 @@ int tbrm_download_label_volume(tbrm_resources* r, uint8_t* host_out, size_t n_by
     if (!r->d_labels) return fail(TBRM_ERR_NOT_INITIALIZED, "no label volume");
     if (n_bytes != label_voxels(r)) return fail(TBRM_ERR_INVALID_ARG, "label volume is %zu bytes, got %zu", label_voxels(r), n_bytes);
     if (int e = bind(r)) return e;
-    void* staging = nullptr;
-    HIP_TRY(hipMalloc(&staging, n_bytes));
-    const int dims[3] = {r->desc.dim_x, r->desc.dim_y, r->desc.dim_z};
-    hipError_t e1 = launch_relayout(relayout_params(r->d_labels, staging, dims, r->dbn, 1, false), r->stream);
-    if (e1 == hipSuccess) e1 = hipMemcpyAsync(host_out, staging, n_bytes, hipMemcpyDeviceToHost, r->stream);
-    if (e1 == hipSuccess) e1 = hipStreamSynchronize(r->stream);
-    (void) hipFree(staging);
-    HIP_TRY(e1);
+    DeviceScratch staging;
+    if (int e = staging.make(n_bytes)) return e;
+    HIP_TRY(launch_relayout(relayout_params(r->d_labels, staging.p, r->data_dims(), r->dbn, 1, false), r->stream));
+    HIP_TRY(hipMemcpyAsync(host_out, staging.p, n_bytes, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
     return TBRM_OK;
 }
 

@@ -60,6 +60,41 @@ int build_ray_params(tbrm_resources* r, const tbrm_camera* cam, const tbrm_tile*
     return TBRM_OK;
 }
 
+// the skipping metadata of a lit frame that asks for it, brought up to date
+int attach_skipping(tbrm_resources* r, const tbrm_raymarch_params* rp, RayParams& p)
+{
+    if (!rp->enable_skipping) return TBRM_OK;
+    if (int e = ensure_skipping(r)) return e;
+    p.empty_bits = r->d_empty;
+    p.skip_dist = r->d_dist[0];
+    return TBRM_OK;
+}
+
+// The host-pointer form of a frame call: checks the tile, has `march` (the call's _device form, which makes every other argument
+// check) render it into the handle's own device buffer, grown to the largest tile seen, and copies that to the caller's, complete
+// on return. *delivered: a frame went out (an empty tile is TBRM_OK with nothing done).
+template <class March> int deliver_frame(tbrm_resources* r, const tbrm_tile* tile, float* host_out_rgba, March&& march, bool* delivered = nullptr)
+{
+    if (!r || !tile || !host_out_rgba) return fail(TBRM_ERR_INVALID_ARG, "null argument");
+    if (tile->w < 0 || tile->h < 0) return fail(TBRM_ERR_INVALID_ARG, "bad tile size");
+    const size_t bytes = (size_t) tile->w * tile->h * 4 * sizeof(float);
+    if (bytes == 0) return TBRM_OK;
+    if (int e = bind(r)) return e;
+    if (bytes > r->out_bytes) {
+        HIP_TRY(hipStreamSynchronize(r->stream));
+        (void) hipFree(r->d_out);
+        r->d_out = nullptr;
+        r->out_bytes = 0;
+        HIP_TRY(hipMalloc((void**) &r->d_out, bytes));
+        r->out_bytes = bytes;
+    }
+    if (int e = march(r->d_out)) return e;
+    HIP_TRY(hipMemcpyAsync(host_out_rgba, r->d_out, bytes, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    if (delivered) *delivered = true;
+    return TBRM_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -75,11 +110,7 @@ int tbrm_raymarch_lit_device(tbrm_resources* r, const tbrm_camera* cam, const tb
     if (int e = build_ray_params(r, cam, tile, rp, world, p)) return e;
     p.depth = device_scene_depth;
     p.out = device_out_rgba;
-    if (rp->enable_skipping) {
-        if (int e = ensure_skipping(r)) return e;
-        p.empty_bits = r->d_empty;
-        p.skip_dist = r->d_dist[0];
-    }
+    if (int e = attach_skipping(r, rp, p)) return e;
     if (int e = label_ray_params(r, p)) return e; // (tbrm_labels.h: the label step, when a label volume shows something)
     if (int e = begin_timed(r, 1)) return e;
     if (r->light_channels == 3) { // (tbrm_color_lights.h: ColorSample.rgb x LightVolume.rgb; a colour handle has no label volume)
@@ -113,11 +144,7 @@ int tbrm_raymarch_lit_slab_device(tbrm_resources* r, const tbrm_camera* cam, con
     p.slab_dir = direction > 0 ? 1 : (direction < 0 ? -1 : 0);
     if (r->resident && (slab->z_begin != r->owned.z_begin || slab->z_end != r->owned.z_end))
         return fail(TBRM_ERR_INVALID_ARG, "a slab-resident handle marches its own slab [%d, %d) only", r->owned.z_begin, r->owned.z_end);
-    if (rp->enable_skipping) {
-        if (int e = ensure_skipping(r)) return e;
-        p.empty_bits = r->d_empty;
-        p.skip_dist = r->d_dist[0];
-    }
+    if (int e = attach_skipping(r, rp, p)) return e;
     if (int e = begin_timed(r, 1)) return e;
     HIP_TRY(launch_raymarch(p, r->stream));
     ++r->launches[2];
@@ -127,23 +154,9 @@ int tbrm_raymarch_lit_slab_device(tbrm_resources* r, const tbrm_camera* cam, con
 int tbrm_raymarch_lit(tbrm_resources* r, const tbrm_camera* cam, const tbrm_tile* tile, const tbrm_raymarch_params* rp,
                       const tbrm_world_params* world, float* host_out_rgba)
 {
-    if (!r || !tile || !host_out_rgba) return fail(TBRM_ERR_INVALID_ARG, "null argument");
-    if (tile->w < 0 || tile->h < 0) return fail(TBRM_ERR_INVALID_ARG, "bad tile size");
-    const size_t bytes = (size_t) tile->w * tile->h * 4 * sizeof(float);
-    if (bytes == 0) return TBRM_OK;
-    if (int e = bind(r)) return e;
-    if (bytes > r->out_bytes) {
-        HIP_TRY(hipStreamSynchronize(r->stream));
-        (void) hipFree(r->d_out);
-        r->d_out = nullptr;
-        r->out_bytes = 0;
-        HIP_TRY(hipMalloc((void**) &r->d_out, bytes));
-        r->out_bytes = bytes;
-    }
-    if (int e = tbrm_raymarch_lit_device(r, cam, tile, rp, world, nullptr, r->d_out)) return e;
-    HIP_TRY(hipMemcpyAsync(host_out_rgba, r->d_out, bytes, hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(hipStreamSynchronize(r->stream));
-    return sweep_failed(r); // (a frame lit by a light volume that a failed sweep left undefined is not handed out as good)
+    bool delivered = false;
+    if (int e = deliver_frame(r, tile, host_out_rgba, [&](float* d_out) { return tbrm_raymarch_lit_device(r, cam, tile, rp, world, nullptr, d_out); }, &delivered)) return e;
+    return delivered ? sweep_failed(r) : TBRM_OK; // (a frame lit by a light volume that a failed sweep left undefined is not handed out as good)
 }
 
 int tbrm_raymarch_intensity_device(tbrm_resources* r, const tbrm_camera* cam, const tbrm_tile* tile, const tbrm_raymarch_params* rp,
@@ -166,29 +179,13 @@ int tbrm_raymarch_intensity_device(tbrm_resources* r, const tbrm_camera* cam, co
 int tbrm_raymarch_intensity(tbrm_resources* r, const tbrm_camera* cam, const tbrm_tile* tile, const tbrm_raymarch_params* rp,
                             const tbrm_world_params* world, float* host_out_rgba)
 {
-    if (!r || !tile || !host_out_rgba) return fail(TBRM_ERR_INVALID_ARG, "null argument");
-    if (tile->w < 0 || tile->h < 0) return fail(TBRM_ERR_INVALID_ARG, "bad tile size");
-    const size_t bytes = (size_t) tile->w * tile->h * 4 * sizeof(float);
-    if (bytes == 0) return TBRM_OK;
-    if (int e = bind(r)) return e;
-    if (bytes > r->out_bytes) {
-        HIP_TRY(hipStreamSynchronize(r->stream));
-        (void) hipFree(r->d_out);
-        r->d_out = nullptr;
-        r->out_bytes = 0;
-        HIP_TRY(hipMalloc((void**) &r->d_out, bytes));
-        r->out_bytes = bytes;
-    }
-    if (int e = tbrm_raymarch_intensity_device(r, cam, tile, rp, world, nullptr, r->d_out)) return e;
-    HIP_TRY(hipMemcpyAsync(host_out_rgba, r->d_out, bytes, hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(hipStreamSynchronize(r->stream));
-    return TBRM_OK;
+    return deliver_frame(r, tile, host_out_rgba, [&](float* d_out) { return tbrm_raymarch_intensity_device(r, cam, tile, rp, world, nullptr, d_out); });
 }
 
 int tbrm_octree_mip_dims(const tbrm_resources* r, int mip, int32_t out_dims[3])
 {
     if (!r || !out_dims || mip < 0 || mip > 3) return fail(TBRM_ERR_INVALID_ARG, "bad argument");
-    const int d[3] = {r->desc.dim_x, r->desc.dim_y, r->desc.dim_z};
+    const tbrm_resources::Dims d = r->data_dims();
     for (int c = 0; c < 3; ++c) {
         int p2 = 1;
         while (p2 < d[c]) p2 <<= 1; // FMath::RoundUpToPowerOfTwo (RaymarchVolume.cpp:876-877)
@@ -254,23 +251,7 @@ int tbrm_raymarch_octree_device(tbrm_resources* r, const tbrm_camera* cam, const
 int tbrm_raymarch_octree(tbrm_resources* r, const tbrm_camera* cam, const tbrm_tile* tile, const tbrm_raymarch_params* rp,
                          const tbrm_world_params* world, int octree_mip, float* host_out_rgba)
 {
-    if (!r || !tile || !host_out_rgba) return fail(TBRM_ERR_INVALID_ARG, "null argument");
-    if (tile->w < 0 || tile->h < 0) return fail(TBRM_ERR_INVALID_ARG, "bad tile size");
-    const size_t bytes = (size_t) tile->w * tile->h * 4 * sizeof(float);
-    if (bytes == 0) return TBRM_OK;
-    if (int e = bind(r)) return e;
-    if (bytes > r->out_bytes) {
-        HIP_TRY(hipStreamSynchronize(r->stream));
-        (void) hipFree(r->d_out);
-        r->d_out = nullptr;
-        r->out_bytes = 0;
-        HIP_TRY(hipMalloc((void**) &r->d_out, bytes));
-        r->out_bytes = bytes;
-    }
-    if (int e = tbrm_raymarch_octree_device(r, cam, tile, rp, world, octree_mip, nullptr, r->d_out)) return e;
-    HIP_TRY(hipMemcpyAsync(host_out_rgba, r->d_out, bytes, hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(hipStreamSynchronize(r->stream));
-    return TBRM_OK;
+    return deliver_frame(r, tile, host_out_rgba, [&](float* d_out) { return tbrm_raymarch_octree_device(r, cam, tile, rp, world, octree_mip, nullptr, d_out); });
 }
 
 int tbrm_count_nominal_samples(tbrm_resources* r, const tbrm_camera* cam, const tbrm_tile* tile, const tbrm_raymarch_params* rp,

@@ -105,7 +105,7 @@ int tbrm_slab_pass_begin(tbrm_resources* r, int32_t pass, tbrm_slab_pass* out)
     out->first_chunk = pl.first_chunk_of_pass;
     out->n_chunks = pl.n_chunks;
     out->halo_rows = pl.lateral ? (pl.sliced ? pl.halo_rows : kChunkTile) : 0;
-    out->plane_elem_bytes = pl.sliced ? (r->lv_fmt == FMT_U8 ? 1 : 4) : 4;
+    out->plane_elem_bytes = pl.sliced ? (int) r->light_elem() : 4;
     return TBRM_OK;
 }
 
@@ -132,16 +132,6 @@ int tbrm_slab_pass_plane(tbrm_resources* r, int32_t boundary, int32_t stream, vo
 
 // ---- slab-resident handles: moving their layers in and out -------------------------------------------------------------
 
-namespace {
-// where brick layer `layer` of a volume lives, or null when the handle does not hold it
-char* layer_address(const tbrm_resources::Residency& q, int layer)
-{
-    if (layer >= q.lo && layer < q.hi) return (char*) q.alloc + (size_t) (layer - q.lo) * q.layer_bytes;
-    if (layer == q.wrap_src) return (char*) q.alloc + (size_t) (q.hi - q.lo) * q.layer_bytes;
-    return nullptr;
-}
-} // namespace
-
 int tbrm_slab_resident_slices(const tbrm_resources* r, int32_t data[3], int32_t light[3])
 {
     if (int e = refuse_color(r, "tbrm_slab_resident_slices")) return e;
@@ -167,25 +157,21 @@ int tbrm_upload_volume_slices(tbrm_resources* r, int32_t z_begin, int32_t z_coun
     if (n_bytes != slice * (size_t) z_count) return fail(TBRM_ERR_INVALID_ARG, "%d slices are %zu bytes, got %zu", z_count, slice * (size_t) z_count, n_bytes);
     if (int e = bind(r)) return e;
     quiesce_occ_stream(r);
-    void* staging = nullptr;
-    HIP_TRY(hipMalloc(&staging, n_bytes));
-    hipError_t e1 = hipMemcpyAsync(staging, host_voxels, n_bytes, hipMemcpyHostToDevice, r->stream);
-    int code = TBRM_OK;
-    for (int layer = z_begin / 8; e1 == hipSuccess && layer < ceil_div(z_begin + z_count, 8); ++layer) { // layer by layer: the wrap copy lives elsewhere
-        char* dst = layer_address(r->res_data, layer);
-        if (!dst) { code = fail(TBRM_ERR_INVALID_ARG, "data slices %d.. are not resident on this handle", layer * 8); break; }
+    DeviceScratch staging;
+    if (int e = staging.make(n_bytes)) return e;
+    HIP_TRY(hipMemcpyAsync(staging.p, host_voxels, n_bytes, hipMemcpyHostToDevice, r->stream));
+    for (int layer = z_begin / 8; layer < ceil_div(z_begin + z_count, 8); ++layer) { // layer by layer: the wrap copy lives elsewhere
+        char* dst = r->res_data.address(layer);
+        if (!dst) {
+            (void) hipStreamSynchronize(r->stream); // (the layers before it have been enqueued: they read the caller's buffer and the staging copy)
+            return fail(TBRM_ERR_INVALID_ARG, "data slices %d.. are not resident on this handle", layer * 8);
+        }
         const int lz = std::min(8, nz - layer * 8);
         const int dims[3] = {r->desc.dim_x, r->desc.dim_y, lz}, bn[3] = {r->dbn[0], r->dbn[1], 1};
-        e1 = launch_relayout(relayout_params((const char*) staging + (size_t) (layer * 8 - z_begin) * slice, dst, dims, bn, esz, true), r->stream);
+        HIP_TRY(launch_relayout(relayout_params((char*) staging.p + (size_t) (layer * 8 - z_begin) * slice, dst, dims, bn, esz, true), r->stream));
     }
-    if (e1 == hipSuccess) e1 = hipStreamSynchronize(r->stream);
-    (void) hipFree(staging);
-    if (code != TBRM_OK) return code;
-    HIP_TRY(e1);
-    r->has_volume = true;
-    r->octree_valid = false;
-    r->minmax_valid = false;
-    ++r->data_gen;
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    r->volume_rewritten();
     return TBRM_OK;
 }
 
@@ -194,28 +180,26 @@ int tbrm_download_light_slices(tbrm_resources* r, int32_t z_begin, int32_t z_cou
     if (int e = refuse_color(r, "tbrm_download_light_slices")) return e;
     if (!r || !host_out) return fail(TBRM_ERR_INVALID_ARG, "null argument");
     const int nz = r->lv_dims[2];
-    const size_t esz = r->lv_fmt == FMT_U8 ? 1 : 4, slice = (size_t) r->lv_dims[0] * r->lv_dims[1] * esz;
+    const size_t esz = r->light_elem(), slice = (size_t) r->lv_dims[0] * r->lv_dims[1] * esz;
     if (z_begin < 0 || z_count <= 0 || z_begin + z_count > nz || z_begin % 8 || ((z_begin + z_count) % 8 && z_begin + z_count != nz))
         return fail(TBRM_ERR_INVALID_ARG, "slices [%d, %d): whole brick layers (multiples of 8) of a light volume %d deep", z_begin, z_begin + z_count, nz);
     if (n_bytes != slice * (size_t) z_count) return fail(TBRM_ERR_INVALID_ARG, "%d slices are %zu bytes, got %zu", z_count, slice * (size_t) z_count, n_bytes);
     if (int e = bind(r)) return e;
-    void* staging = nullptr;
-    HIP_TRY(hipMalloc(&staging, n_bytes));
-    hipError_t e1 = hipSuccess;
-    int code = TBRM_OK;
-    for (int layer = z_begin / 8; e1 == hipSuccess && layer < ceil_div(z_begin + z_count, 8); ++layer) {
+    DeviceScratch staging;
+    if (int e = staging.make(n_bytes)) return e;
+    for (int layer = z_begin / 8; layer < ceil_div(z_begin + z_count, 8); ++layer) {
         const tbrm_resources::Residency& q = r->res_light;
-        char* src = (layer >= q.lo && layer < q.hi) ? layer_address(q, layer) : nullptr; // the layer itself, not a wrap copy of it
-        if (!src) { code = fail(TBRM_ERR_INVALID_ARG, "light-volume slices %d.. are not resident on this handle", layer * 8); break; }
+        char* src = (layer >= q.lo && layer < q.hi) ? q.address(layer) : nullptr; // the layer itself, not a wrap copy of it
+        if (!src) { // (nothing partly filled goes to the host)
+            (void) hipStreamSynchronize(r->stream); // (the layers before it write the staging buffer)
+            return fail(TBRM_ERR_INVALID_ARG, "light-volume slices %d.. are not resident on this handle", layer * 8);
+        }
         const int lz = std::min(8, nz - layer * 8);
         const int dims[3] = {r->lv_dims[0], r->lv_dims[1], lz}, bn[3] = {r->lbn[0], r->lbn[1], 1};
-        e1 = launch_relayout(relayout_params(src, (char*) staging + (size_t) (layer * 8 - z_begin) * slice, dims, bn, esz, false), r->stream);
+        HIP_TRY(launch_relayout(relayout_params(src, (char*) staging.p + (size_t) (layer * 8 - z_begin) * slice, dims, bn, esz, false), r->stream));
     }
-    if (e1 == hipSuccess && code == TBRM_OK) e1 = hipMemcpyAsync(host_out, staging, n_bytes, hipMemcpyDeviceToHost, r->stream);
-    if (e1 == hipSuccess) e1 = hipStreamSynchronize(r->stream);
-    (void) hipFree(staging);
-    if (code != TBRM_OK) return code;
-    HIP_TRY(e1);
+    HIP_TRY(hipMemcpyAsync(host_out, staging.p, n_bytes, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
     return sweep_failed(r); // (the slices of a light volume a failed sweep left undefined are not handed out as good)
 }
 
@@ -229,8 +213,8 @@ int tbrm_slab_light_halo(tbrm_resources* r, int32_t side, void** send_layer, voi
     const int first = r->owned.z_begin / 8, last = r->owned.z_end / 8 - 1, layers = r->lbn[2];
     const int send = side == 0 ? first : last;
     const int recv = side == 0 ? (first == 0 ? layers - 1 : first - 1) : (last == layers - 1 ? 0 : last + 1); // across the ends: the wrap copy
-    *send_layer = layer_address(q, send);
-    *recv_layer = (recv >= first && recv <= last) ? nullptr : layer_address(q, recv); // a handle that owns everything has no halo
+    *send_layer = q.address(send);
+    *recv_layer = (recv >= first && recv <= last) ? nullptr : q.address(recv); // a handle that owns everything has no halo
     *layer_bytes = q.layer_bytes;
     return TBRM_OK;
 }

@@ -16,8 +16,6 @@ using namespace tbrm_host;
 
 namespace {
 
-constexpr size_t kMaxDirtyBoxes = 64;
-
 // What every region call checks before it touches the device, in this order: the pointers, the box's signs (they need no handle),
 // the handle and what it holds, the box against the volume, the byte count.
 int region_args(const tbrm_resources* r, const int32_t origin[3], const int32_t extent[3], const void* voxels, size_t n_bytes, size_t* n_voxels)
@@ -30,7 +28,7 @@ int region_args(const tbrm_resources* r, const int32_t origin[3], const int32_t 
     if (!r) return fail(TBRM_ERR_INVALID_ARG, "null argument");
     if (r->resident) return fail(TBRM_ERR_UNSUPPORTED, "slab-resident handle: its layers are uploaded with tbrm_upload_volume_slices");
     if (!r->has_volume) return fail(TBRM_ERR_NOT_INITIALIZED, "no volume: upload one with tbrm_upload_volume");
-    const int dims[3] = {r->desc.dim_x, r->desc.dim_y, r->desc.dim_z};
+    const tbrm_resources::Dims dims = r->data_dims();
     size_t n = 1;
     for (int c = 0; c < 3; ++c) {
         if (extent[c] > dims[c] - origin[c])
@@ -85,24 +83,6 @@ uint64_t fnv1a(const void* data, size_t n)
     return h;
 }
 
-// the state a written box leaves behind (tbrm_volume_region.h)
-void region_written(tbrm_resources* r, const int32_t origin[3], const int32_t extent[3], size_t n_voxels)
-{
-    r->octree_valid = false;
-    ++r->data_gen;
-    ++r->region_counters[0];
-    r->region_counters[1] += n_voxels;
-    if (!r->minmax_valid) return; // (every brick's range is due anyway)
-    if (r->dirty_boxes.size() >= kMaxDirtyBoxes) { // too many to be worth tracking: the whole grid, once
-        r->dirty_boxes.clear();
-        r->minmax_valid = false;
-        return;
-    }
-    tbrm_resources::DirtyBox b{};
-    for (int c = 0; c < 3; ++c) { b.origin[c] = origin[c]; b.extent[c] = extent[c]; }
-    r->dirty_boxes.push_back(b);
-}
-
 } // namespace
 
 namespace tbrm_host {
@@ -138,7 +118,7 @@ int tbrm_update_volume_region_device(tbrm_resources* r, const int32_t origin[3],
     quiesce_occ_stream(r); // (nothing on the second stream may still be reading the volume)
     HIP_TRY(launch_volume_region(region_params(r, origin, extent, device_voxels, true), r->stream));
     HIP_TRY(hipStreamSynchronize(r->stream));
-    region_written(r, origin, extent, n);
+    r->region_written(origin, extent, n);
     return TBRM_OK;
 }
 
@@ -148,14 +128,12 @@ int tbrm_update_volume_region(tbrm_resources* r, const int32_t origin[3], const 
     if (int e = region_args(r, origin, extent, host_voxels, n_bytes, &n)) return e;
     if (int e = bind(r)) return e;
     quiesce_occ_stream(r);
-    void* staging = nullptr; // the box in HBM, scattered into the bricks by the GPU
-    HIP_TRY(hipMalloc(&staging, n_bytes));
-    hipError_t e1 = hipMemcpyAsync(staging, host_voxels, n_bytes, hipMemcpyHostToDevice, r->stream);
-    if (e1 == hipSuccess) e1 = launch_volume_region(region_params(r, origin, extent, staging, true), r->stream);
-    if (e1 == hipSuccess) e1 = hipStreamSynchronize(r->stream); // the caller may free its buffer on return
-    (void) hipFree(staging);
-    HIP_TRY(e1);
-    region_written(r, origin, extent, n);
+    DeviceScratch staging; // the box in HBM, scattered into the bricks by the GPU
+    if (int e = staging.make(n_bytes)) return e;
+    HIP_TRY(hipMemcpyAsync(staging.p, host_voxels, n_bytes, hipMemcpyHostToDevice, r->stream));
+    HIP_TRY(launch_volume_region(region_params(r, origin, extent, staging.p, true), r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream)); // the caller may free its buffer on return
+    r->region_written(origin, extent, n);
     return TBRM_OK;
 }
 
@@ -164,13 +142,11 @@ int tbrm_download_volume_region(tbrm_resources* r, const int32_t origin[3], cons
     size_t n = 0;
     if (int e = region_args(r, origin, extent, host_out, n_bytes, &n)) return e;
     if (int e = bind(r)) return e;
-    void* staging = nullptr;
-    HIP_TRY(hipMalloc(&staging, n_bytes));
-    hipError_t e1 = launch_volume_region(region_params(r, origin, extent, staging, false), r->stream);
-    if (e1 == hipSuccess) e1 = hipMemcpyAsync(host_out, staging, n_bytes, hipMemcpyDeviceToHost, r->stream);
-    if (e1 == hipSuccess) e1 = hipStreamSynchronize(r->stream);
-    (void) hipFree(staging);
-    HIP_TRY(e1);
+    DeviceScratch staging;
+    if (int e = staging.make(n_bytes)) return e;
+    HIP_TRY(launch_volume_region(region_params(r, origin, extent, staging.p, false), r->stream));
+    HIP_TRY(hipMemcpyAsync(host_out, staging.p, n_bytes, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
     return TBRM_OK;
 }
 

@@ -32,7 +32,7 @@ int stats_handle(const tbrm_resources* r)
 // the box against the volume; an all-zero extent (or no box at all) is the whole volume
 int stats_box(const tbrm_resources* r, const int32_t* origin, const int32_t* extent, StatsParams& p)
 {
-    const int dims[3] = {r->desc.dim_x, r->desc.dim_y, r->desc.dim_z};
+    const tbrm_resources::Dims dims = r->data_dims();
     const bool whole = !extent || (extent[0] == 0 && extent[1] == 0 && extent[2] == 0);
     for (int c = 0; c < 3; ++c) {
         const int o = whole ? 0 : origin[c], e = whole ? dims[c] : extent[c];

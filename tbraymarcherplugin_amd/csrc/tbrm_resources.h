@@ -31,6 +31,24 @@ inline size_t format_bytes(int fmt) { return fmt == TBRM_FMT_G8 ? 1 : (fmt == TB
                 #expr, hipGetErrorString(e_));                                                                \
     } while (0)
 
+// A scratch device allocation that lives as long as one call: the staging buffer of a host <-> device transfer, the few words
+// of a selftest. Freed when its owner goes out of scope, whichever way the call returns, so that the steps after make() are
+// HIP_TRY lines in stream order. Neither the hipMalloc nor the hipFree is counted in alloc_calls / sync_calls.
+struct DeviceScratch {
+    void* p = nullptr;
+    DeviceScratch() = default;
+    DeviceScratch(DeviceScratch&& o) noexcept : p(std::exchange(o.p, nullptr)) {}
+    DeviceScratch& operator=(DeviceScratch&& o) noexcept { std::swap(p, o.p); return *this; } // (o frees what this held)
+    DeviceScratch(const DeviceScratch&) = delete;
+    DeviceScratch& operator=(const DeviceScratch&) = delete;
+    ~DeviceScratch() { if (p) (void) hipFree(p); } // (an empty guard never touches the device)
+    int make(size_t n_bytes) // fills an empty guard: TBRM_OK, or what HIP_TRY makes of a failed hipMalloc
+    {
+        HIP_TRY(hipMalloc(&p, n_bytes));
+        return TBRM_OK;
+    }
+};
+
 // The occlusion factors 1 - CurrentSample (AddDirLightShader.usf:85-117) of ONE light stream for a span of S slices of an
 // axis pass, as the chain kernel consumes them: [page of ones | guard][S x H x W floats][guard], plus the pass's
 // empty-block flags and work lists. Overwritten span by span; a handle has two per stream, so that the next span's can be
@@ -173,8 +191,11 @@ struct FactorScratch {
 
 struct tbrm_resources {
     tbrm_resources_desc desc{};
+    struct Dims { int v[3]; operator const int*() const { return v; } };
+    Dims data_dims() const { return Dims{{desc.dim_x, desc.dim_y, desc.dim_z}}; } // the data volume's, as the light volume's lv_dims
     int32_t lv_dims[3]{};
     int lv_fmt = tbrm::FMT_U8;
+    size_t light_elem() const { return lv_fmt == tbrm::FMT_U8 ? 1 : 4; } // bytes of a light-volume voxel
     int n_cus = 256;               // compute units of the device (chunk length heuristics)
     hipStream_t stream = nullptr;
 
@@ -186,7 +207,19 @@ struct tbrm_resources {
     // [lo, hi) contiguously, then one more layer holding a copy of layer `wrap_src` (what wrap addressing reaches from the
     // first / last slice; -1: none). d_data / d_light point lo * layer_bytes BEFORE the allocation, so a kernel that only
     // touches resident layers addresses them with the global brick offsets, unchanged.
-    struct Residency { int lo = 0, hi = 0, wrap_src = -1; size_t layer_bytes = 0; void* alloc = nullptr; };
+    struct Residency {
+        int lo = 0, hi = 0, wrap_src = -1;
+        size_t layer_bytes = 0;
+        void* alloc = nullptr;
+        int layers() const { return hi - lo + (wrap_src >= 0 ? 1 : 0); } // brick layers held, the wrap copy included
+        size_t bytes() const { return (size_t) layers() * layer_bytes; }  // ... and what they take
+        char* address(int layer) const // where brick layer `layer` lives (wrap_src: the copy of it), or null when it is not held
+        {
+            if (layer >= lo && layer < hi) return (char*) alloc + (size_t) (layer - lo) * layer_bytes;
+            if (layer >= 0 && layer == wrap_src) return (char*) alloc + (size_t) (hi - lo) * layer_bytes; // (-1: no wrap copy, not "layer -1")
+            return nullptr;
+        }
+    };
     bool resident = false;
     tbrm_slab owned{};
     Residency res_data, res_light;
@@ -322,6 +355,27 @@ struct tbrm_resources {
     // data-volume region updates (tbrm_api_volume_region.cpp; include/tbrm_volume_region.h)
     struct DirtyBox { int origin[3], extent[3]; };
     std::vector<DirtyBox> dirty_boxes; // boxes written while minmax_valid held: ensure_skipping recomputes the bricks they reach
+    static constexpr size_t kMaxDirtyBoxes = 64;
+    // The two statements of "data voxels were written". What EVERY new voxel value invalidates goes into data_changed().
+    void data_changed() { octree_valid = false; ++data_gen; } // (data_gen: the factor cache serves nothing computed from the old voxels)
+    // the whole volume (tbrm_upload_volume, _device, _slices): every brick's range is due
+    void volume_rewritten() { has_volume = true; minmax_valid = false; data_changed(); }
+    // a box of it (tbrm_volume_region.h): the ranges stay valid where no box reaches, the box joins dirty_boxes
+    void region_written(const int32_t origin[3], const int32_t extent[3], size_t n_voxels)
+    {
+        data_changed();
+        ++region_counters[0];
+        region_counters[1] += n_voxels;
+        if (!minmax_valid) return; // (every brick's range is due anyway)
+        if (dirty_boxes.size() >= kMaxDirtyBoxes) { // too many to be worth tracking: the whole grid, once
+            dirty_boxes.clear();
+            minmax_valid = false;
+            return;
+        }
+        DirtyBox b{};
+        for (int c = 0; c < 3; ++c) { b.origin[c] = origin[c]; b.extent[c] = extent[c]; }
+        dirty_boxes.push_back(b);
+    }
     uint64_t region_counters[4]{};   // tbrm_volume_region_counters
 
     // volume statistics (tbrm_api_volume_stats.cpp; include/tbrm_volume_stats.h)

@@ -313,3 +313,19 @@ def test_refusals(gpu):
         assert np.array_equal(col.download_light_channel(0), before[0]) and np.array_equal(col.download_light_channel(2), before[2])
         mono.upload_light_channel(0, pattern)
         assert np.array_equal(mono.download_light_channel(0), pattern) and np.array_equal(mono.download_light_volume(), pattern)
+
+
+@pytest.mark.parametrize("light32", [False, True], ids=["u8", "f32"])
+def test_light_transfers_round_trip_on_a_ragged_volume(gpu, light32):
+    """upload then download, exactly, where the bricked layout has something to get wrong: 3 x 2 x 2 bricks, no edge a multiple of 8"""
+    dims = (20, 12, 9)
+    rng = np.random.default_rng(20129)
+    shape = dims[::-1]
+    chans = [rng.random(shape, dtype=np.float32) if light32 else rng.integers(0, 256, size=shape, dtype=np.uint8) for _ in range(4)]
+    with abi.Resources(dims, abi.FMT_G8, light32, rgb=True) as col, abi.Resources(dims, abi.FMT_G8, light32) as mono:
+        for c in (2, 0, 1):
+            col.upload_light_channel(c, chans[c])
+        for c in range(3):
+            assert np.array_equal(col.download_light_channel(c), chans[c]), c
+        mono.upload_light_volume(chans[3])
+        assert np.array_equal(mono.download_light_volume(), chans[3]) and np.array_equal(mono.download_light_channel(0), chans[3])

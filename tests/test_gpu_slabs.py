@@ -357,6 +357,50 @@ def test_slab_resident_handles_light_and_render_like_one_handle(gpu, addr, n_sla
             res.close()
 
 
+def test_slice_transfers_with_both_wrap_copies(gpu):
+    """tbrm_upload_volume_slices / tbrm_download_light_slices on the smallest pair of slab-resident handles whose light volumes hold
+    both wrap copies (wrap addressing: the first slab keeps a copy of the last layer, the last slab one of layer 0): the light
+    volume that lights along every axis leave behind, which reads every data layer, equals a whole handle's, slab by slab.
+    (Data volumes with wrap copies: the 4-slab case of test_slab_resident_handles_light_and_render_like_one_handle.)"""
+    dims = (16, 16, 64)
+    vol = small_volume(dims, np.uint16, 0x5EED0404)
+    lut = abi.color_curve_to_lut(S.tf_keys("A"))
+    w = abi.WindowingParams(0.5, 0.9, True, False)
+    bounds = [(0, 32), (32, 64)]
+    full = abi.Resources(dims, abi.FMT_G16, False, False, 0, abi.ADDRESS_WRAP)
+    parts = [abi.Resources(dims, abi.FMT_G16, False, False, 0, abi.ADDRESS_WRAP, owned=abi.Slab(*b)) for b in bounds]
+    try:
+        full.upload_volume(vol)
+        for res in [full] + parts:
+            res.set_tf_lut(lut)
+            res.set_windowing(w)
+        for res, wrap_slice in zip(parts, (56, 0)):
+            res.upload_resident_part(vol)
+            (dlo, dhi, dwrap), (llo, lhi, lwrap) = res.resident_slices()
+            assert lwrap == wrap_slice and (dlo, dhi, dwrap) == (0, 64, -1)   # (so short a data volume is resident as a whole)
+            res.clear_light_volume(0.0)
+        full.clear_light_volume(0.0)
+        members = [slabs.DeviceSlab(res, k, *bounds[k]) for k, res in enumerate(parts)]
+        fabric = slabs.make_fabric([b[0] for b in bounds] + [dims[2]])
+        world = S.default_world()
+        for d, inten in LIGHTS[:3]:   # one light along each major axis
+            light = abi.DirLightParams(d, inten)
+            full.add_dir_light(light, True, world)
+            slabs.add_dir_light(members, fabric, light, True, world)
+        ref = full.download_light_volume()
+        assert ref.any()
+        for m in members:
+            assert np.array_equal(m.res.download_light_slices(m.z_begin, m.z_end - m.z_begin), ref[m.z_begin:m.z_end]), m.slab_index
+            for z in range(m.z_begin, m.z_end, 8):   # layer by layer: every staging offset
+                assert np.array_equal(m.res.download_light_slices(z, 8), ref[z:z + 8]), (m.slab_index, z)
+        with pytest.raises(abi.TbrmError) as e:   # the other slab's slices: a wrap copy of a layer is not the layer
+            parts[0].download_light_slices(56, 8)
+        assert e.value.code == abi.ERR_INVALID_ARG and "not resident" in str(e.value)
+    finally:
+        for res in [full] + parts:
+            res.close()
+
+
 @pytest.mark.parametrize("seed", range(8))
 def test_random_slab_resident_scenes_against_one_handle(gpu, seed):
     """Seeded random scenes on slab-resident handles: ragged x / y sizes, 2-4 slabs, formats, rotated and scaled volumes with
