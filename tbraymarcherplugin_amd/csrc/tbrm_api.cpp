@@ -480,20 +480,20 @@ static int create_impl(const tbrm_resources_desc* desc, const tbrm_slab* owned, 
     for (int k = 0; k < 2; ++k) CREATE_TRY(hipMalloc((void**) &r->d_dist[k], nb_pad));
     CREATE_TRY(hipMalloc((void**) &r->d_alpha_prefix, 258 * sizeof(int)));
     CREATE_TRY(hipMalloc((void**) &r->d_counter, sizeof(unsigned long long)));
-    if (!r->resident) { // k_raymarch_lit's offset tables (RayParams::tab): per axis, for texel index i = -2 .. n + 1, where the data
-                        // sampler's address mode puts it in the bricked layout, and its brick's share of the linear brick index
+    if (!r->resident) { // k_raymarch_lit's offset tables (RayParams::tab, laid out by ray_tab_*): per axis and texel index, where the data
+                        // sampler's address mode puts the texel in the bricked layout, and its brick's share of the linear brick index
         const int dn[3] = {desc->dim_x, desc->dim_y, desc->dim_z};
-        std::vector<uint2> tab;
-        for (int c = 0; c < 3; ++c)
-            for (int i = -2; i < dn[c] + 2; ++i) {
+        std::vector<uint2> tab((size_t) ray_tab_entries(dn[0], dn[1], dn[2]), make_uint2(0, 0));
+        uint2* axis = tab.data();
+        for (int c = 0; c < 3; axis += ray_tab_axis_entries(dn[c]), ++c)
+            for (int i = -kRayTabApron; ray_tab_index(i) < ray_tab_axis_entries(dn[c]); ++i) {
                 int w = i;
                 if (desc->data_address_mode == TBRM_ADDRESS_CLAMP) w = clamp_int(i, 0, dn[c] - 1);
                 else { w %= dn[c]; if (w < 0) w += dn[c]; }
                 const uint32_t in_brick = (uint32_t) (w & 7) << (3 * c);
                 const uint32_t brick = (uint32_t) (w >> 3) * (c == 0 ? 1u : (c == 1 ? (uint32_t) r->dbn[0] : (uint32_t) (r->dbn[0] * r->dbn[1])));
-                tab.push_back(make_uint2((brick << 9) | in_brick, brick));
+                axis[ray_tab_index(i)] = make_uint2((brick << 9) | in_brick, brick);
             }
-        if (tab.size() & 1) tab.push_back(make_uint2(0, 0));
         CREATE_TRY(hipMalloc((void**) &r->d_ray_tab, tab.size() * sizeof(uint2)));
         CREATE_TRY(hipMemcpy(r->d_ray_tab, tab.data(), tab.size() * sizeof(uint2), hipMemcpyHostToDevice));
     }

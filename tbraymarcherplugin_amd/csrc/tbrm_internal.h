@@ -257,8 +257,8 @@ struct RayParams {
     float* out;         // tile_w*tile_h*4
     const uint32_t* empty_bits; // one bit per brick; null when skipping is off
     int xcd_rows;               // k_raymarch_lit: rows of pixel blocks per band dealt to one XCD (tunable ray_xcd_rows; 0: launch order)
-    const uint2* tab;           // k_raymarch_lit TAB: per axis and texel index -2 .. n + 1 the {voxel offset, brick-index part} of the
-                                // addressed texel (x, then y, then z); null: none (slab-resident handles)
+    const uint2* tab;           // k_raymarch_lit TAB: per axis and texel index the {voxel offset, brick-index part} of the addressed
+                                // texel, laid out by ray_tab_* below; null: none (slab-resident handles)
     const uint8_t* skip_dist;   // per brick: Chebyshev distance (bricks, capped) to the nearest non-empty brick; null when skipping is off
     int bnx, bny, bnz;  // brick grid
     unsigned long long* sample_counter; // count kernel only
@@ -272,6 +272,15 @@ struct RayParams {
     const void* light_g;        // k_raymarch_lit RGB (colour handles, tbrm_color_lights.h): the G and B channels of the light volume,
     const void* light_b;        // laid out like `light` (then the R channel); null: a mono light volume
 };
+
+// Layout of RayParams::tab (built in tbrm_resources_create, copied into LDS and read by k_raymarch_lit TAB): the x, then the y, then
+// the z axis, one entry for every texel index -kRayTabApron .. n + kRayTabApron - 1 (a base tap two texels outside the volume and its
+// +1 tap still have entries), the total padded to an even count (the copy moves 16 bytes at a time).
+constexpr int kRayTabApron = 2;
+constexpr int ray_tab_axis_entries(int n) { return n + 2 * kRayTabApron; }
+constexpr int ray_tab_index(int texel) { return texel + kRayTabApron; }
+constexpr int ray_tab_last_base(int n) { return ray_tab_axis_entries(n) - 2; } // the last index of an axis whose +1 entry exists
+constexpr int ray_tab_entries(int nx, int ny, int nz) { return (ray_tab_axis_entries(nx) + ray_tab_axis_entries(ny) + ray_tab_axis_entries(nz) + 1) & ~1; }
 
 struct BrickParams {
     VolumeDev data;

@@ -134,12 +134,59 @@ __device__ __forceinline__ bool tile_pixel_at(const RayParams& p, int i, int j, 
 
 __device__ __forceinline__ bool tile_pixel(const RayParams& p, int& i, int& j, int& px, int& py)
 {
-    // 16x16 pixel block per workgroup, one 8x8 sub-tile per wave64 (count kernel)
+    // 16x16 pixel block per workgroup, one 8x8 sub-tile per wave64 (the intensity, octree and count kernels: launch_pixel_blocks)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     i = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
     j = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
     return tile_pixel_at(p, i, j, px, py);
 }
+
+// The head of every march (PerformWindowedLitRaymarch, WindowedRaymarchMaterials.usf:46-62; the octree and intensity marches open the
+// same way, :111-127 and :194-206) with JitterEntryPos (RaymarchMaterialCommon.usf:73-78): the ray's sample count and where it starts.
+struct March {
+    int max_steps;    // full steps: floor(Steps * thickness)
+    float final_step; // the fraction of a step behind them
+    int n_samples;    // the full steps, then the fractional one if there is any (:84-93)
+    float sv[3];      // LocalCamVec * StepSize: what a full step adds to the position
+    float pos[3];     // the (jittered) entry position
+    float step_world; // a full step's length for the opacity correction
+};
+__device__ __forceinline__ March march_setup(const RayParams& p, const Ray& ray, int px, int py, bool valid) // !valid: a ray of no samples
+{
+    March m;
+    const float step_size = 1 / p.steps;
+    const float actual = p.steps * ray.thickness;
+    const float fl = floorf(actual);
+    m.max_steps = valid ? (int) fl : 0;
+    m.final_step = valid ? actual - fl : 0.0f;
+    m.n_samples = m.max_steps + (m.final_step > 0.0f ? 1 : 0);
+    m.step_world = 100.0f * step_size;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        m.sv[c] = ray.lcv[c] * step_size;
+        m.pos[c] = ray.pos[c];
+    }
+    if (p.jitter_frame >= 0) {
+        uint32_t rr;
+        rand3d_pcg16(px, py, p.jitter_frame & 7, rr);
+        const float rnd = (float) rr / 65535.0f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) m.pos[c] = m.pos[c] - (m.sv[c] * rnd);
+    }
+    return m;
+}
+
+// AccumulateLightEnergy (RaymarchMaterialCommon.usf:82-88): c = (colour * alpha, alpha) of a sample, front to back
+__device__ __forceinline__ void accumulate(float (&le)[4], const float4& c)
+{
+    const float om = 1.0f - le[3];
+    le[0] = le[0] + (c.x * om);
+    le[1] = le[1] + (c.y * om);
+    le[2] = le[2] + (c.z * om);
+    le[3] = le[3] + (c.w * om);
+}
+// The early exit (:75-79) belongs to the full steps only; the march that takes it leaves alpha at exactly 1.
+__device__ __forceinline__ bool exit_reached(float le3, bool is_full_step) { return le3 > 0.95f && is_full_step; }
 
 // ---- k_raymarch_lit ---------------------------------------------------------------------------------------------
 // A ray is a serial loop in the reference (positions by repeated addition, front-to-back accumulation with early
@@ -174,9 +221,10 @@ extern "C" __attribute__((visibility("default"))) int tbrm_debug_ray_stats(unsig
 
 // TAB: the data volume's texel -> voxel-offset arithmetic (address mode, +1 tap, bricked offset, brick index of the leap-distance
 // look-up: ~45 integer instructions per sample, more than the filter itself) comes out of three small tables the workgroup copies
-// into LDS, one {voxel offset, brick-index part} pair per texel index -2 .. n + 1 and axis (tbrm_api.cpp build_ray_tables); a
-// sample's base and +1 entries of an axis arrive with one 16-byte LDS read. The host picks it when no sample position can lie more than two texels outside the volume
-// (a step of at most one texel: positions stay within one step of the unit cube) and the tables are small.
+// into LDS, one {voxel offset, brick-index part} pair per texel index and axis (tbrm_internal.h ray_tab_*; tbrm_resources_create builds
+// them); a sample's base and +1 entries of an axis arrive with one 16-byte LDS read. The host picks it when no sample position can lie
+// more than two texels outside the volume (a step of at most one texel: positions stay within one step of the unit cube) and the
+// tables are small.
 //
 // LABELS: the label overlay (include/tbrm_labels.h). The lane that takes sample idx also loads the label byte of the sample's
 // nearest voxel, beside the data taps; the replay then applies, per sample and in ray order, the data step, the unlit label step
@@ -196,10 +244,10 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
     static_assert(kRayLanes == 4 || kRayLanes == 8, "instantiated for 4 and 8 lanes per ray");
     static_assert(!(TAB && SLAB), "slab stages keep the arithmetic path (relocated layers)");
     static_assert(!(LABELS && SLAB), "slab stages have no label step");
-    extern __shared__ __attribute__((aligned(16))) uint2 s_tab[]; // TAB: [x | y | z], n + 4 entries each; LABELS: then s_lab, s_lb
+    extern __shared__ __attribute__((aligned(16))) uint2 s_tab[]; // TAB: [x | y | z] (ray_tab_*); LABELS: then s_lab, s_lb
     const uint2* const tab_x = s_tab;
-    const uint2* const tab_y = tab_x + (TAB ? p.data.nx + 4 : 0);
-    const uint2* const tab_z = tab_y + (TAB ? p.data.ny + 4 : 0);
+    const uint2* const tab_y = tab_x + (TAB ? ray_tab_axis_entries(p.data.nx) : 0);
+    const uint2* const tab_z = tab_y + (TAB ? ray_tab_axis_entries(p.data.ny) : 0);
     constexpr int PW = 4, PH = kRayLanes == 4 ? 4 : 2; // rays of a wave: a PW x PH pixel patch
     constexpr int kRayBlockW = 2 * PW, kRayBlockH = 2 * PH;
     constexpr int LSH = kRayLanes == 4 ? 2 : 3;
@@ -207,7 +255,7 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
     __shared__ float4 s_x[256]; // per lane: (colour * alpha, alpha) of its sample; alpha < 0: nothing to accumulate
     s_tf[threadIdx.x] = p.tf[threadIdx.x];
     // LABELS: per colour-table entry its full-step (rgb * a', a'); per lane the label of its sample (-1: no label step)
-    float4* const s_lab = reinterpret_cast<float4*>(s_tab + (TAB ? (p.data.nx + p.data.ny + p.data.nz + 12 + 1) & ~1 : 0));
+    float4* const s_lab = reinterpret_cast<float4*>(s_tab + (TAB ? ray_tab_entries(p.data.nx, p.data.ny, p.data.nz) : 0));
     short* const s_lb = reinterpret_cast<short*>(s_lab + 256);
     if constexpr (LABELS) {
         const float4 c = p.lab_colors[threadIdx.x];
@@ -238,27 +286,16 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
     cube_setup(p, valid ? px : p.tile_x0, valid ? py : p.tile_y0, ray);
 
     // PerformWindowedLitRaymarch (WindowedRaymarchMaterials.usf:36-96)
-    const float step_size = 1 / p.steps;
-    const float actual = p.steps * ray.thickness;
-    const float fl = floorf(actual);
-    const int max_steps = valid ? (int) fl : 0;
-    const float final_step = valid ? actual - fl : 0.0f;
-    const int n_samples = max_steps + (final_step > 0.0f ? 1 : 0); // the full steps, then the fractional one (:84-93)
+    const March m = march_setup(p, ray, px, py, valid);
+    const int max_steps = m.max_steps, n_samples = m.n_samples;
+    const float final_step = m.final_step, step_world = m.step_world, sv0 = m.sv[0], sv1 = m.sv[1], sv2 = m.sv[2];
+    float pos0 = m.pos[0], pos1 = m.pos[1], pos2 = m.pos[2];
     if constexpr (TAB) { // the tables (the handle built them once: tbrm_resources::d_ray_tab), unless no ray of the workgroup meets the volume
         if (__syncthreads_or(n_samples > 0)) {
-            const int n16 = (p.data.nx + p.data.ny + p.data.nz + 12 + 1) >> 1;
+            const int n16 = ray_tab_entries(p.data.nx, p.data.ny, p.data.nz) >> 1;
             for (int i = threadIdx.x; i < n16; i += 256) reinterpret_cast<uint4*>(s_tab)[i] = reinterpret_cast<const uint4*>(p.tab)[i];
             __syncthreads();
         }
-    }
-    const float sv0 = ray.lcv[0] * step_size, sv1 = ray.lcv[1] * step_size, sv2 = ray.lcv[2] * step_size;
-    const float step_world = 100.0f * step_size;
-    float pos0 = ray.pos[0], pos1 = ray.pos[1], pos2 = ray.pos[2];
-    if (p.jitter_frame >= 0) { // JitterEntryPos (RaymarchMaterialCommon.usf:73-78)
-        uint32_t rr;
-        rand3d_pcg16(px, py, p.jitter_frame & 7, rr);
-        const float rnd = (float) rr / 65535.0f;
-        pos0 = pos0 - (sv0 * rnd); pos1 = pos1 - (sv1 * rnd); pos2 = pos2 - (sv2 * rnd);
     }
 
     const float nx = (float) p.data.nx, ny = (float) p.data.ny, nz = (float) p.data.nz;
@@ -275,23 +312,26 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
     bool eager = false;  // the wave's last trip sampled nothing: this trip's lanes renew their ranges (wave-uniform)
     int renew_wait = 0;  // empty trips to let pass before the next renewal (a renewal that bought no blind trip is not repeated at once)
 
-    float le0 = 0.0f, le1 = 0.0f, le2 = 0.0f, le3 = 0.0f; // LightEnergy, replicated in the 8 lanes of the ray
+    float le[4] = {0.0f, 0.0f, 0.0f, 0.0f}; // LightEnergy, replicated in the kRayLanes lanes of the ray
     bool done = n_samples == 0;
     bool mine = valid; // SLAB: this stage's sweep direction handles the ray (rays with local dz >= 0 go up through the slabs)
     if constexpr (SLAB) {
         mine = valid && (p.slab_dir == 0 || (p.slab_dir > 0) == (ray.lcv[2] >= 0.0f));
         if (mine) {
             const float4 in = reinterpret_cast<const float4*>(p.out)[(size_t) j * p.tile_w + i];
-            le0 = in.x; le1 = in.y; le2 = in.z; le3 = in.w;
-            done = done || le3 == 1.0f; // the early exit was taken in a slab before this one (it leaves alpha at exactly 1)
+            le[0] = in.x; le[1] = in.y; le[2] = in.z; le[3] = in.w;
+            done = done || le[3] == 1.0f; // the early exit was taken in a slab before this one (it leaves alpha at exactly 1)
         } else done = true;
     }
     int adds = 0; // full-step additions this lane has applied to its position
-    float4* const xs = s_x + (threadIdx.x & ~(kRayLanes - 1)); // the ray's 8 exchange slots
+    float4* const xs = s_x + (threadIdx.x & ~(kRayLanes - 1)); // the ray's kRayLanes exchange slots
 
+    // A trip is five stages: advance the position, locate the sample, shade it, exchange and replay, the wave-wide leap. They stay one
+    // body, each stage a headed block: at 80 registers the allocation does not survive cutting them out (any one of them as a by-reference
+    // lambda or an inlined function gave some instantiation scratch it had not had).
     for (int base = 0; __builtin_amdgcn_ballot_w64(!done) != 0; base += kRayLanes) {
         const int idx = base + b; // this lane's sample of the ray
-        // CurPos += LocalCamVec before every full sample (:67): sample idx < max_steps sits idx+1 additions in, the
+        // ---- 1. advance. CurPos += LocalCamVec before every full sample (:67): sample idx < max_steps sits idx+1 additions in, the
         // fractional sample max_steps additions plus one scaled step
         const int want = min(idx + 1, max_steps);
         if (__builtin_amdgcn_ballot_w64(!done && want - adds != kRayLanes) == 0) { // mid-ray everywhere: no predication
@@ -308,7 +348,8 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
         const bool has = !done && idx < n_samples;
         if (!is_full) { q0 = pos0 + (sv0 * final_step); q1 = pos1 + (sv1 * final_step); q2 = pos2 + (sv2 * final_step); step = 100.0f * final_step; }
 
-        // the sample: everything of the loop body up to AccumulateLightEnergy
+        // ---- 2. locate: does the sample have to be evaluated (live), where do its data taps lie (texel split, TAB offsets), and how far
+        // does its brick's leap distance prove the lane's next samples empty (safe_until)
         float4 x = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
         bool live = has && idx > safe_until && !(p.clip_mode && is_clipped(q0, q1, q2, p.cc, p.cd));
         if constexpr (SLAB) { // only the samples of this handle's slab
@@ -333,8 +374,10 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
                 texel_split(q2, nz, iz, fz);
             }
             uint32_t tab_brick = 0;
-            if constexpr (TAB) { // (indices -2 .. n: the host's promise; the clamp only keeps a broken promise inside the tables)
-                const int tx = min(max(ix + 2, 0), p.data.nx + 2), ty = min(max(iy + 2, 0), p.data.ny + 2), tz = min(max(iz + 2, 0), p.data.nz + 2);
+            if constexpr (TAB) { // (base taps -2 .. n: the host's promise; the clamp only keeps a broken promise, and the +1 entry, inside the tables)
+                const int tx = min(max(ray_tab_index(ix), 0), ray_tab_last_base(p.data.nx));
+                const int ty = min(max(ray_tab_index(iy), 0), ray_tab_last_base(p.data.ny));
+                const int tz = min(max(ray_tab_index(iz), 0), ray_tab_last_base(p.data.nz));
                 const uint2 ax = tab_x[tx], bx1 = tab_x[tx + 1], ay = tab_y[ty], by1 = tab_y[ty + 1], az = tab_z[tz], bz1 = tab_z[tz + 1];
                 tab_dt.x0 = ax.x; tab_dt.x1 = bx1.x; tab_dt.y0 = ay.x; tab_dt.y1 = by1.x; tab_dt.z0 = az.x; tab_dt.z1 = bz1.x;
                 tab_brick = ax.y + ay.y + az.y;
@@ -362,6 +405,7 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
             if (lane == 0) { atomicAdd(&g_ray_stats[0], 1ull); atomicAdd(&g_ray_stats[1], nd); atomicAdd(&g_ray_stats[2], nl); if (nl) atomicAdd(&g_ray_stats[3], 1ull); }
         }
 #endif
+        // ---- 3. shade: everything of the reference's loop body up to AccumulateLightEnergy -> x = (colour * alpha, alpha)
         if (live) {
             RawTaps<DFMT> dtaps;
             RawTaps<LFMT> ltaps;
@@ -420,7 +464,7 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
             }
         }
 
-        // AccumulateLightEnergy (RaymarchMaterialCommon.usf:82-88) over the ray's 8 samples, in order, in every lane of
+        // ---- 4. exchange and replay: accumulate() over the ray's kRayLanes samples of the trip, in order, in every lane of
         // the ray; the early exit belongs to the full steps only (:75-79). A trip in which no lane of the wave has
         // anything to accumulate (empty space, windowed-out values) needs no exchange.
         bool to_accumulate = x.w >= 0.0f || x.w != x.w;
@@ -439,45 +483,30 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
 #pragma unroll
             for (int t = 0; t < kRayLanes; ++t) {
                 const float4 c = xs[t];
-                if constexpr (!LABELS) {
-                    if (!done && !(c.w < 0.0f)) {
-                        const float om = 1.0f - le3;
-                        le0 = le0 + (c.x * om);
-                        le1 = le1 + (c.y * om);
-                        le2 = le2 + (c.z * om);
-                        le3 = le3 + (c.w * om);
-                        if (le3 > 0.95f && base + t < max_steps) { le3 = 1.0f; done = true; }
-                    }
-                } else if (!done) { // the data step, then the label step (AccumulateOneRaymarchLabelStep: unlit), then the exit test
-                    if (!(c.w < 0.0f)) {
-                        const float om = 1.0f - le3;
-                        le0 = le0 + (c.x * om);
-                        le1 = le1 + (c.y * om);
-                        le2 = le2 + (c.z * om);
-                        le3 = le3 + (c.w * om);
-                    }
+                const bool is_full_step = base + t < max_steps;
+                const bool data_step = !(c.w < 0.0f);
+                // (a slot without a step to take gets no exit test either: a slab stage leaves the state it took over alone)
+                if (done || (!LABELS && !data_step)) continue;
+                if (data_step) accumulate(le, c);
+                if constexpr (LABELS) { // then the label step (AccumulateOneRaymarchLabelStep: unlit)
                     const int lb = s_lb[(threadIdx.x & ~(kRayLanes - 1)) + t];
                     if (lb >= 0) {
                         float4 e;
-                        if (base + t < max_steps) e = s_lab[lb];
+                        if (is_full_step) e = s_lab[lb];
                         else { // the fractional step (once per ray): its own a' with the step 100 * FinalStep
                             const float4 raw = p.lab_colors[lb];
                             const float a = raw.w != 0.0f ? one_minus_pow01_(1.0f - raw.w, 100.0f * final_step) : 0.0f;
                             e = make_float4(raw.x * a, raw.y * a, raw.z * a, a);
                         }
-                        const float om = 1.0f - le3;
-                        le0 = le0 + (e.x * om);
-                        le1 = le1 + (e.y * om);
-                        le2 = le2 + (e.z * om);
-                        le3 = le3 + (e.w * om);
+                        accumulate(le, e);
                     }
-                    if (le3 > 0.95f && base + t < max_steps) { le3 = 1.0f; done = true; }
                 }
+                if (exit_reached(le[3], is_full_step)) { le[3] = 1.0f; done = true; }
             }
             __builtin_amdgcn_wave_barrier();
         }
         if (base + kRayLanes >= n_samples) done = true;
-        // Empty space, wave-wide: when no lane of the wave had anything to sample in this trip, the trips that EVERY marching
+        // ---- 5. leap. Empty space, wave-wide: when no lane of the wave had anything to sample in this trip, the trips that EVERY marching
         // lane would spend the same way — its sample still within its proven-empty range (safe_until), the ray still in its
         // full steps — are taken in one go: their only effect is the positions' additions, performed one by one as before
         // (a position is reached by performing every addition of the ray). 70 % of the benchmark's trips are of this kind.
@@ -506,36 +535,33 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
             eager = renew_wait == 0;
         }
     }
-    if ((SLAB ? mine : valid) && b == 0) reinterpret_cast<float4*>(p.out)[(size_t) j * p.tile_w + i] = make_float4(le0, le1, le2, le3);
+    if ((SLAB ? mine : valid) && b == 0) reinterpret_cast<float4*>(p.out)[(size_t) j * p.tile_w + i] = make_float4(le[0], le[1], le[2], le[3]);
 }
 
-template <int DFMT, int LFMT, int RL, bool LABELS, bool RGB>
-static hipError_t launch_ray3(const RayParams& p, hipStream_t s)
+template <int DFMT, int LFMT, int RL, bool SLAB, bool TAB, bool LABELS, bool RGB>
+static hipError_t launch_lit(const RayParams& p, size_t lds_bytes, hipStream_t s)
 {
     constexpr int BW = 8, BH = RL == 4 ? 8 : 4; // 4 waves of 4x4 / 4x2 rays
     const dim3 grid((p.tile_w + BW - 1) / BW, (p.tile_h + BH - 1) / BH), block(256);
+    if (p.data_addr_mode == ADDR_CLAMP) hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_CLAMP, RL, SLAB, TAB, LABELS, RGB>), grid, block, lds_bytes, s, p);
+    else hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_WRAP, RL, SLAB, TAB, LABELS, RGB>), grid, block, lds_bytes, s, p);
+    return hipGetLastError();
+}
+template <int DFMT, int LFMT, int RL, bool LABELS, bool RGB>
+static hipError_t launch_ray3(const RayParams& p, hipStream_t s)
+{
     // LABELS: the colour-table contributions and the exchanged label bytes, behind the tables (4.5 KiB)
     constexpr size_t lab_bytes = LABELS ? 256 * sizeof(float4) + 256 * sizeof(short) : 0;
     if (p.slab_on) {
         if constexpr (LABELS || RGB) return hipErrorInvalidValue; // (the host refuses slab stages while labels are attached, and on colour handles)
-        else {
-            if (p.data_addr_mode == ADDR_CLAMP) hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_CLAMP, RL, true>), grid, block, 0, s, p);
-            else hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_WRAP, RL, true>), grid, block, 0, s, p);
-            return hipGetLastError();
-        }
+        else return launch_lit<DFMT, LFMT, RL, true, false, false, false>(p, 0, s);
     }
     // the offset tables (k_raymarch_lit TAB): a step of at most one texel along every axis — then no sample's base tap lies below
     // -2 or above n — and tables of at most 16 KiB (six workgroups per CU keep their place)
-    const size_t tab_bytes = (size_t) ((p.data.nx + p.data.ny + p.data.nz + 12 + 1) & ~1) * sizeof(uint2);
+    const size_t tab_bytes = (size_t) ray_tab_entries(p.data.nx, p.data.ny, p.data.nz) * sizeof(uint2);
     const bool tab = p.tab != nullptr && tune(TUNE_RAY_TABLES) != 0 && (float) std::max(p.data.nx, std::max(p.data.ny, p.data.nz)) <= p.steps && tab_bytes <= 16 * 1024;
-    if (tab) {
-        if (p.data_addr_mode == ADDR_CLAMP) hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_CLAMP, RL, false, true, LABELS, RGB>), grid, block, tab_bytes + lab_bytes, s, p);
-        else hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_WRAP, RL, false, true, LABELS, RGB>), grid, block, tab_bytes + lab_bytes, s, p);
-        return hipGetLastError();
-    }
-    if (p.data_addr_mode == ADDR_CLAMP) hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_CLAMP, RL, false, false, LABELS, RGB>), grid, block, lab_bytes, s, p);
-    else hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_WRAP, RL, false, false, LABELS, RGB>), grid, block, lab_bytes, s, p);
-    return hipGetLastError();
+    if (tab) return launch_lit<DFMT, LFMT, RL, false, true, LABELS, RGB>(p, tab_bytes + lab_bytes, s);
+    return launch_lit<DFMT, LFMT, RL, false, false, LABELS, RGB>(p, lab_bytes, s);
 }
 template <int DFMT, int LFMT, bool RGB>
 static hipError_t launch_ray2(const RayParams& p, hipStream_t s)
@@ -617,6 +643,14 @@ hipError_t launch_selftest_opacity_correction(float step0, float step1, unsigned
     return hipGetLastError();
 }
 
+// One ray per lane, 16x16 pixel blocks (tile_pixel): the launch of the intensity, octree and count kernels; an empty tile launches nothing
+static hipError_t launch_pixel_blocks(void (*kernel)(const RayParams), const RayParams& p, hipStream_t s)
+{
+    if (p.tile_w <= 0 || p.tile_h <= 0) return hipSuccess;
+    hipLaunchKernelGGL(kernel, dim3((p.tile_w + 15) / 16, (p.tile_h + 15) / 16), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
 // ---- k_raymarch_intensity: PerformWindowedIntensityRaymarch (WindowedRaymarchMaterials.usf:187-242) ----------------
 // The slice view: the windowed intensity of the first sample the clipping plane leaves. Without a clipping plane that is
 // every ray's first sample, so one ray per lane is the right shape here (no long serial loop to split up).
@@ -627,19 +661,9 @@ __global__ __launch_bounds__(256) void k_raymarch_intensity(const RayParams p)
     if (!tile_pixel(p, i, j, px, py)) return;
     Ray ray;
     cube_setup(p, px, py, ray);
-    const float step_size = 1 / p.steps;
-    const float actual = p.steps * ray.thickness;
-    const float fl = floorf(actual);
-    const int max_steps = (int) fl;
-    const float final_step = actual - fl;
-    const float sv0 = ray.lcv[0] * step_size, sv1 = ray.lcv[1] * step_size, sv2 = ray.lcv[2] * step_size;
-    float pos0 = ray.pos[0], pos1 = ray.pos[1], pos2 = ray.pos[2];
-    if (p.jitter_frame >= 0) {
-        uint32_t rr;
-        rand3d_pcg16(px, py, p.jitter_frame & 7, rr);
-        const float rnd = (float) rr / 65535.0f;
-        pos0 = pos0 - (sv0 * rnd); pos1 = pos1 - (sv1 * rnd); pos2 = pos2 - (sv2 * rnd);
-    }
+    const March m = march_setup(p, ray, px, py, true);
+    const float sv0 = m.sv[0], sv1 = m.sv[1], sv2 = m.sv[2];
+    float pos0 = m.pos[0], pos1 = m.pos[1], pos2 = m.pos[2];
     const float nx = (float) p.data.nx, ny = (float) p.data.ny, nz = (float) p.data.nz;
     auto intensity = [&](float u, float v, float w) -> float { // DataVolume.SampleLevel(Clamp, uvw).r -> clamp(TFPos, 0, 1)
         int ix, iy, iz;
@@ -652,7 +676,7 @@ __global__ __launch_bounds__(256) void k_raymarch_intensity(const RayParams p)
     };
     float4 out = make_float4(0.0f, 0.0f, 0.0f, 0.0f); // didn't hit anything (:241)
     bool hit = false;
-    for (int k = 0; k < max_steps; ++k) {
+    for (int k = 0; k < m.max_steps; ++k) {
         pos0 = pos0 + sv0; pos1 = pos1 + sv1; pos2 = pos2 + sv2;
         const float s0 = saturate_(pos0), s1 = saturate_(pos1), s2 = saturate_(pos2);
         if (!(p.clip_mode && is_clipped(s0, s1, s2, p.cc, p.cd))) {
@@ -662,8 +686,8 @@ __global__ __launch_bounds__(256) void k_raymarch_intensity(const RayParams p)
             break;
         }
     }
-    if (!hit && final_step > 0.0f) {
-        pos0 = pos0 + (sv0 * final_step); pos1 = pos1 + (sv1 * final_step); pos2 = pos2 + (sv2 * final_step);
+    if (!hit && m.final_step > 0.0f) {
+        pos0 = pos0 + (sv0 * m.final_step); pos1 = pos1 + (sv1 * m.final_step); pos2 = pos2 + (sv2 * m.final_step);
         if (!(p.clip_mode && is_clipped(pos0, pos1, pos2, p.cc, p.cd))) {
             const float t = intensity(pos0, pos1, pos2);
             out = make_float4(t, t, t, 1.0f);
@@ -674,14 +698,11 @@ __global__ __launch_bounds__(256) void k_raymarch_intensity(const RayParams p)
 
 hipError_t launch_raymarch_intensity(const RayParams& p, hipStream_t s)
 {
-    if (p.tile_w <= 0 || p.tile_h <= 0) return hipSuccess;
-    const dim3 grid((p.tile_w + 15) / 16, (p.tile_h + 15) / 16), block(256);
     switch (p.data.fmt) {
-        case FMT_U8: hipLaunchKernelGGL(k_raymarch_intensity<FMT_U8>, grid, block, 0, s, p); break;
-        case FMT_U16: hipLaunchKernelGGL(k_raymarch_intensity<FMT_U16>, grid, block, 0, s, p); break;
-        default: hipLaunchKernelGGL(k_raymarch_intensity<FMT_F32>, grid, block, 0, s, p); break;
+        case FMT_U8: return launch_pixel_blocks(k_raymarch_intensity<FMT_U8>, p, s);
+        case FMT_U16: return launch_pixel_blocks(k_raymarch_intensity<FMT_U16>, p, s);
+        default: return launch_pixel_blocks(k_raymarch_intensity<FMT_F32>, p, s);
     }
-    return hipGetLastError();
 }
 
 // ---- Octree render mode (experimental in the reference) -------------------------------------------------------------
@@ -735,27 +756,16 @@ __global__ __launch_bounds__(256) void k_raymarch_octree(const RayParams p)
     if (!tile_pixel(p, i, j, px, py)) return;
     Ray ray;
     cube_setup(p, px, py, ray);
-    const float step_size = 1 / p.steps;
-    const float actual = p.steps * ray.thickness;
-    const float fl = floorf(actual);
-    const int max_steps = (int) fl;
-    const float final_step = actual - fl;
-    const float sv0 = ray.lcv[0] * step_size, sv1 = ray.lcv[1] * step_size, sv2 = ray.lcv[2] * step_size;
-    const float step_world = 100.0f * step_size;
-    float pos0 = ray.pos[0], pos1 = ray.pos[1], pos2 = ray.pos[2];
-    if (p.jitter_frame >= 0) {
-        uint32_t rr;
-        rand3d_pcg16(px, py, p.jitter_frame & 7, rr);
-        const float rnd = (float) rr / 65535.0f;
-        pos0 = pos0 - (sv0 * rnd); pos1 = pos1 - (sv1 * rnd); pos2 = pos2 - (sv2 * rnd);
-    }
+    const March m = march_setup(p, ray, px, py, true);
+    const float sv0 = m.sv[0], sv1 = m.sv[1], sv2 = m.sv[2];
+    float pos0 = m.pos[0], pos1 = m.pos[1], pos2 = m.pos[2];
     const float ow = (float) p.oct_dims[0], oh = (float) p.oct_dims[1], od = (float) p.oct_dims[2], data_depth = (float) p.data.nz;
-    float le0 = 0.0f, le1 = 0.0f, le2 = 0.0f, le3 = 0.0f;
-    for (int k = 0; k <= max_steps; ++k) {
-        if (k < max_steps) { pos0 = pos0 + sv0; pos1 = pos1 + sv1; pos2 = pos2 + sv2; }
+    float le[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (int k = 0; k <= m.max_steps; ++k) {
+        if (k < m.max_steps) { pos0 = pos0 + sv0; pos1 = pos1 + sv1; pos2 = pos2 + sv2; }
         else {
-            if (!(final_step > 0.0f)) break;
-            pos0 = pos0 + (sv0 * final_step); pos1 = pos1 + (sv1 * final_step); pos2 = pos2 + (sv2 * final_step);
+            if (!(m.final_step > 0.0f)) break;
+            pos0 = pos0 + (sv0 * m.final_step); pos1 = pos1 + (sv1 * m.final_step); pos2 = pos2 + (sv2 * m.final_step);
         }
         if (p.clip_mode && is_clipped(pos0, pos1, pos2, p.cc, p.cd)) continue;
         // int3 VoxelPos = float3(x * W, y * H, (z * DataDepth / OctreeDepth0) * OctreeDepth) (:150): truncation; Load outside -> 0
@@ -770,23 +780,13 @@ __global__ __launch_bounds__(256) void k_raymarch_octree(const RayParams p)
         if ((tpos < 0.0f && p.win.low_cutoff > 0.0f) || (tpos > 1.0f && p.win.high_cutoff > 0.0f)) continue;
         const float4 cs = sample_tf(s_tf, tpos);
         const float a_sat = saturate_(cs.w);
-        const float a = 1.0f - pow_(1.0f - a_sat, step_world);
-        const float om = 1.0f - le3; // AccumulateLightEnergy
-        le0 = le0 + ((cs.x * a) * om);
-        le1 = le1 + ((cs.y * a) * om);
-        le2 = le2 + ((cs.z * a) * om);
-        le3 = le3 + (a * om);
-        if (k < max_steps && le3 > 0.95f) { le3 = 1.0f; break; }
+        const float a = 1.0f - pow_(1.0f - a_sat, m.step_world);
+        accumulate(le, make_float4(cs.x * a, cs.y * a, cs.z * a, a)); // ((cs * a) * om, as the lit march's samples)
+        if (exit_reached(le[3], k < m.max_steps)) { le[3] = 1.0f; break; }
     }
-    reinterpret_cast<float4*>(p.out)[(size_t) j * p.tile_w + i] = make_float4(le0, le1, le2, le3);
+    reinterpret_cast<float4*>(p.out)[(size_t) j * p.tile_w + i] = make_float4(le[0], le[1], le[2], le[3]);
 }
-hipError_t launch_raymarch_octree(const RayParams& p, hipStream_t s)
-{
-    if (p.tile_w <= 0 || p.tile_h <= 0) return hipSuccess;
-    const dim3 grid((p.tile_w + 15) / 16, (p.tile_h + 15) / 16), block(256);
-    hipLaunchKernelGGL(k_raymarch_octree, grid, block, 0, s, p);
-    return hipGetLastError();
-}
+hipError_t launch_raymarch_octree(const RayParams& p, hipStream_t s) { return launch_pixel_blocks(k_raymarch_octree, p, s); }
 
 // Nominal samples: sum over rays of floor(Steps*thickness) + [frac > 0].
 __global__ __launch_bounds__(256) void k_count_samples(const RayParams p)
@@ -797,22 +797,14 @@ __global__ __launch_bounds__(256) void k_count_samples(const RayParams p)
     if (valid) {
         Ray ray;
         cube_setup(p, px, py, ray);
-        const float actual = p.steps * ray.thickness;
-        const float fl = floorf(actual);
-        n = (unsigned long long) (int) fl + ((actual - fl) > 0.0f ? 1ull : 0ull);
+        n = (unsigned long long) march_setup(p, ray, px, py, true).n_samples;
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) n += __shfl_down(n, o, 64);
     if ((threadIdx.x & 63) == 0 && n) atomicAdd(p.sample_counter, n);
 }
 
-hipError_t launch_count_samples(const RayParams& p, hipStream_t s)
-{
-    if (p.tile_w <= 0 || p.tile_h <= 0) return hipSuccess;
-    const dim3 grid((p.tile_w + 15) / 16, (p.tile_h + 15) / 16), block(256);
-    hipLaunchKernelGGL(k_count_samples, grid, block, 0, s, p);
-    return hipGetLastError();
-}
+hipError_t launch_count_samples(const RayParams& p, hipStream_t s) { return launch_pixel_blocks(k_count_samples, p, s); }
 
 #endif // TBRM_RAY_RGB_UNIT
 
