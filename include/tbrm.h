@@ -186,7 +186,11 @@ TBRM_API int tbrm_device_count(int* out_count);   /* TBRM_ERR_NO_DEVICE when the
  * wait for each other, bits 3 / 4 skip buffer hazards — WRONG light volumes —; bit 1 prints per-tile time stamps at tbrm_flush,
  * bit 2 the host's time per operator phase, bit 5 leaves out the events behind tbrm_last_gpu_time_ms), occ_dual (1 = the two
  * axis passes of a light share one occlusion launch — their sampling positions are the same, LightingShaders.cpp:114-124 —,
- * 0 = one launch per pass), sweep_chain (4 = up to four consecutive sweep passes of an operator share ONE launch —
+ * 0 = one launch per pass), occ_run (4 = a workgroup of that launch takes up to four z-adjacent live units of one column in a row
+ * and sets up once what they share — the same voxels, the same bits; at most 64; 1 = one unit per workgroup. The run list is
+ * cut by one workgroup that keeps a 64-bit word per column of units and 64 unit layers in LDS: a light volume with more than 4096
+ * such words — (x / 16) * (y / 16) * ceil(z / 512), e.g. 1024 x 1024 x 1024 — takes the per-unit form, and out[15] stands still),
+ * sweep_chain (4 = up to four consecutive sweep passes of an operator share ONE launch —
  * k_light_sweep_chain: the next pass's tiles take their tickets behind this pass's and start as its tiles retire, ordered brick
  * layer by brick layer through progress words; 1 = one launch per pass), sweep_timeout_ms (0 = a sweep tile waits 2 s of wall time for a neighbour's hand-off word before it
  * gives up and the handle reports the light volume undefined; < 0 = not at all: a test hook), sweep_epoch_preset (0; > 0: a
@@ -433,7 +437,9 @@ TBRM_API int tbrm_sweep_launches(const tbrm_resources* res, uint64_t* out);
  * out[12] device-memory management calls (hipMalloc / hipHostMalloc / hipFree / hipMemGetInfo / event and stream creation) made
  * INSIDE light operators since creation, out[13] host-side waits for a stream made inside them — both stand still once the handle
  * is reserved (tbrm_resources_reserve) and the scene stays inside the reserved envelope; out[14] sweep launches that ran several
- * axis passes at once (k_light_sweep_chain: the next pass fills while the one before drains; tunable sweep_chain); out[15] reserved (0). */
+ * axis passes at once (k_light_sweep_chain: the next pass fills while the one before drains; tunable sweep_chain); out[15] occlusion
+ * units that ran as the second or later unit of a run of z-adjacent units (tunable occ_run; 0 with occ_run = 1; never waits:
+ * the launches over a run list that is still being built on the device are added once it is — after tbrm_flush the count is exact). */
 #define TBRM_PATH_COUNTERS 16
 TBRM_API int tbrm_path_counters(const tbrm_resources* res, uint64_t out[TBRM_PATH_COUNTERS]);
 /* The factor cache of the light operators (no counterpart in the reference, invisible in the results). The expensive half

@@ -37,7 +37,7 @@ const TunableDef kTunables[TUNE_COUNT] = {
     {"light_batching", 1}, {"share_grid", 1}, {"ray_wave_skip", -1}, {"ray_lanes", 0}, {"chain_fast_loop", 1},
     {"chain_rect_planes", 1}, {"occ_overlap", 2}, {"light_sweep", 1}, {"sweep_prefetch", 0}, {"stream_priority", 0}, {"sweep_debug", 0},
     {"sweep_timeout_ms", 0}, {"fast_window_div", 1}, {"slab_sweep", 0}, {"gpu_timing", 1}, {"ray_tables", 1}, {"sweep_epoch_preset", 0}, {"occ_dual", 1}, {"sweep_chain", 4}, {"ray_xcd_rows", 1},
-    {"ray_labels", 0}, {"stats_groups", 0},
+    {"ray_labels", 0}, {"stats_groups", 0}, {"occ_run", 4},
 };
 struct TunableStore {
     std::atomic<int> v[TUNE_COUNT];
@@ -792,6 +792,7 @@ int tbrm_path_counters(const tbrm_resources* r, uint64_t out[TBRM_PATH_COUNTERS]
     out[12] = r->alloc_calls;
     out[13] = r->sync_calls;
     out[14] = r->chain_launches;
+    out[15] = tbrm_host::units_in_runs(r);
     return TBRM_OK;
 }
 

@@ -79,12 +79,53 @@ static void free_lists(BlockLists* l)
     delete l;
 }
 
+// tbrm_path_counters [15]: a run list's launches each ran (live units - runs) units behind the first of their run — a number
+// k_occ_runs leaves in pinned memory (count_host[1]). A list that goes, or is cut anew, hands its share to the handle first.
+static void retire_run_list(tbrm_resources* r, BlockLists* l)
+{
+    if (l->run_launches) r->run_followers += l->run_launches * (uint64_t) std::max(l->count_host[1], 0);
+    l->run_launches = 0;
+    l->run_len = 0;
+}
+
 void release_block_lists(tbrm_resources* r)
 {
-    for (BlockLists* l : r->block_lists) free_lists(l);
+    for (BlockLists* l : r->block_lists) {
+        if (l->run_launches) (void) hipEventSynchronize(l->ev_done); // (tbrm_path_counters [15] counts since creation: the share of a list that goes stays)
+        retire_run_list(r, l);
+        free_lists(l);
+    }
     r->block_lists.clear();
     for (BlockLists* l : r->spare_lists) free_lists(l);
     r->spare_lists.clear();
+}
+
+// (never waits: a list whose k_occ_runs has not finished yet — the event recorded behind it has not fired — adds its share later)
+uint64_t units_in_runs(const tbrm_resources* r)
+{
+    uint64_t n = r->run_followers;
+    for (const BlockLists* l : r->block_lists)
+        if (l->run_launches) {
+            if (hipEventQuery(l->ev_done) != hipSuccess) { (void) hipGetLastError(); continue; }
+            n += l->run_launches * (uint64_t) std::max(l->count_host[1], 0);
+        }
+    return n;
+}
+
+// The run list of a dual launch's units cut for runs of up to `len`: what the occlusion launch and k_occ_runs are handed. A list
+// cut for another length (the occ_run tunable changed) is cut anew, on the occlusion stream behind the launches that walk it.
+bool run_list_for(tbrm_resources* r, BlockLists* l, int len, OccRuns* out, bool* build)
+{
+    if (!l->runs) return false;
+    *build = l->run_len != len;
+    if (*build && l->run_launches) { // (the number the old cut left for units_in_runs)
+        ++r->sync_calls;
+        (void) hipEventSynchronize(l->ev_done);
+        retire_run_list(r, l);
+    }
+    l->run_len = len;
+    *out = OccRuns{len, l->runs, l->count, l->count_host};
+    return true;
 }
 
 static void drain(tbrm_resources* r)
@@ -94,15 +135,17 @@ static void drain(tbrm_resources* r)
     if (r->occ_stream) (void) hipStreamSynchronize(r->occ_stream);
 }
 
+// (the units of a dual launch — no ranks — have their run list behind the work list: units + 8 * kOccRunMax words, OccRuns)
 static BlockLists* allocate_lists(size_t blocks, bool with_ranks)
 {
     BlockLists* l = new BlockLists{};
-    bool ok = hipMalloc((void**) &l->flags, blocks) == hipSuccess && hipMalloc((void**) &l->list, blocks * sizeof(uint32_t)) == hipSuccess &&
-              hipMalloc((void**) &l->count, 16 * sizeof(int)) == hipSuccess;
-    if (with_ranks)
-        ok = ok && hipMalloc((void**) &l->slot, blocks * sizeof(int32_t)) == hipSuccess &&
-             hipHostMalloc((void**) &l->count_host, sizeof(int), hipHostMallocDefault) == hipSuccess &&
-             hipEventCreateWithFlags(&l->ev_done, hipEventDisableTiming) == hipSuccess;
+    const size_t list_words = with_ranks ? blocks : 2 * blocks + 8 * kOccRunMax;
+    bool ok = hipMalloc((void**) &l->flags, blocks) == hipSuccess && hipMalloc((void**) &l->list, list_words * sizeof(uint32_t)) == hipSuccess &&
+              hipMalloc((void**) &l->count, 16 * sizeof(int)) == hipSuccess &&
+              hipHostMalloc((void**) &l->count_host, 2 * sizeof(int), hipHostMallocDefault) == hipSuccess &&
+              hipEventCreateWithFlags(&l->ev_done, hipEventDisableTiming) == hipSuccess;
+    if (with_ranks) ok = ok && hipMalloc((void**) &l->slot, blocks * sizeof(int32_t)) == hipSuccess;
+    else if (ok) l->runs = l->list + blocks;
     if (!ok) {
         (void) hipGetLastError();
         free_lists(l);
@@ -133,7 +176,7 @@ static void prune(tbrm_resources* r)
     std::sort(r->block_lists.begin(), r->block_lists.end(), [](const BlockLists* a, const BlockLists* b) { return a->last_use > b->last_use; });
     for (BlockLists* l : r->block_lists) {
         if (l->users > 0 || l->last_use > r->block_lists_op_floor || keep.size() < kMaxLists / 2) keep.push_back(l); // (never the ones the operator being planned holds)
-        else free_lists(l);
+        else { retire_run_list(r, l); free_lists(l); }
     }
     // (units lists whose passes' lists went: ids are never reused, so they are merely never found again)
     r->block_lists.swap(keep);
@@ -173,6 +216,7 @@ static BlockLists* new_lists(tbrm_resources* r, size_t blocks, bool with_ranks)
             for (BlockLists* c : r->block_lists)
                 if (free_to_take(c) && (!l || c->last_use < l->last_use) && op_finished(r, c->last_read_op)) l = c;
         if (l) {
+            retire_run_list(r, l); // (op_finished: its kernels are done)
             l->sig.clear();
             l->a_id = l->b_id = 0;
             l->enqueued = false;
@@ -180,13 +224,13 @@ static BlockLists* new_lists(tbrm_resources* r, size_t blocks, bool with_ranks)
     }
     if (!l) {
         prune(r);
-        count_alloc(r, with_ranks ? 5 : 3, "new block lists (no spare or quiet list to take)");
+        count_alloc(r, with_ranks ? 6 : 5, "new block lists (no spare or quiet list to take)");
         l = allocate_lists(blocks, with_ranks);
         if (!l) return nullptr;
         r->block_lists.push_back(l);
     }
     l->blocks = blocks;
-    if (l->count_host) *l->count_host = 0;
+    l->count_host[0] = l->count_host[1] = 0;
     l->empty_gen = r->empty_gen;
     l->id = ++r->block_lists_serial;
     l->last_use = l->id;

@@ -166,6 +166,21 @@ struct DualOcc {
     int on;
     DualPass pass[2];
 };
+// The run list of a dual launch (k_occ_runs, tbrm_light_kernels.hip): the live units of the launch's work list as runs of up to
+// `len` z-adjacent units of one column, one word each — (length - 1) << kRunLenShift | first unit — in the order the workgroups
+// take them: all runs of `len` units first, then the shorter ones by descending length (the last workgroups to start are the
+// shortest), each length class dealt to the 8 XCDs in eighths (spatial neighbours behind one L2) and padded with kRunNone to whole
+// rounds of 8. count[1] is the number of words.
+constexpr int kOccRunMax = 64;             // longest run (a run never crosses a multiple of 64 units in z)
+constexpr int kRunLenShift = 26;           // a launch of more than 2^26 units takes the per-unit form
+constexpr uint32_t kRunNone = 0xffffffffu; // padding: the workgroup has nothing to do
+constexpr size_t kRunMaskWords = 4096;     // k_occ_runs holds a 64-bit liveness word per column and 64 units of z in LDS: larger launches take the per-unit form
+struct OccRuns {
+    int len;                 // TUNE_OCC_RUN, clamped to kOccRunMax
+    uint32_t* list;          // k_occ_runs writes, k_light_occlusion_runs reads: room for units + 8 * kOccRunMax words
+    int* count;              // BlockLists::count (16 ints)
+    int* count_host;         // pinned: [1] units that are not the first of their run (tbrm_path_counters out[15])
+};
 // k_light_sweep (tbrm_light_sweep.hip): one launch advances every 32x32 tile of the slice plane through a whole span of
 // slices. The previous-slice taps of a pass lie on ONE side of the pixel per plane axis (the constant PrevPixelOffset,
 // AddDirLightShader.usf:81-82), so a tile depends on at most three neighbours — the ones towards the light — and the tiles
@@ -375,6 +390,8 @@ enum Tunable : int {
                              // it has a colour alpha > 0 (a test hook: the same frame by the other kernel); 0: only when one does
     TUNE_STATS_GROUPS,       // > 0: the statistics kernels (tbrm_stats_kernels.hip) launch at most this many workgroups, so that a wave
                              // takes many bricks of even a small volume (a test hook and an A/B switch); 0: sized to the device
+    TUNE_OCC_RUN,            // dual occlusion launches: a workgroup takes up to this many z-adjacent live units of one column in a row and
+                             // keeps what they share (k_light_occlusion_runs; at most kOccRunMax); 1: one unit per workgroup (the A/B switch)
     TUNE_COUNT
 };
 int tune(Tunable t);
@@ -389,8 +406,10 @@ size_t chunk_lds_bytes(const ChunkParams& p, int mode, int lv_fmt);
 size_t occlusion_lds_bytes(const ChunkParams& p); // dynamic LDS of an occlusion workgroup (the bricks it stages)
 constexpr int kPlaneGuard = 4096; // floats of slack on both sides of every plane/occlusion buffer (16-byte row copies overrun rows)
 hipError_t launch_occ_flags(const ChunkParams& p, int mode, int n_chunks, hipStream_t s); // + the work lists
-hipError_t launch_light_occlusion(const ChunkParams& p, int mode, hipStream_t s, const DualOcc* dual = nullptr);
+hipError_t launch_light_occlusion(const ChunkParams& p, int mode, hipStream_t s, const DualOcc* dual = nullptr, const OccRuns* runs = nullptr); // runs: a dual launch in run form
 hipError_t launch_unit_flags(const ChunkParams& pc, const DualOcc& d, hipStream_t s); // + the units' work list (pc: the virtual pass along the third axis)
+bool occ_runs_apply(const ChunkParams& pc);                                          // may a dual launch over pc's units take the run form?
+hipError_t launch_occ_runs(const ChunkParams& pc, const OccRuns& runs, hipStream_t s); // the run list of the units' flags (pc.occ_flags_out)
 hipError_t launch_light_chain(const ChunkParams& p, int mode, int lv_fmt, hipStream_t s);
 hipError_t launch_light_sweep(const ChunkParams& p, const SweepParams& q, int mode, hipStream_t s);
 hipError_t launch_light_sweep_chain(const SweepChainArgs& c, int mode, hipStream_t s); // PASS_ADD / PASS_CHANGE, UNORM8 light volumes

@@ -239,8 +239,8 @@ int enqueue_dual_occlusion(tbrm_resources* r, const PassPlan& pa, const PassPlan
         P.fs_slot = plan.lists->slot;
         P.flags = plan.lists->flags;
     }
+    pc.occ_flags_out = ul->flags;
     if (!ul->enqueued) {
-        pc.occ_flags_out = ul->flags;
         pc.occ_list_out = ul->list;
         pc.occ_count_out = ul->count;
         pc.occ_slot_out = nullptr;
@@ -249,11 +249,21 @@ int enqueue_dual_occlusion(tbrm_resources* r, const PassPlan& pa, const PassPlan
         ul->enqueued = true;
         ++r->lists_launches;
     }
+    // run form (tunable occ_run > 1): a workgroup per run of z-adjacent live units; the run list is kept with the units' list
+    const int run_len = std::min(tune(TUNE_OCC_RUN), kOccRunMax);
+    OccRuns runs{};
+    bool build_runs = false;
+    const bool in_runs = run_len > 1 && occ_runs_apply(pc) && run_list_for(r, ul, run_len, &runs, &build_runs);
+    if (in_runs && build_runs) {
+        HIP_TRY(launch_occ_runs(pc, runs, s));
+        HIP_TRY(hipEventRecord(ul->ev_done, s));
+    }
     pc.occ_flags = nullptr;
     pc.occ_list = ul->list;
     pc.occ_count = ul->count;
     pc.occ_grid_cap = 0;
-    HIP_TRY(launch_light_occlusion(pc, pa.occ_mode, s, &d));
+    HIP_TRY(launch_light_occlusion(pc, pa.occ_mode, s, &d, in_runs ? &runs : nullptr));
+    if (in_runs) ++ul->run_launches;
     ++r->dual_launches;
     for (const PassPlan* plan : plans)
         if (int e2 = occlusion_recorded(r, *plan, s)) return e2;

@@ -658,8 +658,320 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TBRM_OCC_WA
   }
 }
 
+// ---- k_light_occlusion_runs: a dual launch whose workgroups take RUNS of z-adjacent live units ----------------------------------
+// Units, staging, block lists, ranks, factor layout and every voxel's arithmetic are k_light_occlusion<..., 2, DUAL>'s. A
+// workgroup takes one word of the run list (tbrm_internal.h OccRuns): up to occ_run live units of one column, bottom to top.
+// What is a function of the column is set up once per run — the alpha pair table, every thread's u / v taps, weights, validity
+// bits and in-plane tap offsets, the x / y brick range with the x / y part of the staged bricks' indices, the invariant part of
+// the factor-store addresses — and what changes from a unit to the one above it per unit: the eight slice-table entries (two
+// sets, taken in turn, so that a unit's tables are written while the one before is still being read), the z brick range with the
+// staged / interior decision, the staging copy (one z layer of bricks at a time: no index list per unit) and the block ranks.
+// Two barriers per unit instead of four. The texel plane a unit's last slice leaves in registers serves the first slice of
+// the next unit where the texel index continues.
+struct OccThreadTaps {
+    uint32_t o00, o10, o01, o11; // in-plane offsets of the four taps (u, v): bit0 = u tap, bit1 = v tap
+    float fu, fv, u, v;
+    int ok;                      // bits 0..3: tap (u, v) inside the volume; bit 4: u and v equal their saturate (the Add shader's guard)
+};
+
+template <int DFMT, int MODE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TBRM_OCC_WAVES_PER_EU, 8))) void k_light_occlusion_runs(const ChunkParams p, int lds_budget_bytes, const DualOcc d, const uint32_t* __restrict__ runs,
+                                                                                                                                   const int* __restrict__ run_count)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int NS = (MODE == PASS_ADD || MODE == PASS_CHANGE_ONE) ? 1 : 2;
+    constexpr bool GUARD = MODE == PASS_ADD || MODE == PASS_ADD2;
+    constexpr int ESZ = DFMT == FMT_U8 ? 1 : (DFMT == FMT_U16 ? 2 : 4);
+    constexpr int PIECES = 512 * ESZ / 16; // 16-byte pieces of a brick
+    __shared__ float2 s_alpha[257];
+    __shared__ float s_w[2][NS][kOccDepth], s_f[2][NS][kOccDepth]; // [unit parity][stream][slice]
+    __shared__ int s_i[2][NS][kOccDepth], s_flags[2][NS][kOccDepth];
+    __shared__ uint32_t s_o0[2][NS][kOccDepth], s_o1[2][NS][kOccDepth];
+    __shared__ int s_zend[2][NS * 2], s_xyend[NS * 4];
+    __shared__ uint32_t s_brick_xy[kOccMaxBricks];
+
+    if ((int) blockIdx.x >= run_count[1]) return;
+    const uint32_t word = runs[blockIdx.x];
+    if (word == kRunNone) return;
+    const int id = (int) (word & ((1u << kRunLenShift) - 1u)), len = (int) (word >> kRunLenShift) + 1;
+    const int gx = id % p.occ_blocks_x, gy = (id / p.occ_blocks_x) % p.occ_blocks_y, gz0 = id / (p.occ_blocks_x * p.occ_blocks_y);
+    const int px0 = gx * kOccTile, py0 = gy * kOccTile;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int px = px0 + (wave & 1) * 8 + (lane & 7);
+    const int py = py0 + (wave >> 1) * 8 + (lane >> 3);
+    const bool pixel_ok = px < p.W && py < p.H;
+
+    // ---- once per run ----
+    {
+        const float a_t = p.tf[threadIdx.x].w, a_n = p.tf[min((int) threadIdx.x + 1, 255)].w;
+        s_alpha[threadIdx.x + 1] = make_float2(a_t, a_n);
+        if (threadIdx.x == 0) s_alpha[0] = make_float2(a_t, a_t);
+    }
+    if (threadIdx.x >= 64 && threadIdx.x < 64 + NS * 4) { // base tap of the first / last pixel along x and y, one lane each
+        const int t = threadIdx.x - 64, si = t >> 2, a = (t >> 1) & 1, e = t & 1;
+        const ChunkStream& s = si == 0 ? p.a : p.r;
+        const int pxl = min(px0 + kOccTile, p.W) - 1, pyl = min(py0 + kOccTile, p.H) - 1;
+        const int end = a == 0 ? (e ? pxl : px0) : (e ? pyl : py0);
+        const float c = (((float) (uint32_t) end + 0.5f) / (float) (uint32_t) (a == 0 ? p.lv_dims[0] : p.lv_dims[1])) + (a == 0 ? s.uvw_off[0] : s.uvw_off[1]);
+        int i0;
+        float f;
+        texel_split(c, (float) (a == 0 ? p.data.nx : p.data.ny), i0, f);
+        s_xyend[t] = i0;
+    }
+    __syncthreads();
+    // the x / y part of the brick range the column's samples can touch (union over the streams), the same for every thread
+    int b0x, b0y, nbx, nby;
+    bool border_xy = false;
+    {
+        int b0[2], nb[2];
+        int lo[2] = {INT32_MAX, INT32_MAX}, hi[2] = {INT32_MIN, INT32_MIN};
+#pragma unroll
+        for (int t = 0; t < NS * 4; ++t) {
+            const int a = (t >> 1) & 1, i0 = __builtin_amdgcn_readfirstlane(s_xyend[t]);
+            lo[a] = min(lo[a], i0);
+            hi[a] = max(hi[a], i0 + 1);
+        }
+        const int bn[2] = {p.data.bnx, p.data.bnxy / p.data.bnx}, dn[2] = {p.data.nx, p.data.ny};
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            const int b_lo = max(lo[a] >> 3, 0), b_hi = min(hi[a] >> 3, bn[a] - 1);
+            b0[a] = b_lo;
+            nb[a] = max(b_hi - b_lo + 1, 0);
+            border_xy = border_xy || lo[a] < 0 || hi[a] >= dn[a];
+        }
+        b0x = b0[0]; b0y = b0[1]; nbx = nb[0]; nby = nb[1];
+    }
+    const int nxy = nbx * nby;
+    if ((int) threadIdx.x < min(nxy, kOccMaxBricks)) // x / y part of every staged brick's index (read behind the first unit's barrier)
+        s_brick_xy[threadIdx.x] = (uint32_t) ((b0y + (int) threadIdx.x / nbx) * p.data.bnx + (b0x + (int) threadIdx.x % nbx));
+
+    // a thread's taps in the plane: offsets inside the staged block (STAGED_FORM) or in the bricked volume
+    auto thread_taps = [&](int si, bool staged_form) -> OccThreadTaps {
+        const ChunkStream& s = si == 0 ? p.a : p.r;
+        OccThreadTaps t;
+        // GetUVW(pos, res) + UVWOffset (AddDirLightShader.usf:85): the two in-plane components
+        t.u = (((float) (uint32_t) px + 0.5f) / (float) (uint32_t) p.lv_dims[0]) + s.uvw_off[0];
+        t.v = (((float) (uint32_t) py + 0.5f) / (float) (uint32_t) p.lv_dims[1]) + s.uvw_off[1];
+        const AxisTaps tu = axis_taps(t.u, p.data.nx), tv = axis_taps(t.v, p.data.ny);
+        t.fu = tu.f;
+        t.fv = tv.f;
+        // (k_light_occlusion's voff: clamped into the volume and the staged block; staged_off's brick index * 512 + in-brick part)
+        auto off_x = [&](int c) -> uint32_t {
+            c = min(max(c, 0), p.data.nx - 1);
+            if (!staged_form) return brick_off_x(c);
+            return (uint32_t) (min(max(c >> 3, b0x), b0x + nbx - 1) - b0x) * 512u + (uint32_t) (c & 7);
+        };
+        auto off_y = [&](int c) -> uint32_t {
+            c = min(max(c, 0), p.data.ny - 1);
+            if (!staged_form) return brick_off_y(c, p.data.bnx);
+            return (uint32_t) (min(max(c >> 3, b0y), b0y + nby - 1) - b0y) * (uint32_t) nbx * 512u + ((uint32_t) (c & 7) << 3);
+        };
+        const uint32_t u0 = off_x(tu.i0), u1 = off_x(tu.i0 + 1), v0 = off_y(tv.i0), v1 = off_y(tv.i0 + 1);
+        t.o00 = u0 + v0; t.o10 = u1 + v0; t.o01 = u0 + v1; t.o11 = u1 + v1;
+        const bool guard_uv = (t.u == saturate_(t.u)) && (t.v == saturate_(t.v));
+        t.ok = ((tu.ok0 && tv.ok0) ? 1 : 0) | ((tu.ok1 && tv.ok0) ? 2 : 0) | ((tu.ok0 && tv.ok1) ? 4 : 0) | ((tu.ok1 && tv.ok1) ? 8 : 0) | (guard_uv ? 16 : 0);
+        return t;
+    };
+    // what a thread carries through the run per stream (two named sets, not arrays: they stay in registers)
+    struct StreamRegs {
+        uint32_t o00, o10, o01, o11;
+        float fu, fv;
+        int ok;
+        float lo, hi; // texel planes of the footprint (4 taps at one z, filtered along x and y) around the last slice taken
+        int held;     // z texel index of `lo`; `hi` is the plane after it
+    };
+    auto stream_regs = [&](int si) __attribute__((always_inline)) -> StreamRegs {
+        const OccThreadTaps t = thread_taps(si, true);
+        return StreamRegs{t.o00, t.o10, t.o01, t.o11, t.fu, t.fv, t.ok, 0.0f, 0.0f, INT32_MIN / 2};
+    };
+    StreamRegs regs_a = stream_regs(0), regs_r = NS == 2 ? stream_regs(1) : StreamRegs{};
+    // where a thread's factors go in the two passes' stores, as far as the column decides it: the pass's block is
+    // fs_slot[inv_idx + what the unit adds], the voxel's place in it inv_off + what the unit adds (k_light_occlusion: out2)
+    int inv_idx[2], inv_off[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const DualPass& P = d.pass[k];
+        if (P.axis == 2) {
+            inv_idx[k] = (py >> 4) * P.blocks_x + (px >> 4);
+            inv_off[k] = (py & 15) * 16 + (px & 15);
+        } else {
+            const int pa = P.axis == 0 ? px : py, pu = P.axis == 0 ? py : px; // (the pass's rows are z)
+            const int ks = (pa - P.start) * P.dir;
+            inv_idx[k] = (ks >> 3) * P.blocks_y * P.blocks_x + (pu >> 4);
+            inv_off[k] = (ks & 7) * 256 + (pu & 15);
+        }
+    }
+    bool steps_nonneg = true;
+#pragma unroll
+    for (int si = 0; si < NS; ++si) steps_nonneg = steps_nonneg && d.pass[0].step100[si] >= 0.0f && d.pass[1].step100[si] >= 0.0f;
+
+    // ---- per unit ----
+    for (int ui = 0; ui < len; ++ui) {
+        const int par = ui & 1;
+        const int k0 = (gz0 + ui) * kOccDepth;
+        const int nk = min(kOccDepth, p.n_steps - k0);
+        if (threadIdx.x < NS * kOccDepth) { // z taps of each slice of the unit (wave-uniform values)
+            const int si = threadIdx.x / kOccDepth, q = threadIdx.x % kOccDepth;
+            const ChunkStream& s = si == 0 ? p.a : p.r;
+            const int j = min(k0 + q, p.n_steps - 1);
+            const float w = (((float) (uint32_t) j + 0.5f) / (float) (uint32_t) p.lv_dims[2]) + s.uvw_off[2];
+            const AxisTaps t = axis_taps(w, p.data.nz);
+            s_w[par][si][q] = w; s_f[par][si][q] = t.f; s_i[par][si][q] = t.i0;
+            s_flags[par][si][q] = (t.ok0 ? 1 : 0) | (t.ok1 ? 2 : 0) | ((w == saturate_(w)) ? 4 : 0);
+        }
+        if (threadIdx.x >= 64 && threadIdx.x < 64 + NS * 2) { // base tap of the unit's first / last slice
+            const int t = threadIdx.x - 64, si = t >> 1, e = t & 1;
+            const ChunkStream& s = si == 0 ? p.a : p.r;
+            const int end = e ? k0 + nk - 1 : k0;
+            const float c = (((float) (uint32_t) end + 0.5f) / (float) (uint32_t) p.lv_dims[2]) + s.uvw_off[2];
+            int i0;
+            float f;
+            texel_split(c, (float) p.data.nz, i0, f);
+            s_zend[par][t] = i0;
+        }
+        __syncthreads(); // (also: every thread is done with the bricks of the unit before)
+        bool staged, interior;
+        int b0z, nbz;
+        {
+            int zlo = INT32_MAX, zhi = INT32_MIN;
+#pragma unroll
+            for (int t = 0; t < NS * 2; ++t) {
+                const int i0 = __builtin_amdgcn_readfirstlane(s_zend[par][t]);
+                zlo = min(zlo, i0);
+                zhi = max(zhi, i0 + 1);
+            }
+            const int b_lo = max(zlo >> 3, 0), b_hi = min(zhi >> 3, ((p.data.nz + 7) >> 3) - 1);
+            b0z = b_lo;
+            nbz = max(b_hi - b_lo + 1, 0);
+            const int count = nxy * nbz;
+            staged = count > 0 && count <= kOccMaxBricks && count * 512 * ESZ <= lds_budget_bytes; // else: taps from global memory
+            interior = !(border_xy || zlo < 0 || zhi >= p.data.nz);
+        }
+        if (staged) { // copy the bricks, a z layer at a time: 512*ESZ bytes each, 16 bytes per lane
+            const int layer = nxy * PIECES;
+            const int wave_base = wave * 64;
+            for (int lz = 0; lz < nbz; ++lz) {
+                const uint32_t gz_part = (uint32_t) ((b0z + lz) * p.data.bnxy);
+                for (int cb = wave_base; cb < layer; cb += 256) {
+                    const int c = cb + lane;
+                    if (c < layer) { // (8-bit bricks are 32 pieces: an odd number of them ends in the middle of a wave)
+                        const uint32_t gb = s_brick_xy[c / PIECES] + gz_part;
+                        dma_16((const char*) p.data.data + ((size_t) gb * 512 * ESZ + (size_t) (c % PIECES) * 16), smem + (size_t) (lz * layer + cb) * 16);
+                    }
+                }
+            }
+        }
+        if (threadIdx.x < NS * kOccDepth) { // z tap offsets of each slice, in the layout just chosen
+            const int si = threadIdx.x / kOccDepth, q = threadIdx.x % kOccDepth;
+            auto zoff = [&](int c) -> uint32_t {
+                c = min(max(c, 0), p.data.nz - 1);
+                if (!staged) return brick_off_z(c, p.data.bnxy);
+                return (uint32_t) (min(max(c >> 3, b0z), b0z + nbz - 1) - b0z) * (uint32_t) nxy * 512u + ((uint32_t) (c & 7) << 6);
+            };
+            s_o0[par][si][q] = zoff(s_i[par][si][q]);
+            s_o1[par][si][q] = zoff(s_i[par][si][q] + 1);
+        }
+        // the unit's blocks in the two passes (ranks are loaded while the copies are in flight)
+        int32_t rank[2];
+        int unit_off[2], out2_step[2];
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const DualPass& P = d.pass[k];
+            int unit_idx;
+            if (P.axis == 2) {
+                const int ks = (k0 - P.start) * P.dir;
+                unit_idx = (ks >> 3) * P.blocks_y * P.blocks_x;
+                unit_off[k] = (ks & 7) * 256;
+                out2_step[k] = 256 * P.dir;
+            } else {
+                unit_idx = (k0 >> 4) * P.blocks_x;
+                unit_off[k] = (k0 & 15) * 16;
+                out2_step[k] = kOccTile;
+            }
+            rank[k] = pixel_ok ? P.fs_slot[inv_idx[k] + unit_idx] : -1;
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (!pixel_ok) continue;
+
+        // the sample loop, specialised as k_light_occlusion's: STAGED / INTERIOR / CLIP
+        auto run = [&](auto staged_c, auto interior_c, auto clip_c, auto nonneg_c) __attribute__((always_inline)) { // (inlined early: lo / hi / held stay in registers)
+            constexpr bool STAGED = decltype(staged_c)::value, INTERIOR = decltype(interior_c)::value, CLIP = decltype(clip_c)::value, NONNEG = decltype(nonneg_c)::value;
+            const float border = p.data_border;
+            auto tap = [&](uint32_t off, bool ok) -> float {
+                if constexpr (INTERIOR) return STAGED ? lds_voxel<DFMT>(smem, off) : load_voxel<DFMT>(p.data.data, off);
+                else return ok ? (STAGED ? lds_voxel<DFMT>(smem, off) : load_voxel<DFMT>(p.data.data, off)) : border;
+            };
+            auto stream = [&](auto si_c, StreamRegs& sr) __attribute__((always_inline)) {
+                constexpr int si = decltype(si_c)::value;
+                uint32_t o00 = sr.o00, o10 = sr.o10, o01 = sr.o01, o11 = sr.o11;
+                float u = 0.0f, v = 0.0f;
+                if constexpr (!STAGED || CLIP) { // the uncommon forms recompute what the run does not carry for them
+                    const OccThreadTaps t = thread_taps(si, STAGED);
+                    o00 = t.o00; o10 = t.o10; o01 = t.o01; o11 = t.o11;
+                    u = t.u; v = t.v;
+                }
+                const float fu = sr.fu, fv = sr.fv;
+                const int ok = sr.ok;
+                float* out2[2]; // where this thread's voxels go in the two passes' stores (null: block flagged empty)
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    const DualPass& P = d.pass[k];
+                    out2[k] = nullptr;
+                    if (rank[k] >= 0) {
+                        float* const blk_base = (uint32_t) rank[k] < P.fs_cap[si] ? P.fs_keep[si] + (size_t) (uint32_t) rank[k] * 2048 : P.fs_spill[si] + (size_t) ((uint32_t) rank[k] - P.fs_cap[si]) * 2048;
+                        out2[k] = blk_base + (inv_off[k] + unit_off[k]);
+                    }
+                }
+                auto fetch_plane = [&](int q, bool upper) -> float {
+                    const uint32_t w = upper ? s_o1[par][si][q] : s_o0[par][si][q];
+                    const bool a = (s_flags[par][si][q] & (upper ? 2 : 1)) != 0;
+                    const float t00 = tap(o00 + w, (ok & 1) && a), t10 = tap(o10 + w, (ok & 2) && a);
+                    const float t01 = tap(o01 + w, (ok & 4) && a), t11 = tap(o11 + w, (ok & 8) && a);
+                    return lerp_(lerp_(t00, t10, fu), lerp_(t01, t11, fu), fv);
+                };
+                // the step sizes in vector registers (as scalars they are spilled around this loop and fetched back every trip)
+                float step_v0 = d.pass[0].step100[si], step_v1 = d.pass[1].step100[si];
+                asm volatile("" : "+v"(step_v0), "+v"(step_v1));
+                for (int q = 0; q < nk; ++q) {
+                    const float fs = s_f[par][si][q];
+                    const int fl = s_flags[par][si][q];
+                    const int i = __builtin_amdgcn_readfirstlane(s_i[par][si][q]); // wave-uniform: scalar branches below
+                    if (i == sr.held + 1) { sr.lo = sr.hi; sr.hi = fetch_plane(q, true); }
+                    else if (i == sr.held - 1) { sr.hi = sr.lo; sr.lo = fetch_plane(q, false); }
+                    else if (i != sr.held) { sr.lo = fetch_plane(q, false); sr.hi = fetch_plane(q, true); }
+                    sr.held = i;
+                    float aw = 1.0f;
+                    if constexpr (CLIP) aw = clip_alpha_weight(u, v, s_w[par][si][q], p.cc, p.cd, p.lv_dims);
+                    bool inside = true;
+                    if constexpr (GUARD) inside = (ok & 16) && (fl & 4);
+                    float occ0 = 0.0f, occ1 = 0.0f;
+                    if (aw > 0.0f && inside) {
+                        windowed_alpha2<DFMT != FMT_F32, NONNEG>(lerp_(sr.lo, sr.hi, fs), step_v0, step_v1, s_alpha, p.win, occ0, occ1);
+                        occ0 = occ0 * aw;
+                        occ1 = occ1 * aw;
+                    }
+                    if (out2[0]) out2[0][q * out2_step[0]] = 1 - occ0;
+                    if (out2[1]) out2[1][q * out2_step[1]] = 1 - occ1;
+                }
+            };
+            stream(std::integral_constant<int, 0>{}, regs_a);
+            if constexpr (NS == 2) stream(std::integral_constant<int, 1>{}, regs_r);
+        };
+        using T_ = std::true_type; using F_ = std::false_type;
+        auto forms = [&](auto nonneg_c) __attribute__((always_inline)) {
+            if (staged && interior && !p.clip_mode) run(T_{}, T_{}, F_{}, nonneg_c); // the common case
+            else if (staged && !p.clip_mode) run(T_{}, F_{}, F_{}, nonneg_c);         // shell of the volume
+            else if (staged) run(T_{}, F_{}, T_{}, nonneg_c);                         // clip plane active
+            else run(F_{}, F_{}, T_{}, nonneg_c);                                     // bricks did not fit in LDS
+        };
+        if (steps_nonneg) forms(T_{});
+        else forms(F_{});
+    }
+}
+
 template <int DFMT, int MODE, int AXIS>
-static hipError_t launch_occ3(const ChunkParams& p, hipStream_t s, const DualOcc* dual)
+static hipError_t launch_occ3(const ChunkParams& p, hipStream_t s, const DualOcc* dual, const OccRuns* runs)
 {
     const int blocks = ((p.W + kOccTile - 1) / kOccTile) * ((p.H + kOccTile - 1) / kOccTile) * ((p.n_steps + kOccDepth - 1) / kOccDepth);
     int wgs = 8 * ((blocks + 7) / 8);
@@ -671,6 +983,12 @@ static hipError_t launch_occ3(const ChunkParams& p, hipStream_t s, const DualOcc
         if constexpr (MODE == PASS_ADD2 || AXIS != 2) return hipErrorInvalidConfiguration; // (dual launches loop along z: DualOcc)
         else {
             if (!p.occ_list || !p.occ_count || p.dir != 1 || p.j0 != 0) return hipErrorInvalidConfiguration; // (the units come from their work list)
+            if (runs) { // one workgroup per word of the run list; how many there are is known on the device only
+                static std::atomic<uint64_t> attr_done3{0};
+                if (const hipError_t e = allow_big_lds(k_light_occlusion_runs<DFMT, MODE>, attr_done3, 128 * 1024); e != hipSuccess) return e;
+                hipLaunchKernelGGL((k_light_occlusion_runs<DFMT, MODE>), dim3(wgs + 8 * runs->len), block, lds, s, p, (int) lds, *dual, runs->list, runs->count);
+                return hipGetLastError();
+            }
             static std::atomic<uint64_t> attr_done2{0};
             if (const hipError_t e = allow_big_lds(k_light_occlusion<DFMT, MODE, AXIS, true>, attr_done2, 128 * 1024); e != hipSuccess) return e;
             hipLaunchKernelGGL((k_light_occlusion<DFMT, MODE, AXIS, true>), grid, block, lds, s, p, (int) lds, *dual);
@@ -683,25 +1001,25 @@ static hipError_t launch_occ3(const ChunkParams& p, hipStream_t s, const DualOcc
     return hipGetLastError();
 }
 template <int DFMT, int MODE>
-static hipError_t launch_occ2(const ChunkParams& p, hipStream_t s, const DualOcc* dual)
+static hipError_t launch_occ2(const ChunkParams& p, hipStream_t s, const DualOcc* dual, const OccRuns* runs)
 {
-    return p.axis == 0 ? launch_occ3<DFMT, MODE, 0>(p, s, dual) : (p.axis == 1 ? launch_occ3<DFMT, MODE, 1>(p, s, dual) : launch_occ3<DFMT, MODE, 2>(p, s, dual));
+    return p.axis == 0 ? launch_occ3<DFMT, MODE, 0>(p, s, dual, runs) : (p.axis == 1 ? launch_occ3<DFMT, MODE, 1>(p, s, dual, runs) : launch_occ3<DFMT, MODE, 2>(p, s, dual, runs));
 }
 template <int DFMT>
-static hipError_t launch_occ1(const ChunkParams& p, int mode, hipStream_t s, const DualOcc* dual)
+static hipError_t launch_occ1(const ChunkParams& p, int mode, hipStream_t s, const DualOcc* dual, const OccRuns* runs)
 {
-    return mode == PASS_ADD ? launch_occ2<DFMT, PASS_ADD>(p, s, dual)
-           : (mode == PASS_CHANGE ? launch_occ2<DFMT, PASS_CHANGE>(p, s, dual) : (mode == PASS_ADD2 ? launch_occ2<DFMT, PASS_ADD2>(p, s, dual) : launch_occ2<DFMT, PASS_CHANGE_ONE>(p, s, dual)));
+    return mode == PASS_ADD ? launch_occ2<DFMT, PASS_ADD>(p, s, dual, runs)
+           : (mode == PASS_CHANGE ? launch_occ2<DFMT, PASS_CHANGE>(p, s, dual, runs) : (mode == PASS_ADD2 ? launch_occ2<DFMT, PASS_ADD2>(p, s, dual, runs) : launch_occ2<DFMT, PASS_CHANGE_ONE>(p, s, dual, runs)));
 }
 // computes the occlusion of the chunk described by (j0, n_steps) into {a,r}.occ_next; dual: of BOTH passes of a light, p
-// describing the virtual pass along z (tbrm_internal.h DualOcc)
-hipError_t launch_light_occlusion(const ChunkParams& p, int mode, hipStream_t s, const DualOcc* dual)
+// describing the virtual pass along z (tbrm_internal.h DualOcc); runs: that launch in run form (k_light_occlusion_runs)
+hipError_t launch_light_occlusion(const ChunkParams& p, int mode, hipStream_t s, const DualOcc* dual, const OccRuns* runs)
 {
     if (p.n_steps <= 0) return hipSuccess;
     switch (p.data.fmt) {
-        case FMT_U8: return launch_occ1<FMT_U8>(p, mode, s, dual);
-        case FMT_U16: return launch_occ1<FMT_U16>(p, mode, s, dual);
-        default: return launch_occ1<FMT_F32>(p, mode, s, dual);
+        case FMT_U8: return launch_occ1<FMT_U8>(p, mode, s, dual, runs);
+        case FMT_U16: return launch_occ1<FMT_U16>(p, mode, s, dual, runs);
+        default: return launch_occ1<FMT_F32>(p, mode, s, dual, runs);
     }
 }
 
@@ -738,6 +1056,106 @@ hipError_t launch_unit_flags(const ChunkParams& pc, const DualOcc& d, hipStream_
     hipLaunchKernelGGL(k_unit_flags, dim3((per_chunk + 255) / 256), dim3(256), 0, s, pc, d, per_chunk);
     const int segs = (per_chunk + kCompactSeg - 1) / kCompactSeg;
     hipLaunchKernelGGL(k_occ_compact, dim3(segs), dim3(256), 0, s, pc, segs);
+    return hipGetLastError();
+}
+
+// ---- k_occ_runs: the run list of a dual launch (tbrm_internal.h OccRuns) ------------------------------------------------------------
+// One workgroup, its threads dealt over the columns of units: a thread packs the column's flags into 64-bit liveness words (kept in LDS), cuts every
+// stretch of live units into runs of R and a shorter last one, and counts its runs per length. Then, per length from R down to 1,
+// a scan over the columns gives every run its ascending position j in its class, and the run goes where the workgroup of XCD
+// j / ceil(class / 8) finds it: workgroups are dealt to the 8 XCDs round-robin by id, so word 8 * slot + x of a class is XCD x's
+// slot-th run, and each XCD takes a contiguous eighth of the class (columns that are neighbours in the volume behind one L2).
+constexpr int kRunThreads = 256; // (four waves find a place beside a sweep's resident tiles at once; sixteen were measured waiting for one for 0.3 ms)
+__global__ __launch_bounds__(kRunThreads) void k_occ_runs(const uint8_t* __restrict__ flags, int columns, int groups, int R, uint32_t* __restrict__ runs, int* __restrict__ count,
+                                                           int* __restrict__ count_host)
+{
+    __shared__ unsigned long long s_mask[kRunMaskWords];
+    __shared__ int s_hist[kOccRunMax + 1], s_start[kOccRunMax + 1], s_wave[kRunThreads / 64 + 1], s_live, s_total;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int words = (groups + 63) >> 6;
+    if (tid <= kOccRunMax) s_hist[tid] = 0;
+    if (tid == 0) s_live = 0;
+    __syncthreads();
+    // f(first unit's z, length) for every run of liveness word m (64 units of z from z0 on)
+    auto for_runs = [&](unsigned long long m, int z0, auto&& f) {
+        while (m) {
+            const int s = __builtin_ctzll(m);
+            const unsigned long long t = ~(m >> s);
+            const int n = t ? min(__builtin_ctzll(t), 64 - s) : 64 - s;
+            m = n == 64 ? 0ull : m & ~(((1ull << n) - 1ull) << s);
+            for (int o = 0; o < n; o += R) f(z0 + s + o, min(R, n - o));
+        }
+    };
+    for (int col = tid; col < columns; col += kRunThreads)
+        for (int w = 0; w < words; ++w) {
+            unsigned long long m = 0;
+            const int n = min(64, groups - 64 * w);
+            for (int g = 0; g < n; ++g) m |= (unsigned long long) (flags[(size_t) (64 * w + g) * columns + col] ? 0 : 1) << g;
+            s_mask[(size_t) col * words + w] = m;
+            atomicAdd(&s_live, __builtin_popcountll(m));
+            for_runs(m, 64 * w, [&](int, int l) { atomicAdd(&s_hist[l], 1); });
+        }
+    __syncthreads();
+    if (tid == 0) {
+        int start = 0, n_runs = 0;
+        for (int l = R; l >= 1; --l) {
+            s_start[l] = start;
+            start += 8 * ((s_hist[l] + 7) >> 3);
+            n_runs += s_hist[l];
+        }
+        s_total = start;
+        count[1] = start;
+        count_host[1] = s_live - n_runs; // (visible to the host once an event behind the launch has completed)
+    }
+    __syncthreads();
+    for (int i = tid; i < s_total; i += kRunThreads) runs[i] = kRunNone;
+    __syncthreads();
+    for (int l = R; l >= 1; --l) {
+        const int in_class = s_hist[l];
+        if (in_class == 0) continue;
+        const int per_xcd = (in_class + 7) >> 3;
+        int before = 0; // runs of this length in the columns already taken
+        for (int col0 = 0; col0 < columns; col0 += kRunThreads) {
+            const int col = col0 + tid;
+            int mine = 0;
+            if (col < columns)
+                for (int w = 0; w < words; ++w) for_runs(s_mask[(size_t) col * words + w], 64 * w, [&](int, int n) { mine += n == l ? 1 : 0; });
+            int incl = mine; // inclusive scan over the workgroup
+            for (int dd = 1; dd < 64; dd <<= 1) {
+                const int t = __shfl_up(incl, dd);
+                if (lane >= dd) incl += t;
+            }
+            if (lane == 63) s_wave[wave] = incl;
+            __syncthreads();
+            if (tid == 0) {
+                int acc = 0;
+                for (int k = 0; k < kRunThreads / 64; ++k) { const int t = s_wave[k]; s_wave[k] = acc; acc += t; }
+                s_wave[kRunThreads / 64] = acc;
+            }
+            __syncthreads();
+            int j = before + s_wave[wave] + incl - mine;
+            before += s_wave[kRunThreads / 64];
+            if (col < columns)
+                for (int w = 0; w < words; ++w)
+                    for_runs(s_mask[(size_t) col * words + w], 64 * w, [&](int z, int n) {
+                        if (n != l) return;
+                        runs[s_start[l] + 8 * (j % per_xcd) + j / per_xcd] = ((uint32_t) (n - 1) << kRunLenShift) | (uint32_t) (z * columns + col);
+                        ++j;
+                    });
+            __syncthreads(); // (s_wave is written again)
+        }
+    }
+}
+
+bool occ_runs_apply(const ChunkParams& pc)
+{
+    const size_t columns = (size_t) pc.occ_blocks_x * pc.occ_blocks_y;
+    return columns * (size_t) ((pc.occ_groups + 63) / 64) <= kRunMaskWords && columns * (size_t) pc.occ_groups <= ((size_t) 1 << kRunLenShift);
+}
+
+hipError_t launch_occ_runs(const ChunkParams& pc, const OccRuns& runs, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_occ_runs, dim3(1), dim3(kRunThreads), 0, s, pc.occ_flags_out, pc.occ_blocks_x * pc.occ_blocks_y, pc.occ_groups, runs.len, runs.list, runs.count, runs.count_host);
     return hipGetLastError();
 }
 

@@ -151,6 +151,9 @@ struct BlockLists {
     bool enqueued = false;          // its kernels are on the occlusion stream
     uint64_t id = 0;                // never reused within a handle
     uint64_t a_id = 0, b_id = 0;    // units of a dual launch: the two passes' lists (0: a pass's own lists)
+    uint32_t* runs = nullptr;       // units of a dual launch: their run list (tbrm_internal.h OccRuns), behind `list` in the same allocation
+    int run_len = 0;                // ... the occ_run it was cut for (0: not built)
+    uint64_t run_launches = 0;      // ... occlusion launches that walked it since it was built (units_in_runs)
     int users = 0;                  // factor cache entries whose ranks these are (+ the slab operation that holds a plan over them)
     uint64_t last_use = 0;
     uint64_t last_read_op = 0;      // tbrm_resources::op_serial of the last operator whose launches (occlusion, sweeps) were handed these
@@ -294,6 +297,7 @@ struct tbrm_resources {
     uint64_t block_lists_op_floor = 0;  // block_lists_serial when the operator being planned began: its plans point at younger lists
     std::vector<BlockLists*> spare_lists;  // made by tbrm_resources_reserve, never used yet: [with ranks], then [without]
     uint64_t lists_launches = 0;   // passes / dual launches whose lists had to be computed (tbrm_path_counters)
+    uint64_t run_followers = 0;    // occlusion units that ran as the second or later unit of a run, of run lists that are gone (units_in_runs)
     // tbrm_resources_reserve: everything the light operators would otherwise allocate as they go
     bool reserved = false;
     bool reserved_eagerly = false; // (by tbrm_resources_reserve: scratch stores and hand-off records too)
@@ -505,6 +509,8 @@ BlockLists* make_spare_lists(tbrm_resources* r, size_t blocks, bool with_ranks);
 // tbrm_block_lists.cpp
 BlockLists* block_lists_for_pass(tbrm_resources* r, const ChunkParams& p, int occ_mode);  // null: allocation failed (tbrm_last_error)
 BlockLists* block_lists_for_dual(tbrm_resources* r, const BlockLists* a, const BlockLists* b, size_t units);
+bool run_list_for(tbrm_resources* r, BlockLists* l, int len, OccRuns* out, bool* build); // false: these lists have no room for one
+uint64_t units_in_runs(const tbrm_resources* r); // tbrm_path_counters [15]: waits for run lists that are still being built
 bool block_lists_count(BlockLists* l, bool wait, size_t* count); // the live-block count, once it has arrived
 void release_block_lists(tbrm_resources* r); // (the streams must be idle)
 void release_occ_stores(tbrm_resources* r); // frees the occlusion stores and the factor cache (the streams must be idle)
