@@ -203,7 +203,8 @@ TBRM_API int tbrm_device_count(int* out_count);   /* TBRM_ERR_NO_DEVICE when the
  * pixel blocks to the GPU's eight XCDs row by row — horizontal neighbours, which march through the same bricks, share an L2 —; n = in
  * bands of n rows; 0 = in launch order, i.e. round-robin block by block: 10 % slower at 512^3),
  * stats_groups (0 = the statistics kernels of tbrm_volume_stats.h size their grid to the device; n > 0 = at most n workgroups: a test
- * hook and an A/B switch). Unknown name: TBRM_ERR_INVALID_ARG. */
+ * hook and an A/B switch), view_cache_mb (1536 = MiB of records per handle from which a lit frame of an unchanged view is relit
+ * instead of marched again, bit-identically: tbrm_view_cache.h; 0 = every frame marches). Unknown name: TBRM_ERR_INVALID_ARG. */
 TBRM_API int tbrm_set_tunable(const char* name, int32_t value);
 TBRM_API int tbrm_get_tunable(const char* name, int32_t* value);
 

@@ -180,6 +180,11 @@ class HistogramDesc(C.Structure):  # tbrm_histogram_desc
 # tbrm_label_stat, as a numpy record
 LABEL_STAT_DTYPE = np.dtype([("count", np.uint64), ("nan_count", np.uint64), ("sum", np.float64), ("min", np.float64), ("max", np.float64)])
 
+# every symbol include/tbrm_view_cache.h declares (the view cache; tests/test_gpu_view_cache.py checks the header against this list)
+VIEW_CACHE_SYMBOLS = ["tbrm_view_cache_abi_version", "tbrm_view_cache_stats"]
+
+VIEW_CACHE_ABI_VERSION = 1  # TBRM_VIEW_CACHE_ABI_VERSION of include/tbrm_view_cache.h
+
 _lib = None
 
 
@@ -306,6 +311,11 @@ def load():
     lib.tbrm_label_statistics.argtypes = [vp, P(C.c_int32 * 3), P(C.c_int32 * 3), vp]
     lib.tbrm_host_window_from_histogram.argtypes = [vp, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, P(WindowingParams)]
     lib.tbrm_volume_stats_counters.argtypes = [vp, P(C.c_uint64 * 4)]
+    have = lib.tbrm_view_cache_abi_version() if hasattr(lib, "tbrm_view_cache_abi_version") else -1
+    if have != VIEW_CACHE_ABI_VERSION:
+        raise ImportError(f"{LIB_PATH} has view-cache ABI version {have}, this binding is written against {VIEW_CACHE_ABI_VERSION}: "
+                          "rebuild it (`python tbraymarcherplugin_amd/build.py --force`)")
+    lib.tbrm_view_cache_stats.argtypes = [vp, P(C.c_uint64 * 6)]
     _lib = lib
     return lib
 
@@ -800,6 +810,14 @@ class Resources:
         out = (C.c_uint64 * 4)()
         check(self.lib.tbrm_light_cache_stats(self.handle, C.byref(out)))
         return {"hits": int(out[0]), "propagated": int(out[1]), "entries": int(out[2]), "bytes": int(out[3])}
+
+    VIEW_CACHE_STATS = ("plain", "counted", "filled", "relit", "dropped", "record_bytes")
+
+    def view_cache_stats(self):
+        """tbrm_view_cache_stats (include/tbrm_view_cache.h): how this handle's lit frames were served."""
+        out = (C.c_uint64 * 6)()
+        check(self.lib.tbrm_view_cache_stats(self.handle, C.byref(out)))
+        return {k: int(out[i]) for i, k in enumerate(self.VIEW_CACHE_STATS)}
 
     def light_cache_clear(self):
         check(self.lib.tbrm_light_cache_clear(self.handle))

@@ -3,6 +3,7 @@
 // slice view (:187-242), the Octree mode's pyramid and march (GenerateOctreeShader.usf:28-107, :99-183) and the nominal-sample
 // count of the benchmark's metric. Handle life cycle, inputs and light operators: tbrm_api.cpp.
 #include "tbrm_resources.h"
+#include "../../include/tbrm_view_cache.h"
 
 #include <algorithm>
 #include <cmath>
@@ -20,7 +21,7 @@ int build_ray_params(tbrm_resources* r, const tbrm_camera* cam, const tbrm_tile*
 {
     if (!(rp->steps > 0.0f)) return fail(TBRM_ERR_INVALID_ARG, "steps must be > 0");
     if (tile->w < 0 || tile->h < 0 || cam->width <= 0 || cam->height <= 0) return fail(TBRM_ERR_INVALID_ARG, "bad tile/camera size");
-    p = RayParams{};
+    std::memset(&p, 0, sizeof(p)); // (padding too: the view cache compares the block)
     p.data = data_view(r);
     p.data_addr_mode = r->desc.data_address_mode == TBRM_ADDRESS_CLAMP ? ADDR_CLAMP : ADDR_WRAP;
     p.tf = r->d_tf;
@@ -95,9 +96,158 @@ template <class March> int deliver_frame(tbrm_resources* r, const tbrm_tile* til
     return TBRM_OK;
 }
 
+// ---- the view cache (tbrm_resources.h ViewCache; DESIGN.md 4.1 "Relit frames") -----------------------------------------------------
+
+// The current view's share of the arena: [counts | offsets | meta] for its waves, then as many trips' base words and rows as fit.
+// false: no arena, or not even the per-wave words fit.
+bool carve_view_arena(ViewCache& v, const RayParams& p)
+{
+    const size_t bw = 8, bh = v.lanes == 4 ? 8 : 4; // (launch_lit's grid: 4 waves per workgroup)
+    const size_t waves = ((size_t) p.tile_w + bw - 1) / bw * (((size_t) p.tile_h + bh - 1) / bh) * 4;
+    const size_t align = 256, header = (2 * waves * sizeof(uint32_t) + 16 + align - 1) / align * align;
+    if (!v.arena || waves > 0xffffffffu || header + 2 * align + kRayRecordTripBytes > v.arena_bytes) return false;
+    const size_t cap = std::min<size_t>((v.arena_bytes - header - align) / kRayRecordTripBytes, 0xffffffffu);
+    v.n_waves = (uint32_t) waves;
+    v.cap_trips = (uint32_t) cap;
+    v.rec.counts = reinterpret_cast<uint32_t*>(v.arena);
+    v.rec.offsets = v.rec.counts + waves;
+    v.rec.meta = v.rec.offsets + waves;
+    v.rec.base = reinterpret_cast<int32_t*>(v.arena + header);
+    v.rec.rows = v.arena + header + (cap * sizeof(int32_t) + align - 1) / align * align;
+    return true;
+}
+
+// The frame of a mono handle: the march, or — for a view this handle has marched, counted and recorded — k_relight.
+int march_or_relight(tbrm_resources* r, RayParams& p)
+{
+    ViewCache& v = r->view;
+    const auto plain = [&]() -> int {
+        HIP_TRY(launch_raymarch(p, r->stream));
+        ++v.stats[0];
+        return TBRM_OK;
+    };
+    // frames that never take part: the feature off, a scene depth, an attached label volume, slab stages and slab-resident handles
+    if (tune(TUNE_VIEW_CACHE_MB) <= 0 || p.depth || r->d_labels || p.slab_on || r->resident || p.tile_w <= 0 || p.tile_h <= 0) {
+        v.state = ViewCache::kNone;
+        v.stats[5] = 0;
+        return plain();
+    }
+    RayParams key;
+    std::memcpy(&key, &p, sizeof(key));
+    key.out = nullptr;
+    const int lanes = ray_lanes_for(p), tables = ray_tables_for(p) ? 1 : 0;
+    if (v.state == ViewCache::kNone || v.lanes != lanes || v.tables != tables || v.data_gen != r->data_gen || v.tf_gen != r->tf_gen ||
+        std::memcmp(&v.key, &key, sizeof(key)) != 0) { // another view (a moving camera stays here: the march it always ran)
+        std::memcpy(&v.key, &key, sizeof(key));
+        v.lanes = lanes;
+        v.tables = tables;
+        v.data_gen = r->data_gen;
+        v.tf_gen = r->tf_gen;
+        v.state = ViewCache::kPlain;
+        v.stats[5] = 0;
+        return plain();
+    }
+    switch (v.state) {
+    case ViewCache::kPlain: // the second frame of the view: the march, counting its recorded trips per wave
+        ensure_view_arena(r, false);
+        if (!carve_view_arena(v, p)) {
+            v.state = ViewCache::kTooLarge;
+            ++v.stats[4];
+            return plain();
+        }
+        p.rec = v.rec;
+        HIP_TRY(launch_raymarch_recording(p, false, r->stream));
+        v.state = ViewCache::kCounted;
+        ++v.stats[1];
+        return TBRM_OK;
+    case ViewCache::kCounted: // the third: offsets, the march writing the records (if they fit), and the verdict on its way to the host
+        p.rec = v.rec;
+        HIP_TRY(launch_view_scan(v.rec, v.n_waves, v.cap_trips, r->stream));
+        HIP_TRY(launch_raymarch_recording(p, true, r->stream));
+        HIP_TRY(hipMemcpyAsync(v.meta_host, v.rec.meta, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
+        HIP_TRY(hipEventRecord(v.ev_meta, r->stream));
+        v.state = ViewCache::kFilled;
+        ++v.stats[2];
+        return TBRM_OK;
+    case ViewCache::kFilled: { // asked, never waited for
+        const hipError_t q = hipEventQuery(v.ev_meta);
+        if (q == hipErrorNotReady) {
+            (void) hipGetLastError();
+            return plain();
+        }
+        HIP_TRY(q);
+        if (!v.meta_host[1]) {
+            v.state = ViewCache::kTooLarge;
+            ++v.stats[4];
+            return plain();
+        }
+        v.state = ViewCache::kReady;
+        v.stats[5] = (uint64_t) v.meta_host[0] * kRayRecordTripBytes + 2 * (uint64_t) v.n_waves * sizeof(uint32_t);
+        [[fallthrough]];
+    }
+    case ViewCache::kReady:
+        p.rec = v.rec;
+        HIP_TRY(launch_relight(p, r->stream));
+        ++v.stats[3];
+        return TBRM_OK;
+    default: // kTooLarge: the march, until the key changes
+        return plain();
+    }
+}
+
 } // namespace
 
+namespace tbrm_host {
+
+void ensure_view_arena(tbrm_resources* r, bool eager)
+{
+    ViewCache& v = r->view;
+    const int mb = tune(TUNE_VIEW_CACHE_MB);
+    if (v.arena_tried || mb <= 0 || r->resident || r->light_channels != 1) return;
+    v.arena_tried = true;
+    size_t want = (size_t) mb << 20, free_b = 0, total_b = 0;
+    // (the factor-cache arena's rule, reserve_resources: never the last of the device's memory)
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+        const size_t spare = free_b > ((size_t) 8 << 30) ? free_b - ((size_t) 8 << 30) : 0;
+        want = std::min(want, eager ? spare / 2 : spare / 8);
+    } else (void) hipGetLastError();
+    void* a = nullptr;
+    void* h = nullptr;
+    hipEvent_t ev = nullptr;
+    if (want >= ((size_t) 64 << 10) && hipMalloc(&a, want) == hipSuccess && hipHostMalloc(&h, 4 * sizeof(uint32_t), hipHostMallocDefault) == hipSuccess &&
+        hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess) {
+        v.arena = (char*) a;
+        v.arena_bytes = want;
+        v.meta_host = (uint32_t*) h;
+        v.ev_meta = ev;
+        return;
+    }
+    (void) hipGetLastError(); // (no arena: no relit frames — every frame still marches)
+    if (a) (void) hipFree(a);
+    if (h) (void) hipHostFree(h);
+}
+
+void release_view_cache(tbrm_resources* r)
+{
+    ViewCache& v = r->view;
+    if (v.arena) (void) hipFree(v.arena);
+    if (v.meta_host) (void) hipHostFree(v.meta_host);
+    if (v.ev_meta) (void) hipEventDestroy(v.ev_meta);
+    v = ViewCache{};
+}
+
+} // namespace tbrm_host
+
 extern "C" {
+
+int tbrm_view_cache_abi_version(void) { return TBRM_VIEW_CACHE_ABI_VERSION; }
+
+int tbrm_view_cache_stats(const tbrm_resources* r, uint64_t out[6])
+{
+    if (!r || !out) return fail(TBRM_ERR_INVALID_ARG, "null argument");
+    for (int k = 0; k < 6; ++k) out[k] = r->view.stats[k];
+    return TBRM_OK;
+}
 
 int tbrm_raymarch_lit_device(tbrm_resources* r, const tbrm_camera* cam, const tbrm_tile* tile, const tbrm_raymarch_params* rp,
                              const tbrm_world_params* world, const float* device_scene_depth, float* device_out_rgba)
@@ -118,7 +268,7 @@ int tbrm_raymarch_lit_device(tbrm_resources* r, const tbrm_camera* cam, const tb
         p.light_g = r->light_channel(1);
         p.light_b = r->light_channel(2);
         HIP_TRY(launch_raymarch_rgb(p, r->stream));
-    } else HIP_TRY(launch_raymarch(p, r->stream));
+    } else if (int e = march_or_relight(r, p)) return e;
     ++r->launches[2];
     return end_timed(r, 1);
 }

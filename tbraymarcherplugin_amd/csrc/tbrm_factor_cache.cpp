@@ -422,6 +422,7 @@ int reserve_resources(tbrm_resources* r, int n_lights, unsigned flags)
             else (void) hipGetLastError(); // (no arena: no cache — the operators still run)
         }
     }
+    if (eager) ensure_view_arena(r, true); // (the view cache's records; a handle nobody reserved takes them at its first count frame)
     if (flags & 1u) { // the chunked chain's occlusion stores too (passes the sweep declines: reaches beyond 14 texels, ...)
         const size_t flag_bytes = blocks + 16 * (blocks / std::max<size_t>((size_t) depth / 8, 1)); // (whole spans of 128 slices: up to 16 slice groups more than the pass has)
         for (int b = 0; b < 2; ++b)

@@ -248,6 +248,21 @@ struct SweepChainArgs {
     SweepChainPass pass[kSweepChainMax];
 };
 
+// The view cache's records of one frame (DESIGN.md 4.1 "Relit frames"): what k_raymarch_lit's recording forms write and k_relight
+// reads. A wave is numbered by its workgroup's linear launch id (before the XCD band mapping) and its number in the workgroup; its
+// trips that had something to accumulate are stored in order from trip offsets[wave] on. Per trip one wave-uniform word (the trip's
+// first sample index) and a 64-lane block in struct-of-arrays order: a float4 row (colour.rgb, corrected opacity; w = -1: nothing to
+// accumulate) and three float rows (the saturated position the light volume is sampled at).
+constexpr size_t kRayRecordRowBytes = 64 * (sizeof(float4) + 3 * sizeof(float)); // 1792
+constexpr size_t kRayRecordTripBytes = kRayRecordRowBytes + sizeof(int32_t);
+struct RayRecord {
+    uint32_t* counts;   // [wave] recorded trips (written by the count form)
+    uint32_t* offsets;  // [wave] first trip of the wave (k_view_scan)
+    uint32_t* meta;     // {total trips, fits the arena} (k_view_scan)
+    int32_t* base;      // [trip] the wave-uniform word: the trip's first sample index
+    char* rows;         // [trip] kRayRecordRowBytes each
+};
+
 struct RayParams {
     VolumeDev data;
     int data_addr_mode; // ADDR_WRAP / ADDR_CLAMP
@@ -286,7 +301,12 @@ struct RayParams {
     const float4* lab_colors;   // ... its colour table (256 x RGBA float)
     const void* light_g;        // k_raymarch_lit RGB (colour handles, tbrm_color_lights.h): the G and B channels of the light volume,
     const void* light_b;        // laid out like `light` (then the R channel); null: a mono light volume
+    RayRecord rec;              // the recording forms of k_raymarch_lit and k_relight only (else null)
 };
+
+// What launch_ray2 / launch_ray3 decide for a frame (the view cache keys on both: tbrm_api_render.cpp)
+int ray_lanes_for(const RayParams& p);   // lanes per ray: 4 or 8
+bool ray_tables_for(const RayParams& p); // the LDS offset tables (k_raymarch_lit TAB) apply
 
 // Layout of RayParams::tab (built in tbrm_resources_create, copied into LDS and read by k_raymarch_lit TAB): the x, then the y, then
 // the z axis, one entry for every texel index -kRayTabApron .. n + kRayTabApron - 1 (a base tap two texels outside the volume and its
@@ -392,6 +412,8 @@ enum Tunable : int {
                              // takes many bricks of even a small volume (a test hook and an A/B switch); 0: sized to the device
     TUNE_OCC_RUN,            // dual occlusion launches: a workgroup takes up to this many z-adjacent live units of one column in a row and
                              // keeps what they share (k_light_occlusion_runs; at most kOccRunMax); 1: one unit per workgroup (the A/B switch)
+    TUNE_VIEW_CACHE_MB,      // HBM budget in MiB of the view cache's records (a still view under a moving light is relit from them: k_relight);
+                             // 0: off, every frame marches
     TUNE_COUNT
 };
 int tune(Tunable t);
@@ -417,6 +439,11 @@ hipError_t launch_fill(void* dst, int fmt, size_t n, float value, hipStream_t s)
 hipError_t launch_propagate_slice(const PropParams& p, bool change, hipStream_t s);
 hipError_t launch_raymarch(const RayParams& p, hipStream_t s);
 hipError_t launch_raymarch_rgb(const RayParams& p, hipStream_t s); // (colour handles: tbrm_kernels.hip compiled as the RGB unit)
+// the view cache (tbrm_kernels.hip compiled as the recording unit): the march that also counts (fill = false) or writes (true) p.rec,
+// the scan between the two, and the frame from the records
+hipError_t launch_raymarch_recording(const RayParams& p, bool fill, hipStream_t s);
+hipError_t launch_view_scan(const RayRecord& rec, uint32_t n_waves, uint32_t cap_trips, hipStream_t s);
+hipError_t launch_relight(const RayParams& p, hipStream_t s);
 hipError_t launch_raymarch_intensity(const RayParams& p, hipStream_t s);
 hipError_t launch_raymarch_octree(const RayParams& p, hipStream_t s);
 hipError_t launch_octree_level(const OctreeParams& p, bool base, hipStream_t s);

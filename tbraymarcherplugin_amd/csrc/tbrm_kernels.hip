@@ -14,12 +14,14 @@
 
 namespace tbrm {
 
-// Compiled twice (build.py): as it stands, and with -DTBRM_RAY_RGB_UNIT=1 for k_raymarch_lit's RGB-light form alone
-// (launch_raymarch_rgb), so that the two sets of instantiations build side by side.
-#ifdef TBRM_RAY_RGB_UNIT
+// Compiled three times (build.py): as it stands, with -DTBRM_RAY_RGB_UNIT=1 for k_raymarch_lit's RGB-light form alone
+// (launch_raymarch_rgb), and with -DTBRM_RAY_REC_UNIT=1 for the view cache's kernels alone (the recording forms of k_raymarch_lit,
+// k_view_scan, k_relight), so that the three sets of instantiations build side by side.
+#if defined(TBRM_RAY_RGB_UNIT) || defined(TBRM_RAY_REC_UNIT)
+#define TBRM_RAY_ONLY_UNIT 1
 #undef TBRM_RAY_STATS // (the diagnostics build counts in the mono unit alone)
 #endif
-#ifndef TBRM_RAY_RGB_UNIT
+#ifndef TBRM_RAY_ONLY_UNIT
 // ------------------------------------------------------------------------------------------------------------
 // fill
 
@@ -47,7 +49,7 @@ hipError_t launch_fill(void* dst, int fmt, size_t n, float value, hipStream_t s)
     hipLaunchKernelGGL(k_fill<FMT_F32>, dim3(grid), dim3(block), 0, s, dst, n, value);
     return hipGetLastError();
 }
-#endif // !TBRM_RAY_RGB_UNIT
+#endif // !TBRM_RAY_ONLY_UNIT
 
 // ------------------------------------------------------------------------------------------------------------
 // raymarch
@@ -188,6 +190,29 @@ __device__ __forceinline__ void accumulate(float (&le)[4], const float4& c)
 // The early exit (:75-79) belongs to the full steps only; the march that takes it leaves alpha at exactly 1.
 __device__ __forceinline__ bool exit_reached(float le3, bool is_full_step) { return le3 > 0.95f && is_full_step; }
 
+// The frame kernels' wave -> pixel mapping (k_raymarch_lit, k_relight): ray r of wave `wave` is ray (i, j) of the launch.
+// Workgroups are dealt to the 8 XCDs round-robin by linear id: with the plain (x, y) order the eight horizontal neighbours of a
+// pixel block — which march through the same bricks — sit behind eight different L2s. Bands of p.xcd_rows rows of blocks are dealt
+// to the XCDs instead (band 8 m + x to XCD x: every XCD still gets an even share of the silhouette), walked column by column; an
+// affinity for speed only.
+template <int kRayLanes>
+__device__ __forceinline__ void ray_of_wave(const RayParams& p, int wave, int r, int& i, int& j)
+{
+    constexpr int PW = 4, PH = kRayLanes == 4 ? 4 : 2; // rays of a wave: a PW x PH pixel patch
+    constexpr int kRayBlockW = 2 * PW, kRayBlockH = 2 * PH;
+    int bx = blockIdx.x, by = blockIdx.y;
+    if (p.xcd_rows > 0 && (int) gridDim.y % (8 * p.xcd_rows) == 0) {
+        const int id = by * (int) gridDim.x + bx, k = id >> 3, per_band = p.xcd_rows * (int) gridDim.x;
+        const int band = k / per_band, kk = k - band * per_band;
+        bx = kk / p.xcd_rows;
+        by = (band * 8 + (id & 7)) * p.xcd_rows + (kk - bx * p.xcd_rows);
+    }
+    i = bx * kRayBlockW + (wave & 1) * PW + (r % PW);
+    j = by * kRayBlockH + (wave >> 1) * PH + (r / PW);
+}
+// ... and the number a wave's records go by (RayRecord): from the launch id, which the mapping above does not change
+__device__ __forceinline__ uint32_t ray_wave_number() { return ((uint32_t) blockIdx.y * gridDim.x + blockIdx.x) * 4u + (threadIdx.x >> 6); }
+
 // ---- k_raymarch_lit ---------------------------------------------------------------------------------------------
 // A ray is a serial loop in the reference (positions by repeated addition, front-to-back accumulation with early
 // exit). One ray per lane makes a frame as slow as its longest ray: a 512-step ray is 512 dependent memory round trips
@@ -237,9 +262,16 @@ extern "C" __attribute__((visibility("default"))) int tbrm_debug_ray_stats(unsig
 // needed only behind a_sat != 0: the channels are fetched and filtered there, one after the other — three sets of raw taps beside
 // the data taps do not fit the 80 registers of six waves per SIMD. The sample is ((cs.r l_r) a, (cs.g l_g) a, (cs.b l_b) a, a);
 // nothing else of the march sees the light.
-template <int DFMT, int LFMT, int DMODE, int kRayLanes, bool SLAB = false, bool TAB = false, bool LABELS = false, bool RGB = false>
+//
+// REC: the view cache's recording forms (DESIGN.md 4.1 "Relit frames"; compiled in the recording unit alone). Both deliver the
+// normal frame. REC_COUNT also writes, per wave, the number of its trips that had something to accumulate (any_x); REC_FILL writes
+// those trips' records (RayRecord: the sample's colour, corrected opacity and saturated position — everything of x but the light)
+// from the wave's offset on, when the scan before it found that they fit. REC_OFF is the march itself.
+constexpr int REC_OFF = 0, REC_COUNT = 1, REC_FILL = 2;
+template <int DFMT, int LFMT, int DMODE, int kRayLanes, bool SLAB = false, bool TAB = false, bool LABELS = false, bool RGB = false, int REC = REC_OFF>
 __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6 waves per SIMD (80 VGPRs): measured 3-8 % faster than 5 or 8
 {
+    static_assert(REC == REC_OFF || (!SLAB && !LABELS && !RGB), "only the plain mono march has recording forms");
     static_assert(!(RGB && (SLAB || LABELS)), "colour handles have no slab stage and no label step");
     static_assert(kRayLanes == 4 || kRayLanes == 8, "instantiated for 4 and 8 lanes per ray");
     static_assert(!(TAB && SLAB), "slab stages keep the arithmetic path (relocated layers)");
@@ -248,8 +280,6 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
     const uint2* const tab_x = s_tab;
     const uint2* const tab_y = tab_x + (TAB ? ray_tab_axis_entries(p.data.nx) : 0);
     const uint2* const tab_z = tab_y + (TAB ? ray_tab_axis_entries(p.data.ny) : 0);
-    constexpr int PW = 4, PH = kRayLanes == 4 ? 4 : 2; // rays of a wave: a PW x PH pixel patch
-    constexpr int kRayBlockW = 2 * PW, kRayBlockH = 2 * PH;
     constexpr int LSH = kRayLanes == 4 ? 2 : 3;
     __shared__ float4 s_tf[256];
     __shared__ float4 s_x[256]; // per lane: (colour * alpha, alpha) of its sample; alpha < 0: nothing to accumulate
@@ -266,20 +296,8 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b = lane & (kRayLanes - 1), r = lane >> LSH; // sample slot, ray within the wave
-    // Workgroups are dealt to the 8 XCDs round-robin by linear id: with the plain (x, y) order the eight horizontal neighbours of a
-    // pixel block — which march through the same bricks — sit behind eight different L2s. Bands of p.xcd_rows rows of blocks are dealt
-    // to the XCDs instead (band 8 m + x to XCD x: every XCD still gets an even share of the silhouette), walked column by column; an
-    // affinity for speed only.
-    int bx = blockIdx.x, by = blockIdx.y;
-    if (p.xcd_rows > 0 && (int) gridDim.y % (8 * p.xcd_rows) == 0) {
-        const int id = by * (int) gridDim.x + bx, k = id >> 3, per_band = p.xcd_rows * (int) gridDim.x;
-        const int band = k / per_band, kk = k - band * per_band;
-        bx = kk / p.xcd_rows;
-        by = (band * 8 + (id & 7)) * p.xcd_rows + (kk - bx * p.xcd_rows);
-    }
-    const int i = bx * kRayBlockW + (wave & 1) * PW + (r % PW);
-    const int j = by * kRayBlockH + (wave >> 1) * PH + (r / PW);
-    int px, py;
+    int i, j, px, py;
+    ray_of_wave<kRayLanes>(p, wave, r, i, j);
     const bool valid = tile_pixel_at(p, i, j, px, py);
 
     Ray ray;
@@ -324,6 +342,12 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
         } else done = true;
     }
     int adds = 0; // full-step additions this lane has applied to its position
+    // REC: trips recorded so far; REC_FILL: where the wave's records go, if it may write them (the count form counted as many)
+    [[maybe_unused]] uint32_t n_rec = 0, rec_first = 0, rec_room = 0;
+    if constexpr (REC == REC_FILL) {
+        rec_first = p.rec.offsets[ray_wave_number()];
+        rec_room = p.rec.meta[1] != 0 ? p.rec.counts[ray_wave_number()] : 0;
+    }
     float4* const xs = s_x + (threadIdx.x & ~(kRayLanes - 1)); // the ray's kRayLanes exchange slots
 
     // A trip is five stages: advance the position, locate the sample, shade it, exchange and replay, the wave-wide leap. They stay one
@@ -351,6 +375,8 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
         // ---- 2. locate: does the sample have to be evaluated (live), where do its data taps lie (texel split, TAB offsets), and how far
         // does its brick's leap distance prove the lane's next samples empty (safe_until)
         float4 x = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+        [[maybe_unused]] float4 rec_x = x;                                // REC_FILL: (cs.rgb, a) of x
+        [[maybe_unused]] float rec_sp0 = 0.0f, rec_sp1 = 0.0f, rec_sp2 = 0.0f; // ... and where its light is sampled
         bool live = has && idx > safe_until && !(p.clip_mode && is_clipped(q0, q1, q2, p.cc, p.cd));
         if constexpr (SLAB) { // only the samples of this handle's slab
             const int zi = min((int) (saturate_(q2) * lnz), p.lv_dims[2] - 1);
@@ -456,6 +482,7 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
                     } else {
                         const float l = ltaps.filter(gx, gy, gz);
                         x = make_float4((cs.x * l) * a, (cs.y * l) * a, (cs.z * l) * a, a);
+                        if constexpr (REC == REC_FILL) { rec_x = make_float4(cs.x, cs.y, cs.z, a); rec_sp0 = sp0; rec_sp1 = sp1; rec_sp2 = sp2; }
                     }
                 }
             }
@@ -477,33 +504,18 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
         }
 #endif
         if (any_x) {
-            s_x[threadIdx.x] = x;
-            if constexpr (LABELS) s_lb[threadIdx.x] = (short) lab;
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int t = 0; t < kRayLanes; ++t) {
-                const float4 c = xs[t];
-                const bool is_full_step = base + t < max_steps;
-                const bool data_step = !(c.w < 0.0f);
-                // (a slot without a step to take gets no exit test either: a slab stage leaves the state it took over alone)
-                if (done || (!LABELS && !data_step)) continue;
-                if (data_step) accumulate(le, c);
-                if constexpr (LABELS) { // then the label step (AccumulateOneRaymarchLabelStep: unlit)
-                    const int lb = s_lb[(threadIdx.x & ~(kRayLanes - 1)) + t];
-                    if (lb >= 0) {
-                        float4 e;
-                        if (is_full_step) e = s_lab[lb];
-                        else { // the fractional step (once per ray): its own a' with the step 100 * FinalStep
-                            const float4 raw = p.lab_colors[lb];
-                            const float a = raw.w != 0.0f ? one_minus_pow01_(1.0f - raw.w, 100.0f * final_step) : 0.0f;
-                            e = make_float4(raw.x * a, raw.y * a, raw.z * a, a);
-                        }
-                        accumulate(le, e);
-                    }
+            if constexpr (REC == REC_FILL) {
+                if (n_rec < rec_room) {
+                    const size_t trip = (size_t) rec_first + n_rec;
+                    char* const row = p.rec.rows + trip * kRayRecordRowBytes;
+                    if (lane == 0) p.rec.base[trip] = base;
+                    reinterpret_cast<float4*>(row)[lane] = rec_x;
+                    float* const sp = reinterpret_cast<float*>(row + 64 * sizeof(float4));
+                    sp[lane] = rec_sp0; sp[64 + lane] = rec_sp1; sp[128 + lane] = rec_sp2;
                 }
-                if (exit_reached(le[3], is_full_step)) { le[3] = 1.0f; done = true; }
             }
-            __builtin_amdgcn_wave_barrier();
+            if constexpr (REC != REC_OFF) ++n_rec;
+#include "tbrm_ray_replay.inc"
         }
         if (base + kRayLanes >= n_samples) done = true;
         // ---- 5. leap. Empty space, wave-wide: when no lane of the wave had anything to sample in this trip, the trips that EVERY marching
@@ -536,35 +548,49 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
         }
     }
     if ((SLAB ? mine : valid) && b == 0) reinterpret_cast<float4*>(p.out)[(size_t) j * p.tile_w + i] = make_float4(le[0], le[1], le[2], le[3]);
+    if constexpr (REC == REC_COUNT) {
+        if (lane == 0) p.rec.counts[ray_wave_number()] = n_rec;
+    }
 }
 
-template <int DFMT, int LFMT, int RL, bool SLAB, bool TAB, bool LABELS, bool RGB>
+// The frame kernels' grid (k_raymarch_lit, k_relight): workgroups of 4 waves of 4x4 / 4x2 rays
+template <int RL> static dim3 ray_grid(const RayParams& p)
+{
+    constexpr int BW = 8, BH = RL == 4 ? 8 : 4;
+    return dim3((p.tile_w + BW - 1) / BW, (p.tile_h + BH - 1) / BH);
+}
+template <int DFMT, int LFMT, int RL, bool SLAB, bool TAB, bool LABELS, bool RGB, int REC>
 static hipError_t launch_lit(const RayParams& p, size_t lds_bytes, hipStream_t s)
 {
-    constexpr int BW = 8, BH = RL == 4 ? 8 : 4; // 4 waves of 4x4 / 4x2 rays
-    const dim3 grid((p.tile_w + BW - 1) / BW, (p.tile_h + BH - 1) / BH), block(256);
-    if (p.data_addr_mode == ADDR_CLAMP) hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_CLAMP, RL, SLAB, TAB, LABELS, RGB>), grid, block, lds_bytes, s, p);
-    else hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_WRAP, RL, SLAB, TAB, LABELS, RGB>), grid, block, lds_bytes, s, p);
+    const dim3 grid = ray_grid<RL>(p), block(256);
+    if (p.data_addr_mode == ADDR_CLAMP) hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_CLAMP, RL, SLAB, TAB, LABELS, RGB, REC>), grid, block, lds_bytes, s, p);
+    else hipLaunchKernelGGL((k_raymarch_lit<DFMT, LFMT, ADDR_WRAP, RL, SLAB, TAB, LABELS, RGB, REC>), grid, block, lds_bytes, s, p);
     return hipGetLastError();
 }
-template <int DFMT, int LFMT, int RL, bool LABELS, bool RGB>
+#ifndef TBRM_RAY_ONLY_UNIT
+// the offset tables (k_raymarch_lit TAB): a step of at most one texel along every axis — then no sample's base tap lies below
+// -2 or above n — and tables of at most 16 KiB (six workgroups per CU keep their place)
+bool ray_tables_for(const RayParams& p)
+{
+    const size_t tab_bytes = (size_t) ray_tab_entries(p.data.nx, p.data.ny, p.data.nz) * sizeof(uint2);
+    return !p.slab_on && p.tab != nullptr && tune(TUNE_RAY_TABLES) != 0 && (float) std::max(p.data.nx, std::max(p.data.ny, p.data.nz)) <= p.steps && tab_bytes <= 16 * 1024;
+}
+#endif
+template <int DFMT, int LFMT, int RL, bool LABELS, bool RGB, int REC>
 static hipError_t launch_ray3(const RayParams& p, hipStream_t s)
 {
     // LABELS: the colour-table contributions and the exchanged label bytes, behind the tables (4.5 KiB)
     constexpr size_t lab_bytes = LABELS ? 256 * sizeof(float4) + 256 * sizeof(short) : 0;
     if (p.slab_on) {
-        if constexpr (LABELS || RGB) return hipErrorInvalidValue; // (the host refuses slab stages while labels are attached, and on colour handles)
-        else return launch_lit<DFMT, LFMT, RL, true, false, false, false>(p, 0, s);
+        if constexpr (LABELS || RGB || REC != REC_OFF) return hipErrorInvalidValue; // (the host refuses slab stages while labels are attached, and on colour handles)
+        else return launch_lit<DFMT, LFMT, RL, true, false, false, false, REC_OFF>(p, 0, s);
     }
-    // the offset tables (k_raymarch_lit TAB): a step of at most one texel along every axis — then no sample's base tap lies below
-    // -2 or above n — and tables of at most 16 KiB (six workgroups per CU keep their place)
     const size_t tab_bytes = (size_t) ray_tab_entries(p.data.nx, p.data.ny, p.data.nz) * sizeof(uint2);
-    const bool tab = p.tab != nullptr && tune(TUNE_RAY_TABLES) != 0 && (float) std::max(p.data.nx, std::max(p.data.ny, p.data.nz)) <= p.steps && tab_bytes <= 16 * 1024;
-    if (tab) return launch_lit<DFMT, LFMT, RL, false, true, LABELS, RGB>(p, tab_bytes + lab_bytes, s);
-    return launch_lit<DFMT, LFMT, RL, false, false, LABELS, RGB>(p, lab_bytes, s);
+    if (ray_tables_for(p)) return launch_lit<DFMT, LFMT, RL, false, true, LABELS, RGB, REC>(p, tab_bytes + lab_bytes, s);
+    return launch_lit<DFMT, LFMT, RL, false, false, LABELS, RGB, REC>(p, lab_bytes, s);
 }
-template <int DFMT, int LFMT, bool RGB>
-static hipError_t launch_ray2(const RayParams& p, hipStream_t s)
+#ifndef TBRM_RAY_ONLY_UNIT
+int ray_lanes_for(const RayParams& p)
 {
     // Lanes per ray, measured on MI355X (ms per frame; 2 lanes: 0.85 / 0.64 / 0.27, 16 lanes: 0.80 / 1.50 / 0.15):
     //                     config 3 (1024^2 rays,   config 5 (2048^2,   config 2 (512^2,   config 4 (1024^2,
@@ -575,32 +601,161 @@ static hipError_t launch_ray2(const RayParams& p, hipStream_t s)
     // want 8. The rule: rays x (512 / steps) <= 700 k.
     const double load = (double) p.tile_w * (double) p.tile_h * 512.0 / (double) (p.steps > 1.0f ? p.steps : 1.0f);
     const int forced = tune(TUNE_RAY_LANES);
-    const int rl = forced ? forced : (load <= 700000.0 ? 8 : 4);
+    return (forced ? forced : (load <= 700000.0 ? 8 : 4)) == 8 ? 8 : 4;
+}
+#endif
+template <int DFMT, int LFMT, bool RGB, int REC>
+static hipError_t launch_ray2(const RayParams& p, hipStream_t s)
+{
+    const int rl = ray_lanes_for(p);
     if constexpr (RGB) {
         if (p.labels || !p.light_g || !p.light_b) return hipErrorInvalidValue; // (the host refuses label volumes on colour handles)
-        return rl == 8 ? launch_ray3<DFMT, LFMT, 8, false, true>(p, s) : launch_ray3<DFMT, LFMT, 4, false, true>(p, s);
+        return rl == 8 ? launch_ray3<DFMT, LFMT, 8, false, true, REC>(p, s) : launch_ray3<DFMT, LFMT, 4, false, true, REC>(p, s);
+    } else if constexpr (REC != REC_OFF) {
+        if (p.labels) return hipErrorInvalidValue; // (frames with a label step are not recorded)
+        return rl == 8 ? launch_ray3<DFMT, LFMT, 8, false, false, REC>(p, s) : launch_ray3<DFMT, LFMT, 4, false, false, REC>(p, s);
     } else {
-        if (p.labels) return rl == 8 ? launch_ray3<DFMT, LFMT, 8, true, false>(p, s) : launch_ray3<DFMT, LFMT, 4, true, false>(p, s);
-        return rl == 8 ? launch_ray3<DFMT, LFMT, 8, false, false>(p, s) : launch_ray3<DFMT, LFMT, 4, false, false>(p, s);
+        if (p.labels) return rl == 8 ? launch_ray3<DFMT, LFMT, 8, true, false, REC>(p, s) : launch_ray3<DFMT, LFMT, 4, true, false, REC>(p, s);
+        return rl == 8 ? launch_ray3<DFMT, LFMT, 8, false, false, REC>(p, s) : launch_ray3<DFMT, LFMT, 4, false, false, REC>(p, s);
     }
 }
-template <int DFMT, bool RGB>
+template <int DFMT, bool RGB, int REC>
 static hipError_t launch_ray1(const RayParams& p, hipStream_t s)
 {
-    return p.lv_fmt == FMT_U8 ? launch_ray2<DFMT, FMT_U8, RGB>(p, s) : launch_ray2<DFMT, FMT_F32, RGB>(p, s);
+    return p.lv_fmt == FMT_U8 ? launch_ray2<DFMT, FMT_U8, RGB, REC>(p, s) : launch_ray2<DFMT, FMT_F32, RGB, REC>(p, s);
 }
-template <bool RGB>
+template <bool RGB, int REC = REC_OFF>
 static hipError_t launch_ray0(const RayParams& p, hipStream_t s)
 {
     if (p.tile_w <= 0 || p.tile_h <= 0) return hipSuccess;
     switch (p.data.fmt) {
-        case FMT_U8: return launch_ray1<FMT_U8, RGB>(p, s);
-        case FMT_U16: return launch_ray1<FMT_U16, RGB>(p, s);
-        default: return launch_ray1<FMT_F32, RGB>(p, s);
+        case FMT_U8: return launch_ray1<FMT_U8, RGB, REC>(p, s);
+        case FMT_U16: return launch_ray1<FMT_U16, RGB, REC>(p, s);
+        default: return launch_ray1<FMT_F32, RGB, REC>(p, s);
     }
 }
-#ifdef TBRM_RAY_RGB_UNIT
+#if defined(TBRM_RAY_RGB_UNIT)
 hipError_t launch_raymarch_rgb(const RayParams& p, hipStream_t s) { return launch_ray0<true>(p, s); }
+#elif defined(TBRM_RAY_REC_UNIT)
+hipError_t launch_raymarch_recording(const RayParams& p, bool fill, hipStream_t s)
+{
+    return fill ? launch_ray0<false, REC_FILL>(p, s) : launch_ray0<false, REC_COUNT>(p, s);
+}
+
+// ---- k_view_scan: the count form's per-wave trip counts -> each wave's first trip, the total, and whether the arena holds it -------
+__global__ __launch_bounds__(1024) void k_view_scan(const RayRecord rec, uint32_t n_waves, uint32_t cap_trips)
+{
+    // (64-bit sums: a total beyond 2^32 trips must read as "does not fit", not wrap; the offsets of such a view are never used.
+    // Each thread walks a contiguous run of counts: uncoalesced, and run once per view)
+    __shared__ unsigned long long s_sum[1024];
+    const uint32_t per = (n_waves + 1023u) / 1024u;
+    const uint32_t w0 = (uint32_t) min((unsigned long long) threadIdx.x * per, (unsigned long long) n_waves), w1 = (uint32_t) min((unsigned long long) w0 + per, (unsigned long long) n_waves);
+    unsigned long long sum = 0;
+    for (uint32_t w = w0; w < w1; ++w) sum += rec.counts[w];
+    s_sum[threadIdx.x] = sum;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) { // inclusive scan of the threads' sums
+        const unsigned long long v = (int) threadIdx.x >= d ? s_sum[threadIdx.x - d] : 0ull;
+        __syncthreads();
+        s_sum[threadIdx.x] += v;
+        __syncthreads();
+    }
+    unsigned long long at = s_sum[threadIdx.x] - sum;
+    for (uint32_t w = w0; w < w1; ++w) { rec.offsets[w] = (uint32_t) at; at += rec.counts[w]; }
+    if (threadIdx.x == 1023) {
+        const unsigned long long total = s_sum[1023];
+        rec.meta[0] = (uint32_t) min(total, 0xffffffffull);
+        rec.meta[1] = total <= cap_trips ? 1u : 0u;
+    }
+}
+hipError_t launch_view_scan(const RayRecord& rec, uint32_t n_waves, uint32_t cap_trips, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_view_scan, dim3(1), dim3(1024), 0, s, rec, n_waves, cap_trips);
+    return hipGetLastError();
+}
+
+// ---- k_relight: the frame of an unchanged view from its records ------------------------------------------------------------------
+// Everything of a sample but its light is a function of the view (camera, tile, steps, volume, window, transfer function, clip plane):
+// the recording forms of k_raymarch_lit kept, for every trip of a wave that had something to accumulate, each lane's (colour, corrected
+// opacity) and the saturated position its light is sampled at. A wave here is the march's wave (same grid, same ray_of_wave, same
+// ray_wave_number): it walks its records in order, fetches and filters the 8 light taps of the lanes that have a step to take (the
+// general path of the march's light look-up: texel_split_bounded + tap_offsets<ADDR_WRAP>, which the shared-grid shortcut equals bit
+// for bit), forms x = ((cs.rgb l) a, a) and runs the march's own stage 4. The alpha channel and the early exit never see the light,
+// so the steps taken and the exits are the march's. Trip t + 1's record is requested before trip t is worked on.
+struct RelightTrip { int base; float4 c; float sp0, sp1, sp2; };
+__device__ __forceinline__ RelightTrip relight_load(const RayRecord& rec, size_t trip, int lane)
+{
+    const char* const row = rec.rows + trip * kRayRecordRowBytes;
+    const float* const sp = reinterpret_cast<const float*>(row + 64 * sizeof(float4));
+    return RelightTrip{rec.base[trip], reinterpret_cast<const float4*>(row)[lane], sp[lane], sp[64 + lane], sp[128 + lane]};
+}
+template <int LFMT, int kRayLanes>
+__global__ __launch_bounds__(256) void k_relight(const RayParams p)
+{
+    constexpr int LSH = kRayLanes == 4 ? 2 : 3;
+    __shared__ float4 s_x[256];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = lane & (kRayLanes - 1), r = lane >> LSH;
+    int i, j, px, py;
+    ray_of_wave<kRayLanes>(p, wave, r, i, j);
+    const bool valid = tile_pixel_at(p, i, j, px, py);
+    Ray ray;
+    cube_setup(p, valid ? px : p.tile_x0, valid ? py : p.tile_y0, ray);
+    const March m = march_setup(p, ray, px, py, valid);
+    const int max_steps = m.max_steps, n_samples = m.n_samples;
+
+    const float lnx = (float) p.lv_dims[0], lny = (float) p.lv_dims[1], lnz = (float) p.lv_dims[2];
+    const VolumeDev lightv{p.light, p.lv_dims[0], p.lv_dims[1], p.lv_dims[2], LFMT, p.lv_bnx, p.lv_bnxy, p.lv_wrap_layer, p.lv_wrap_shift};
+    float le[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    bool done = n_samples == 0;
+    float4* const xs = s_x + (threadIdx.x & ~(kRayLanes - 1));
+    // (what the shared stage 4 names for the label step, which a relit frame never has)
+    constexpr bool LABELS = false;
+    [[maybe_unused]] short* const s_lb = nullptr;
+    [[maybe_unused]] const float4* const s_lab = nullptr;
+    [[maybe_unused]] const int lab = -1;
+    [[maybe_unused]] const float final_step = 0.0f;
+
+    const uint32_t w = ray_wave_number();
+    const uint32_t n = p.rec.counts[w];
+    const size_t first = p.rec.offsets[w];
+    RelightTrip next{};
+    if (n > 0) next = relight_load(p.rec, first, lane);
+    for (uint32_t trip = 0; trip < n; ++trip) { // (the included stage 4 has a loop variable t of its own)
+        const RelightTrip cur = next;
+        if (trip + 1 < n) next = relight_load(p.rec, first + trip + 1, lane);
+        float4 x = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+        if (cur.c.w >= 0.0f || cur.c.w != cur.c.w) {
+            int lx, ly, lz;
+            float gx, gy, gz;
+            texel_split_bounded(cur.sp0, lnx, lx, gx);
+            texel_split_bounded(cur.sp1, lny, ly, gy);
+            texel_split_bounded(cur.sp2, lnz, lz, gz);
+            RawTaps<LFMT> ltaps;
+            ltaps.issue(p.light, tap_offsets<ADDR_WRAP, false>(lightv, lx, ly, lz));
+            const float l = ltaps.filter(gx, gy, gz);
+            x = make_float4((cur.c.x * l) * cur.c.w, (cur.c.y * l) * cur.c.w, (cur.c.z * l) * cur.c.w, cur.c.w);
+        }
+        const int base = cur.base;
+        {
+#include "tbrm_ray_replay.inc"
+        }
+        if (base + kRayLanes >= n_samples) done = true;
+    }
+    if (valid && b == 0) reinterpret_cast<float4*>(p.out)[(size_t) j * p.tile_w + i] = make_float4(le[0], le[1], le[2], le[3]);
+}
+template <int LFMT, int RL> static hipError_t launch_relight2(const RayParams& p, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_relight<LFMT, RL>), ray_grid<RL>(p), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+hipError_t launch_relight(const RayParams& p, hipStream_t s) // (the lanes per ray the records were written with: the key holds them)
+{
+    if (p.tile_w <= 0 || p.tile_h <= 0) return hipSuccess;
+    const bool eight = ray_lanes_for(p) == 8;
+    if (p.lv_fmt == FMT_U8) return eight ? launch_relight2<FMT_U8, 8>(p, s) : launch_relight2<FMT_U8, 4>(p, s);
+    return eight ? launch_relight2<FMT_F32, 8>(p, s) : launch_relight2<FMT_F32, 4>(p, s);
+}
 #else
 hipError_t launch_raymarch(const RayParams& p, hipStream_t s) { return launch_ray0<false>(p, s); }
 
@@ -806,6 +961,6 @@ __global__ __launch_bounds__(256) void k_count_samples(const RayParams p)
 
 hipError_t launch_count_samples(const RayParams& p, hipStream_t s) { return launch_pixel_blocks(k_count_samples, p, s); }
 
-#endif // TBRM_RAY_RGB_UNIT
+#endif // the unit
 
 } // namespace tbrm

@@ -192,6 +192,26 @@ struct FactorScratch {
     bool idle_recorded = false;     // ... and whether that sweep recorded ev_idle (else: the operator's op_done event)
 };
 
+// The view cache (tbrm_api_render.cpp; DESIGN.md 4.1 "Relit frames"). Of what k_raymarch_lit does per sample only the light taps and
+// the accumulation depend on the light volume's contents; everything else is a function of what `key` holds. ONE view per handle:
+// the frames of an unchanged key go plain -> count -> fill -> relit (k_relight, from the records in `arena`); any other key starts
+// over at plain, so a host whose camera moves every frame only ever runs the march it ran before. Light operators leave it alone.
+struct ViewCache {
+    enum State { kNone, kPlain, kCounted, kFilled, kReady, kTooLarge };
+    State state = kNone;
+    tbrm::RayParams key;            // zero-filled block with the frame's RayParams copied in, `out` and `rec` cleared
+    int lanes = 0, tables = 0;      // what launch_ray2 / launch_ray3 chose for it
+    uint64_t data_gen = 0, tf_gen = 0;
+    char* arena = nullptr;          // the records: [counts | offsets | meta | base words | rows] of the current view
+    size_t arena_bytes = 0;
+    bool arena_tried = false;       // (a handle allocates it once: tbrm_resources_reserve, or its first count frame)
+    uint32_t* meta_host = nullptr;  // pinned: {total trips, fits}, copied behind the fill frame ...
+    hipEvent_t ev_meta = nullptr;   // ... and followed by this event, which later frames query and never wait for
+    tbrm::RayRecord rec{};          // the arena as the kernels see it
+    uint32_t n_waves = 0, cap_trips = 0;
+    uint64_t stats[6]{};            // tbrm_view_cache_stats
+};
+
 struct tbrm_resources {
     tbrm_resources_desc desc{};
     struct Dims { int v[3]; operator const int*() const { return v; } };
@@ -332,6 +352,8 @@ struct tbrm_resources {
     float* d_out = nullptr; // staging for the host-pointer raymarch variant
     size_t out_bytes = 0;
 
+    ViewCache view;
+
     struct SlabOp* slab_op = nullptr; // the slab-partitioned light operation in flight (tbrm_slab_*)
 
     hipEvent_t ev[2][2]{};
@@ -417,6 +439,10 @@ int ensure_skipping(tbrm_resources* r);
 // boxes, or as many bricks as the volume has — minmax_valid dropped so that ensure_skipping rebuilds all of it
 int refresh_dirty_minmax(tbrm_resources* r, const BrickParams& whole);
 int raymarch_clip_mode(const float cc[3], const float cd[3]);
+// the view cache (tbrm_api_render.cpp): its arena, pinned word and event, once per handle, under the factor-cache arena's free-memory
+// rule (eager: asked for by tbrm_resources_reserve); and their release (the stream must be idle)
+void ensure_view_arena(tbrm_resources* r, bool eager);
+void release_view_cache(tbrm_resources* r);
 // volume statistics (tbrm_api_volume_stats.cpp): the scratch of the statistics calls, taken once (counted: tbrm_path_counters [12])
 int ensure_stats_scratch(tbrm_resources* r, bool counted = true);
 // label overlay (tbrm_api_labels.cpp)

@@ -4,7 +4,7 @@ why the HBM roofline fraction of a kernel is what it is.
     python tools/issue_roofline.py <out.json> <counter_collection.csv> [...]
     python tools/issue_roofline.py <out.json> --from-json <earlier out.json>     (recompute the ratios from its per-launch sums)
 
-Per kernel family (k_light_sweep, k_light_occlusion, k_raymarch_lit; averaged per launch, summed over the chip). GRBM_GUI_ACTIVE
+Per kernel family (k_light_sweep, k_light_occlusion, k_raymarch_lit, k_relight; averaged per launch, summed over the chip). GRBM_GUI_ACTIVE
 is summed over the 8 XCDs (a 0.58 ms frame reads 11.0 M = 8 x 0.58 ms x 2.37 GHz), so a launch lasts GRBM_GUI_ACTIVE / 8 cycles;
 SQ_WAVE_CYCLES and SQ_WAIT_INST_ANY count in units of 4 cycles.
   valu_issue_frac   SQ_INSTS_VALU x 4 cycles / (1024 SIMDs x launch cycles): share of the chip's VALU issue slots used, at the
@@ -20,7 +20,7 @@ import csv
 import json
 import sys
 
-FAMILIES = ("k_light_sweep", "k_light_occlusion", "k_raymarch_lit", "k_light_chain")
+FAMILIES = ("k_light_sweep", "k_light_occlusion", "k_raymarch_lit", "k_relight", "k_light_chain")
 
 
 def main():

@@ -22,6 +22,13 @@ def per_kernel(path, counter):
     return acc
 
 
+FRAME_KERNELS = ("k_raymarch_lit", "k_relight")  # a step's frame: the march, or the same frame relit from the view cache's records
+
+
+def is_frame(name):
+    return any(k in name for k in FRAME_KERNELS)
+
+
 LIGHT_KERNELS = ("k_light_sweep", "k_light_chain", "k_light_occlusion", "k_occ_flags", "k_occ_compact", "k_propagate_slice")
 
 
@@ -38,7 +45,7 @@ def operator_runs(path, counter, scale):
     rows.sort()
     runs, cur, modes, seen_frame = [], 0.0, set(), False
     for _, name, value in rows:
-        if "k_raymarch_lit" in name:
+        if is_frame(name):
             if seen_frame and modes:
                 kind = "cached" if "3" in modes else ("both" if "1" in modes else ("remove+add" if "0" in modes else "from cache"))
                 runs.append((cur * scale, kind))
@@ -68,13 +75,15 @@ def signature(path, counter):
     rows.sort()
     counts, frames = collections.Counter(), 0
     for _, name in rows:
-        if "k_raymarch_lit" in name:
+        if is_frame(name):
             frames += 1
         if frames == 0:
             continue  # (the setup's ResetAllLights)
-        for fam in ("k_light_sweep", "k_light_occlusion", "k_raymarch_lit"):
+        for fam in ("k_light_sweep", "k_light_occlusion"):
             if fam in name:
                 counts[fam] += 1
+        if is_frame(name):  # (bench.py checks this family against tbrm_path_counters' "raymarch", which counts every frame call)
+            counts["k_raymarch_lit"] += 1
     # (the light kernels behind the last frame belong to no step: none in bench.py --timed-only)
     steps = max(frames, 1)
     return {"kernel_source_hash": kernel_source_hash(), "steps": frames, "launches_per_step": {k: round(v / steps, 3) for k, v in sorted(counts.items())}}
@@ -95,7 +104,7 @@ def main():
                      "hbm_bytes_per_launch": rd + wr, "fetch_size_raw_kib": f / max(nf, 1), "write_size_raw_kib": w / max(nw, 1)}
     # per operator call (see operator_runs); reads doubled like the per-kernel figures
     reads, writes = operator_runs(sys.argv[1], "FETCH_SIZE", 2.0 * 1024), operator_runs(sys.argv[2], "WRITE_SIZE", 1024.0)
-    ray = [v for k, v in out.items() if "k_raymarch_lit" in k]
+    ray = [v for k, v in out.items() if is_frame(k)]
     if ray and reads and len(reads) == len(writes):
         calls = [(r[0] + w[0], r[1]) for r, w in zip(reads, writes)]
         by_kind = collections.defaultdict(list)
