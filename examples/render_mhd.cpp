@@ -5,10 +5,12 @@
 //
 //   g++ -std=c++17 -O2 -I include examples/render_mhd.cpp -o render_mhd -L tbraymarcherplugin_amd/lib -ltbrm -lz
 //       (plus -Wl,-rpath,$PWD/tbraymarcherplugin_amd/lib -Wl,-rpath,/opt/rocm/lib to run it in place)
-//   ./render_mhd volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]]
+//   ./render_mhd volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y]
 //       --light-color: the key light's colour (components in [0, 1]) on an RGB light volume (include/tbrm_color_lights.h); the fill stays white
 //       --auto-window: the window comes from the data (ARaymarchVolume::AutoWindow, include/tbrm_volume_stats.h): the span between
 //                      the LOW and HIGH percentiles of the value histogram, 0.01,0.99 when not given
+//       --pick: what the frame's pixel (X, Y) shows first (ARaymarchVolume::PickVolume, include/tbrm_hit.h): the spot where the ray's
+//                      accumulated opacity passes 0.5, printed as one "pick" line
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -33,6 +35,16 @@ int main(int argc, char** argv)
             argc -= 1;
             break;
         }
+    int pick_x = -1, pick_y = -1;
+    bool pick = false;
+    for (int i = 1; i + 1 < argc; ++i)
+        if (!std::strcmp(argv[i], "--pick")) {
+            if (std::sscanf(argv[i + 1], "%d,%d", &pick_x, &pick_y) != 2) { argc = 0; break; }
+            pick = true;
+            for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
+            argc -= 2;
+            break;
+        }
     for (int i = 1; i + 1 < argc; ++i) // the option and its value leave the positional arguments
         if (!std::strcmp(argv[i], "--light-color")) {
             if (std::sscanf(argv[i + 1], "%f,%f,%f", &key_color[0], &key_color[1], &key_color[2]) != 3) { argc = 0; break; }
@@ -42,7 +54,7 @@ int main(int argc, char** argv)
             break;
         }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y]\n", argv[0]);
         return 2;
     }
     const int width = argc > 3 ? std::atoi(argv[3]) : 512, height = argc > 4 ? std::atoi(argv[4]) : 512;
@@ -110,5 +122,15 @@ int main(int argc, char** argv)
     std::fwrite(rgb.data(), 1, rgb.size(), f);
     std::fclose(f);
     std::printf("wrote %s (%d x %d, mean alpha %.4f)\n", argv[2], width, height, coverage / ((double) width * height));
+    if (pick) {
+        FVolumeHit hit;
+        if (!volume.PickVolume(cam, pick_x, pick_y, 0.5f, hit)) {
+            std::fprintf(stderr, "pick failed: %s\n", tbrm_last_error());
+            return 1;
+        }
+        if (hit.bHit) std::printf("pick %d,%d hit sample %d world %.9g %.9g %.9g depth %.9g value %.9g label %d\n", pick_x, pick_y, hit.Sample,
+                                  hit.WorldPosition.x, hit.WorldPosition.y, hit.WorldPosition.z, hit.Depth, (double) hit.Value, hit.Label);
+        else std::printf("pick %d,%d miss\n", pick_x, pick_y);
+    }
     return 0;
 }

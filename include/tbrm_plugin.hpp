@@ -19,6 +19,7 @@
 #include "tbrm_color_lights.h"
 #include "tbrm_volume_region.h"
 #include "tbrm_volume_stats.h"
+#include "tbrm_hit.h"
 
 #include <algorithm>
 #include <cmath>
@@ -252,6 +253,17 @@ struct ARaymarchClipPlane { // (location, -up) (RaymarchClipPlane.cpp:32-35)
     FVector Location{0, 0, 0};
     FVector UpVector{0, 0, 1};
     FClippingPlaneParameters GetCurrentParameters() const { return FClippingPlaneParameters(Location, FVector{-UpVector.x, -UpVector.y, -UpVector.z}); }
+};
+
+// What a ray of the lit march meets first (include/tbrm_hit.h; no counterpart in the reference, whose VR controllers point at the
+// cube mesh): ARaymarchVolume::PickVolume
+struct FVolumeHit {
+    bool bHit = false;
+    FVector WorldPosition{0, 0, 0};
+    double Depth = 0.0;  // along the camera's forward axis, world units (the scene-depth convention); no hit: +inf
+    float Value = 0.0f;  // the filtered data value there, in the window's units
+    int Label = -1;      // the label volume's voxel there; -1 without a label volume or a hit
+    int Sample = -1;     // the sample's index along the ray
 };
 
 class ARaymarchVolume {
@@ -510,6 +522,37 @@ public:
         const tbrm_world_params w = WorldParameters.abi();
         ++Stats.Frames;
         return tbrm_raymarch_octree(RaymarchResources.Handle, &Camera, &tile, &rp, &w, OctreeVolumeMip, OutRGBA) == TBRM_OK;
+    }
+
+    // Picking and depth (include/tbrm_hit.h): what the lit march of this volume — current window, transfer function, clip plane,
+    // labels and step count, no jitter — first gets opaque at, where "opaque" is an accumulated opacity above Threshold (0 .. 0.95).
+    // Neither call touches the illumination or counts as a frame.
+    bool PickVolume(const tbrm_camera& Camera, int Px, int Py, float Threshold, FVolumeHit& Out)
+    {
+        Out = FVolumeHit{};
+        if (!RaymarchResources.bIsInitialized) return false;
+        const tbrm_raymarch_params rp{RaymarchingSteps, -1, 1, 0};
+        const tbrm_world_params w = WorldParameters.abi();
+        tbrm_hit h{};
+        double xyz[3] = {0, 0, 0};
+        if (tbrm_pick(RaymarchResources.Handle, &Camera, Px, Py, &rp, &w, Threshold, &h, xyz, &Out.Depth) != TBRM_OK) return false;
+        Out.bHit = h.sample >= 0;
+        Out.WorldPosition = FVector{xyz[0], xyz[1], xyz[2]};
+        Out.Value = h.value;
+        Out.Label = h.label;
+        Out.Sample = h.sample;
+        return true;
+    }
+    // The visible surface as a depth buffer, Camera.width x Camera.height floats in the convention of the march's own scene depth
+    // (+inf where a ray meets nothing): what scene geometry is composited against.
+    bool RenderHitDepth(const tbrm_camera& Camera, float* OutDepth, float Threshold)
+    {
+        if (!RaymarchResources.bIsInitialized || !OutDepth) return false;
+        const tbrm_tile tile{0, 0, Camera.width, Camera.height, 1, 0};
+        const tbrm_raymarch_params rp{RaymarchingSteps, -1, 1, 0};
+        const tbrm_world_params w = WorldParameters.abi();
+        std::vector<tbrm_hit> Hits((size_t) (Camera.width > 0 ? Camera.width : 0) * (size_t) (Camera.height > 0 ? Camera.height : 0));
+        return tbrm_raymarch_hits(RaymarchResources.Handle, &Camera, &tile, &rp, &w, Threshold, Hits.data(), OutDepth) == TBRM_OK;
     }
 
     // What the cube mesh would show with the currently selected material (SwitchRenderer, :786-800).

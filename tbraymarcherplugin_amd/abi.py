@@ -185,6 +185,17 @@ VIEW_CACHE_SYMBOLS = ["tbrm_view_cache_abi_version", "tbrm_view_cache_stats"]
 
 VIEW_CACHE_ABI_VERSION = 1  # TBRM_VIEW_CACHE_ABI_VERSION of include/tbrm_view_cache.h
 
+# every symbol include/tbrm_hit.h declares (hit maps and picking; tests/test_hit_reference.py checks the header against this list)
+HIT_SYMBOLS = [
+    "tbrm_hit_abi_version", "tbrm_raymarch_hits_device", "tbrm_raymarch_hits", "tbrm_pick", "tbrm_host_hits_to_world", "tbrm_hit_counters",
+]
+
+HIT_ABI_VERSION = 1  # TBRM_HIT_ABI_VERSION of include/tbrm_hit.h
+
+# tbrm_hit, as a numpy record
+HIT_DTYPE = np.dtype([("uvw", np.float32, (3,)), ("sample", np.int32), ("alpha", np.float32), ("value", np.float32), ("label", np.int32),
+                      ("full_steps", np.int32)])
+
 _lib = None
 
 
@@ -316,6 +327,15 @@ def load():
         raise ImportError(f"{LIB_PATH} has view-cache ABI version {have}, this binding is written against {VIEW_CACHE_ABI_VERSION}: "
                           "rebuild it (`python tbraymarcherplugin_amd/build.py --force`)")
     lib.tbrm_view_cache_stats.argtypes = [vp, P(C.c_uint64 * 6)]
+    have = lib.tbrm_hit_abi_version() if hasattr(lib, "tbrm_hit_abi_version") else -1
+    if have != HIT_ABI_VERSION:
+        raise ImportError(f"{LIB_PATH} has hit ABI version {have}, this binding is written against {HIT_ABI_VERSION}: rebuild it "
+                          "(`python tbraymarcherplugin_amd/build.py --force`)")
+    lib.tbrm_raymarch_hits_device.argtypes = [vp, P(Camera), P(Tile), P(RaymarchParams), P(WorldParams), C.c_float, vp, vp, vp]
+    lib.tbrm_raymarch_hits.argtypes = [vp, P(Camera), P(Tile), P(RaymarchParams), P(WorldParams), C.c_float, vp, vp]
+    lib.tbrm_pick.argtypes = [vp, P(Camera), C.c_int32, C.c_int32, P(RaymarchParams), P(WorldParams), C.c_float, vp, P(C.c_double * 3), P(C.c_double)]
+    lib.tbrm_host_hits_to_world.argtypes = [P(WorldParams), P(Camera), vp, C.c_size_t, vp, vp]
+    lib.tbrm_hit_counters.argtypes = [vp, P(C.c_uint64 * 3)]
     _lib = lib
     return lib
 
@@ -407,6 +427,17 @@ def window_from_histogram(counts, lo_edge, hi_edge, p_low=0.01, p_high=0.99):
     check(load().tbrm_host_window_from_histogram(counts.ctypes.data, int(counts.size), float(lo_edge), float(hi_edge), float(p_low), float(p_high),
                                                  C.byref(out)))
     return out
+
+
+def hits_to_world(world, camera, hits):
+    """tbrm_host_hits_to_world: (world positions float64 [..., 3], depths along camera.forward float64 [...]) of HIT_DTYPE records;
+    records without a hit give 0, 0, 0 and +inf. Host arithmetic: needs no device."""
+    shape = np.shape(hits)
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE).reshape(-1)
+    xyz = np.empty((hits.size, 3), dtype=np.float64)
+    depth = np.empty(hits.size, dtype=np.float64)
+    check(load().tbrm_host_hits_to_world(C.byref(world), C.byref(camera), hits.ctypes.data, hits.size, xyz.ctypes.data, depth.ctypes.data))
+    return xyz.reshape(shape + (3,)), depth.reshape(shape)
 
 
 def make_default_label_colors():
@@ -622,6 +653,48 @@ class Resources:
         out = (C.c_uint64 * 4)()
         check(self.lib.tbrm_volume_stats_counters(self.handle, C.byref(out)))
         return {k: int(out[i]) for i, k in enumerate(self.VOLUME_STATS_COUNTERS)}
+
+    # hit maps and picking (include/tbrm_hit.h)
+    def raymarch_hits(self, camera, tile, params, world, threshold, scene_depth=None, depth=False):
+        """the tile's hit records (HIT_DTYPE [h, w]); depth=True: (records, float32 [h, w] depths along camera.forward, +inf without a
+        hit). scene_depth: a float32 framebuffer-sized array the rays stop at (goes through device memory: needs torch)"""
+        hits = np.empty((tile.h, tile.w), dtype=HIT_DTYPE)
+        dep = np.empty((tile.h, tile.w), dtype=np.float32) if depth else None
+        if scene_depth is None:
+            check(self.lib.tbrm_raymarch_hits(self.handle, C.byref(camera), C.byref(tile), C.byref(params), C.byref(world), float(threshold),
+                                              hits.ctypes.data, dep.ctypes.data if depth else None))
+        else:
+            import torch
+            dev = torch.device("cuda", self.device)
+            d_scene = torch.from_numpy(np.ascontiguousarray(scene_depth, dtype=np.float32)).to(dev)
+            d_hits = torch.empty(max(hits.nbytes, 1), dtype=torch.uint8, device=dev)
+            d_dep = torch.empty(max(hits.size, 1), dtype=torch.float32, device=dev)
+            self.raymarch_hits_device(camera, tile, params, world, threshold, d_hits.data_ptr(), d_dep.data_ptr() if depth else None,
+                                      d_scene.data_ptr())
+            self.flush()
+            hits = d_hits.cpu().numpy()[:hits.nbytes].view(HIT_DTYPE).reshape(tile.h, tile.w)
+            dep = d_dep.cpu().numpy()[:hits.size].reshape(tile.h, tile.w) if depth else None
+        return (hits, dep) if depth else hits
+
+    def raymarch_hits_device(self, camera, tile, params, world, threshold, hits_ptr, depth_ptr=None, scene_depth_ptr=None):
+        """enqueues the hit map into device memory: tile.h * tile.w records of 32 bytes at hits_ptr, floats at depth_ptr (or None)"""
+        check(self.lib.tbrm_raymarch_hits_device(self.handle, C.byref(camera), C.byref(tile), C.byref(params), C.byref(world), float(threshold),
+                                                 C.c_void_p(scene_depth_ptr), C.c_void_p(hits_ptr), C.c_void_p(depth_ptr)))
+
+    def pick(self, camera, px, py, params, world, threshold):
+        """tbrm_pick: (the pixel's record as a HIT_DTYPE scalar, world position float64 [3], depth)"""
+        hit = np.zeros(1, dtype=HIT_DTYPE)
+        xyz, depth = (C.c_double * 3)(), C.c_double()
+        check(self.lib.tbrm_pick(self.handle, C.byref(camera), int(px), int(py), C.byref(params), C.byref(world), float(threshold),
+                                 hit.ctypes.data, C.byref(xyz), C.byref(depth)))
+        return hit[0], np.array(xyz[:], dtype=np.float64), float(depth.value)
+
+    HIT_COUNTERS = ("hit_maps", "picks", "launches")
+
+    def hit_counters(self):
+        out = (C.c_uint64 * 3)()
+        check(self.lib.tbrm_hit_counters(self.handle, C.byref(out)))
+        return {k: int(out[i]) for i, k in enumerate(self.HIT_COUNTERS)}
 
     def is_initialized(self):
         return bool(self.lib.tbrm_resources_is_initialized(self.handle))

@@ -534,6 +534,7 @@ int tbrm_resources_destroy(tbrm_resources* r)
     for (uint8_t* d : r->d_dist) (void) hipFree(d);
     release_labels(r);
     (void) hipFree(r->d_stats);
+    (void) hipFree(r->d_hit);
     (void) hipFree(r->d_alpha_prefix);
     (void) hipFree(r->d_counter);
     (void) hipFree(r->d_ray_tab);

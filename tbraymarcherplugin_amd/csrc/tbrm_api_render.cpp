@@ -14,7 +14,7 @@
 using namespace tbrm;
 using namespace tbrm_host;
 
-namespace {
+namespace tbrm_host {
 
 int build_ray_params(tbrm_resources* r, const tbrm_camera* cam, const tbrm_tile* tile, const tbrm_raymarch_params* rp,
                      const tbrm_world_params* world, RayParams& p)
@@ -70,6 +70,10 @@ int attach_skipping(tbrm_resources* r, const tbrm_raymarch_params* rp, RayParams
     p.skip_dist = r->d_dist[0];
     return TBRM_OK;
 }
+
+} // namespace tbrm_host
+
+namespace {
 
 // The host-pointer form of a frame call: checks the tile, has `march` (the call's _device form, which makes every other argument
 // check) render it into the handle's own device buffer, grown to the largest tile seen, and copies that to the caller's, complete

@@ -171,6 +171,34 @@ void host_world_to_local(const tbrm_transform& t, float m[12])
     m[9] = (float) tr.x; m[10] = (float) tr.y; m[11] = (float) tr.z;
 }
 
+// ---- hit records (include/tbrm_hit.h) -----------------------------------------------------------------------------
+
+// FTransform::TransformPosition of a position of the unit cube moved to the mesh's [-0.5, 0.5]^3: the inverse of what the
+// cube setup does to the camera (inverse_transform_position, + 0.5)
+static Vec3 unit_cube_to_world(const tbrm_transform& t, const Vec3& u)
+{
+    return rotate(t.rotation, (u - Vec3(0.5, 0.5, 0.5)) * Vec3(t.scale3d)) + Vec3(t.translation);
+}
+
+void host_hits_to_world(const tbrm_world_params& world, const tbrm_camera& cam, const tbrm_hit* hits, size_t n, double* out_xyz, double* out_depth)
+{
+    const Vec3 eye(cam.position), fwd(cam.forward);
+    for (size_t k = 0; k < n; ++k) {
+        const bool hit = hits[k].sample >= 0;
+        const Vec3 P = hit ? unit_cube_to_world(world.volume_transform, Vec3(hits[k].uvw[0], hits[k].uvw[1], hits[k].uvw[2])) : Vec3();
+        if (out_xyz) { out_xyz[3 * k] = P.x; out_xyz[3 * k + 1] = P.y; out_xyz[3 * k + 2] = P.z; }
+        if (out_depth) out_depth[k] = hit ? (P - eye).dot(fwd) : HUGE_VAL;
+    }
+}
+
+void host_hit_depth_form(const tbrm_transform& t, const tbrm_camera& cam, float dg[3], float* d0)
+{
+    const Vec3 fwd(cam.forward), scale(t.scale3d);
+    const Vec3 axes[3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    for (int c = 0; c < 3; ++c) dg[c] = (float) rotate(t.rotation, axes[c] * scale).dot(fwd); // d P / d u_c, along forward
+    *d0 = (float) (Vec3(t.translation) - Vec3(cam.position)).dot(fwd);                        // the cube's centre
+}
+
 // min over the box [lo,hi]^3 (UVW space) of dot(p - centre, dir): the smallest signed distance any sample
 // position in that box can have from the clip plane, measured along the kept direction. The callers use it to
 // prove a clip plane inert (IsCurPosClipped never true; AlphaWeight exactly 1) and drop the per-sample test.

@@ -1,6 +1,7 @@
 // tbrm_host_math.h — host parameter math (see tbrm_host_math.cpp for the reference lines each function restates).
 #pragma once
 #include "../../include/tbrm.h"
+#include "../../include/tbrm_hit.h"
 
 namespace tbrm {
 
@@ -10,6 +11,10 @@ void host_local_clipping(const tbrm_world_params& world, float center[3], float 
 float host_data_border(const tbrm_windowing_params& w, int border_mode);
 void host_world_to_local(const tbrm_transform& t, float m[12]);
 double host_min_plane_distance(const float cc[3], const float cd[3], double lo, double hi);
+// include/tbrm_hit.h: tbrm_host_hits_to_world, and the same depth as the linear form of the unit-cube position that k_raymarch_hit
+// evaluates: depth(u) = dg . (u - 0.5) + d0
+void host_hits_to_world(const tbrm_world_params& world, const tbrm_camera& cam, const tbrm_hit* hits, size_t n, double* out_xyz, double* out_depth);
+void host_hit_depth_form(const tbrm_transform& t, const tbrm_camera& cam, float dg[3], float* d0);
 
 uint16_t float_to_half(float f);
 float half_to_float(uint16_t h);

@@ -308,6 +308,15 @@ struct RayParams {
 int ray_lanes_for(const RayParams& p);   // lanes per ray: 4 or 8
 bool ray_tables_for(const RayParams& p); // the LDS offset tables (k_raymarch_lit TAB) apply
 
+// k_raymarch_hit's own arguments beside the view's RayParams (include/tbrm_hit.h; tbrm_kernels.hip compiled as the hit unit). RayParams
+// itself stays as it is: the view cache compares it as a block, and k_raymarch_lit's kernel-argument segment keeps its layout.
+struct HitParams {
+    uint4* hits;     // tile_w x tile_h records of two 16-byte words (tbrm_hit), row-major
+    float* depth;    // tile_w x tile_h floats, or null
+    float threshold; // a ray's hit: the first sample after whose steps LightEnergy.a > threshold
+    float dg[3], d0; // distance along camera.forward of a position u of the unit cube: dg . (u - 0.5) + d0, in world units
+};
+
 // Layout of RayParams::tab (built in tbrm_resources_create, copied into LDS and read by k_raymarch_lit TAB): the x, then the y, then
 // the z axis, one entry for every texel index -kRayTabApron .. n + kRayTabApron - 1 (a base tap two texels outside the volume and its
 // +1 tap still have entries), the total padded to an even count (the copy moves 16 bytes at a time).
@@ -444,6 +453,7 @@ hipError_t launch_raymarch_rgb(const RayParams& p, hipStream_t s); // (colour ha
 hipError_t launch_raymarch_recording(const RayParams& p, bool fill, hipStream_t s);
 hipError_t launch_view_scan(const RayRecord& rec, uint32_t n_waves, uint32_t cap_trips, hipStream_t s);
 hipError_t launch_relight(const RayParams& p, hipStream_t s);
+hipError_t launch_raymarch_hit(const RayParams& p, const HitParams& h, hipStream_t s); // (tbrm_kernels.hip compiled as the hit unit)
 hipError_t launch_raymarch_intensity(const RayParams& p, hipStream_t s);
 hipError_t launch_raymarch_octree(const RayParams& p, hipStream_t s);
 hipError_t launch_octree_level(const OctreeParams& p, bool base, hipStream_t s);

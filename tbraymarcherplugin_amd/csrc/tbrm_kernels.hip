@@ -14,10 +14,11 @@
 
 namespace tbrm {
 
-// Compiled three times (build.py): as it stands, with -DTBRM_RAY_RGB_UNIT=1 for k_raymarch_lit's RGB-light form alone
-// (launch_raymarch_rgb), and with -DTBRM_RAY_REC_UNIT=1 for the view cache's kernels alone (the recording forms of k_raymarch_lit,
-// k_view_scan, k_relight), so that the three sets of instantiations build side by side.
-#if defined(TBRM_RAY_RGB_UNIT) || defined(TBRM_RAY_REC_UNIT)
+// Compiled four times (build.py): as it stands, with -DTBRM_RAY_RGB_UNIT=1 for k_raymarch_lit's RGB-light form alone
+// (launch_raymarch_rgb), with -DTBRM_RAY_REC_UNIT=1 for the view cache's kernels alone (the recording forms of k_raymarch_lit,
+// k_view_scan, k_relight), and with -DTBRM_RAY_HIT_UNIT=1 for k_raymarch_hit alone (launch_raymarch_hit), so that the four sets of
+// instantiations build side by side.
+#if defined(TBRM_RAY_RGB_UNIT) || defined(TBRM_RAY_REC_UNIT) || defined(TBRM_RAY_HIT_UNIT)
 #define TBRM_RAY_ONLY_UNIT 1
 #undef TBRM_RAY_STATS // (the diagnostics build counts in the mono unit alone)
 #endif
@@ -352,79 +353,13 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
 
     // A trip is five stages: advance the position, locate the sample, shade it, exchange and replay, the wave-wide leap. They stay one
     // body, each stage a headed block: at 80 registers the allocation does not survive cutting them out (any one of them as a by-reference
-    // lambda or an inlined function gave some instantiation scratch it had not had).
+    // lambda or an inlined function gave some instantiation scratch it had not had). The stages another kernel runs as well are text
+    // included here: 1 and 2 (tbrm_ray_locate.inc) and 5 (tbrm_ray_leap.inc) with k_raymarch_hit, 4 (tbrm_ray_replay.inc) with k_relight.
     for (int base = 0; __builtin_amdgcn_ballot_w64(!done) != 0; base += kRayLanes) {
-        const int idx = base + b; // this lane's sample of the ray
-        // ---- 1. advance. CurPos += LocalCamVec before every full sample (:67): sample idx < max_steps sits idx+1 additions in, the
-        // fractional sample max_steps additions plus one scaled step
-        const int want = min(idx + 1, max_steps);
-        if (__builtin_amdgcn_ballot_w64(!done && want - adds != kRayLanes) == 0) { // mid-ray everywhere: no predication
-#pragma unroll
-            for (int t = 0; t < kRayLanes; ++t) { pos0 = pos0 + sv0; pos1 = pos1 + sv1; pos2 = pos2 + sv2; }
-            adds += kRayLanes;
-        } else {
-#pragma unroll
-            for (int t = 0; t < kRayLanes; ++t)
-                if (adds < want) { pos0 = pos0 + sv0; pos1 = pos1 + sv1; pos2 = pos2 + sv2; ++adds; }
-        }
-        float q0 = pos0, q1 = pos1, q2 = pos2, step = step_world;
-        const bool is_full = idx < max_steps;
-        const bool has = !done && idx < n_samples;
-        if (!is_full) { q0 = pos0 + (sv0 * final_step); q1 = pos1 + (sv1 * final_step); q2 = pos2 + (sv2 * final_step); step = 100.0f * final_step; }
-
-        // ---- 2. locate: does the sample have to be evaluated (live), where do its data taps lie (texel split, TAB offsets), and how far
-        // does its brick's leap distance prove the lane's next samples empty (safe_until)
         float4 x = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
         [[maybe_unused]] float4 rec_x = x;                                // REC_FILL: (cs.rgb, a) of x
         [[maybe_unused]] float rec_sp0 = 0.0f, rec_sp1 = 0.0f, rec_sp2 = 0.0f; // ... and where its light is sampled
-        bool live = has && idx > safe_until && !(p.clip_mode && is_clipped(q0, q1, q2, p.cc, p.cd));
-        if constexpr (SLAB) { // only the samples of this handle's slab
-            const int zi = min((int) (saturate_(q2) * lnz), p.lv_dims[2] - 1);
-            live = live && zi >= p.slab_z0 && zi < p.slab_z1;
-        }
-        int ix = 0, iy = 0, iz = 0;
-        float fx = 0.0f, fy = 0.0f, fz = 0.0f;
-        int lab = -1; // LABELS: the label of this lane's sample when it has a label step to take
-        // (after a trip in which no lane of the wave sampled, the lanes inside their proven-empty range look their brick up
-        // again as well: all ranges then start from here, and the wave can take the trips they share in one go — below)
-        const bool renew = eager && has && !live && idx <= safe_until;
-        TapOffsets tab_dt{}; // TAB: the data taps' offsets, out of the tables
-        if (live || renew) {
-            if constexpr (TAB) { // (the host's promise behind the tables: positions within a step of the unit cube)
-                texel_split_bounded(q0, nx, ix, fx);
-                texel_split_bounded(q1, ny, iy, fy);
-                texel_split_bounded(q2, nz, iz, fz);
-            } else {
-                texel_split(q0, nx, ix, fx);
-                texel_split(q1, ny, iy, fy);
-                texel_split(q2, nz, iz, fz);
-            }
-            uint32_t tab_brick = 0;
-            if constexpr (TAB) { // (base taps -2 .. n: the host's promise; the clamp only keeps a broken promise, and the +1 entry, inside the tables)
-                const int tx = min(max(ray_tab_index(ix), 0), ray_tab_last_base(p.data.nx));
-                const int ty = min(max(ray_tab_index(iy), 0), ray_tab_last_base(p.data.ny));
-                const int tz = min(max(ray_tab_index(iz), 0), ray_tab_last_base(p.data.nz));
-                const uint2 ax = tab_x[tx], bx1 = tab_x[tx + 1], ay = tab_y[ty], by1 = tab_y[ty + 1], az = tab_z[tz], bz1 = tab_z[tz + 1];
-                tab_dt.x0 = ax.x; tab_dt.x1 = bx1.x; tab_dt.y0 = ay.x; tab_dt.y1 = by1.x; tab_dt.z0 = az.x; tab_dt.z1 = bz1.x;
-                tab_brick = ax.y + ay.y + az.y;
-            }
-            if (p.skip_dist) { // a sample based in a brick that maps every reachable value to opacity 0 is an exact no-op
-                int dist;
-                if constexpr (TAB) dist = p.skip_dist[tab_brick];
-                else {
-                    const int bx = address<DMODE>(ix, p.data.nx) >> kBrickShift;
-                    const int by = address<DMODE>(iy, p.data.ny) >> kBrickShift;
-                    const int bz = address<DMODE>(iz, p.data.nz) >> kBrickShift;
-                    dist = p.skip_dist[(bz * p.bny + by) * p.bnx + bx];
-                }
-                live = live && dist == 0;
-                // Every brick within Chebyshev distance < dist is empty as well. From anywhere inside this brick a base
-                // tap has to move more than 8*(dist-1) texels along some axis to leave them, and a base tap moves at
-                // most 1 texel more than the position does: the lane's samples up to that many steps ahead need no test.
-                if (dist >= 2) safe_until = max(safe_until, idx + (int) fminf(((float) (8 * (dist - 1)) - 1.25f) * inv_texels_per_step, 1.0e6f));
-            }
-        }
-        const bool any_live = !wave_skip || __builtin_amdgcn_ballot_w64(live) != 0;
+#include "tbrm_ray_locate.inc"
 #ifdef TBRM_RAY_STATS
         {
             const unsigned long long nd = __builtin_popcountll(__builtin_amdgcn_ballot_w64(!done)), nl = __builtin_popcountll(__builtin_amdgcn_ballot_w64(live));
@@ -518,34 +453,7 @@ __global__ __launch_bounds__(256, 6) void k_raymarch_lit(const RayParams p) // 6
 #include "tbrm_ray_replay.inc"
         }
         if (base + kRayLanes >= n_samples) done = true;
-        // ---- 5. leap. Empty space, wave-wide: when no lane of the wave had anything to sample in this trip, the trips that EVERY marching
-        // lane would spend the same way — its sample still within its proven-empty range (safe_until), the ray still in its
-        // full steps — are taken in one go: their only effect is the positions' additions, performed one by one as before
-        // (a position is reached by performing every addition of the ray). 70 % of the benchmark's trips are of this kind.
-        const bool renewed = eager;
-        eager = false;
-        if (!any_live) {
-            int k_lane = INT32_MAX; // whole trips this lane can take blind after this one
-            if (!done) {
-                const int ahead = safe_until - base - b; // its sample of trip t from now is base + kRayLanes t + b
-                const int by_safe = ahead >= kRayLanes ? ahead / kRayLanes : 0;
-                const int left = max_steps - 1 - (base + kRayLanes); // full steps behind the end of this trip, but for the last
-                const int by_length = left >= kRayLanes ? left / kRayLanes : 0;
-                k_lane = min(by_safe, by_length);
-            }
-            int k = 0; // the wave's minimum (small: counted up with ballots)
-            while (k < 64 && __builtin_amdgcn_ballot_w64(k_lane <= k) == 0) ++k;
-            if (k > 0) {
-                for (int t = 0; t < k * kRayLanes; ++t) { pos0 = pos0 + sv0; pos1 = pos1 + sv1; pos2 = pos2 + sv2; }
-                adds += k * kRayLanes;
-                base += k * kRayLanes;
-            }
-            // (next to the volume's content the ranges are a trip or two long: renewing them every empty trip would cost more
-            // than the look-ups it aligns — small volumes lost 10 - 20 % of their frame that way)
-            if (renewed && k == 0) renew_wait = 4;
-            else if (renew_wait > 0) --renew_wait;
-            eager = renew_wait == 0;
-        }
+#include "tbrm_ray_leap.inc"
     }
     if ((SLAB ? mine : valid) && b == 0) reinterpret_cast<float4*>(p.out)[(size_t) j * p.tile_w + i] = make_float4(le[0], le[1], le[2], le[3]);
     if constexpr (REC == REC_COUNT) {
@@ -636,6 +544,192 @@ static hipError_t launch_ray0(const RayParams& p, hipStream_t s)
 }
 #if defined(TBRM_RAY_RGB_UNIT)
 hipError_t launch_raymarch_rgb(const RayParams& p, hipStream_t s) { return launch_ray0<true>(p, s); }
+#elif defined(TBRM_RAY_HIT_UNIT)
+// ---- k_raymarch_hit: where each ray of a tile first gets opaque (include/tbrm_hit.h) ---------------------------------
+// The accumulated opacity of a ray never sees the light volume, so this is k_raymarch_lit without its light taps, light filter and
+// colour channels: the same prologue (ray_of_wave, cube_setup, march_setup), the same trip — stages 1, 2 and 5 are the lit march's
+// own text — and the same replay of accumulate() over the ray's samples in ray order, with one float (the corrected opacity) per
+// lane through LDS instead of a float4. The hit test `LightEnergy.a > threshold` stands where exit_reached() stands in the lit
+// march, on the fractional step as well; a threshold of at most 0.95 is passed no later than 0.95 is, so the march needs no second
+// exit. The lane that evaluated the hit sample still holds its position, filtered value and label and writes the record; lane 0 of
+// a ray that ends without a hit writes the no-hit record. Records go out as two 16-byte words.
+//
+// Waves per SIMD (TBRM_HIT_WAVES, a build-time switch for tools/hit_map_time.py): 6, the lit march's bound, under which the allocator
+// is left alone — the instantiations take 58 - 74 registers, none spills, all reach 6 - 8 waves. Builds with 4, 5 and 7 are this code;
+// 8 caps the registers at 64 (six instantiations then spill two to scratch, ten keep scalars in vector lanes) and measured the same
+// frame time (profiles/r09_hit_map.txt).
+#ifndef TBRM_HIT_WAVES
+#define TBRM_HIT_WAVES 6
+#endif
+template <int DFMT, int DMODE, int kRayLanes, bool TAB, bool LABELS>
+__global__ __launch_bounds__(256, TBRM_HIT_WAVES) void k_raymarch_hit(const RayParams p, const HitParams h)
+{
+    static_assert(kRayLanes == 4 || kRayLanes == 8, "instantiated for 4 and 8 lanes per ray");
+    constexpr bool SLAB = false; // (what the shared stages name for the slab stage, which a hit map never is)
+    extern __shared__ __attribute__((aligned(16))) uint2 s_tab[]; // TAB: [x | y | z] (ray_tab_*); LABELS: then s_lab, s_lb
+    const uint2* const tab_x = s_tab;
+    const uint2* const tab_y = tab_x + (TAB ? ray_tab_axis_entries(p.data.nx) : 0);
+    const uint2* const tab_z = tab_y + (TAB ? ray_tab_axis_entries(p.data.ny) : 0);
+    constexpr int LSH = kRayLanes == 4 ? 2 : 3;
+    __shared__ float s_tfa[256]; // the transfer function's alpha channel
+    __shared__ float s_a[256];   // per lane: the corrected opacity of its sample; < 0: nothing to accumulate
+    s_tfa[threadIdx.x] = p.tf[threadIdx.x].w;
+    // LABELS: per colour-table entry its full-step a'; per lane the label of its sample (-1: no label step)
+    float* const s_lab = reinterpret_cast<float*>(s_tab + (TAB ? ray_tab_entries(p.data.nx, p.data.ny, p.data.nz) : 0));
+    short* const s_lb = reinterpret_cast<short*>(s_lab + 256);
+    if constexpr (LABELS) {
+        const float cw = p.lab_colors[threadIdx.x].w;
+        s_lab[threadIdx.x] = cw != 0.0f ? one_minus_pow01_(1.0f - cw, 100.0f * (1 / p.steps)) : 0.0f; // (the data path's step_world)
+    }
+    if constexpr (!TAB) __syncthreads();
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = lane & (kRayLanes - 1), r = lane >> LSH; // sample slot, ray within the wave
+    int i, j, px, py;
+    ray_of_wave<kRayLanes>(p, wave, r, i, j);
+    const bool valid = tile_pixel_at(p, i, j, px, py);
+
+    Ray ray;
+    cube_setup(p, valid ? px : p.tile_x0, valid ? py : p.tile_y0, ray);
+    const March m = march_setup(p, ray, px, py, valid);
+    const int max_steps = m.max_steps, n_samples = m.n_samples;
+    const float final_step = m.final_step, step_world = m.step_world, sv0 = m.sv[0], sv1 = m.sv[1], sv2 = m.sv[2];
+    float pos0 = m.pos[0], pos1 = m.pos[1], pos2 = m.pos[2];
+    if constexpr (TAB) { // the tables, unless no ray of the workgroup meets the volume
+        if (__syncthreads_or(n_samples > 0)) {
+            const int n16 = ray_tab_entries(p.data.nx, p.data.ny, p.data.nz) >> 1;
+            for (int k = threadIdx.x; k < n16; k += 256) reinterpret_cast<uint4*>(s_tab)[k] = reinterpret_cast<const uint4*>(p.tab)[k];
+            __syncthreads();
+        }
+    }
+
+    const float nx = (float) p.data.nx, ny = (float) p.data.ny, nz = (float) p.data.nz;
+    [[maybe_unused]] const float lnz = 0.0f; // (named by the slab stage's test in the shared text)
+    const float inv_texels_per_step = 1.0f / fmaxf(fmaxf(fabsf(sv0) * nx, fabsf(sv1) * ny), fabsf(sv2) * nz);
+    int safe_until = -1;
+    const bool wave_skip = p.wave_skip != 0 && p.skip_dist != nullptr;
+    bool eager = false;
+    int renew_wait = 0;
+
+    float le[4] = {0.0f, 0.0f, 0.0f, 0.0f}; // LightEnergy: only .a is ever read, so only .a is computed
+    bool done = n_samples == 0;
+    bool found = false; // the ray's hit record has been written
+    int adds = 0;
+    float* const xs = s_a + (threadIdx.x & ~(kRayLanes - 1)); // the ray's kRayLanes exchange slots
+    const size_t out_at = (size_t) j * p.tile_w + i;
+
+    for (int base = 0; __builtin_amdgcn_ballot_w64(!done) != 0; base += kRayLanes) {
+#include "tbrm_ray_locate.inc"
+        // ---- 3. shade: the reference's loop body up to AccumulateLightEnergy, alpha alone -> xa
+        float xa = -1.0f, v = 0.0f;
+        [[maybe_unused]] int lab_at = -1; // LABELS: the label byte of the sample's nearest voxel, whether or not it has a step to take
+        if (live) {
+            RawTaps<DFMT> dtaps;
+            TapOffsets dt;
+            if constexpr (TAB) dt = tab_dt;
+            else dt = tap_offsets<DMODE, false>(p.data, ix, iy, iz);
+            dtaps.issue(p.data.data, dt);
+            if constexpr (LABELS) { // the nearest label voxel (SampleLabelVolume): rint((N - 1) * saturate(pos)) per axis, in [0, N - 1]
+                const int lx = (int) __builtin_rintf((float) (p.data.nx - 1) * saturate_(q0));
+                const int ly = (int) __builtin_rintf((float) (p.data.ny - 1) * saturate_(q1));
+                const int lz = (int) __builtin_rintf((float) (p.data.nz - 1) * saturate_(q2));
+                lab = p.labels[brick_off(lx, ly, lz, p.data.bnx, p.data.bnxy)];
+                lab_at = lab;
+            }
+            v = dtaps.filter(fx, fy, fz);
+            // SampleWindowedTransferFunction (WindowedSampling.usf:20-37), its alpha
+            const float tpos = window_position<DFMT != FMT_F32>(v, p.win);
+            if (!((tpos < 0.0f && p.win.low_cutoff > 0.0f) || (tpos > 1.0f && p.win.high_cutoff > 0.0f))) {
+                const float a_sat = saturate_(sample_tf_alpha(s_tfa, tpos));
+                if (a_sat != 0.0f) xa = one_minus_pow01_(1.0f - a_sat, step); // (the lit march's domain: a_sat in (0, 1], step >= 0)
+            }
+            if constexpr (LABELS) {
+                if (is_full && s_lab[lab] == 0.0f) lab = -1; // adds exactly nothing
+            }
+        }
+
+        // ---- 4. exchange and replay, as the lit march's stage 4 (tbrm_ray_replay.inc) with the hit test for its exit test
+        bool to_accumulate = xa >= 0.0f || xa != xa;
+        if constexpr (LABELS) to_accumulate = to_accumulate || lab >= 0;
+        int hit_slot = -1; // the slot of the trip whose sample is the ray's hit (the same in every lane of the ray)
+        if (__builtin_amdgcn_ballot_w64(to_accumulate) != 0) {
+            s_a[threadIdx.x] = xa;
+            if constexpr (LABELS) s_lb[threadIdx.x] = (short) lab;
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int t = 0; t < kRayLanes; ++t) {
+                const float cw = xs[t];
+                const bool data_step = !(cw < 0.0f);
+                if (done || (!LABELS && !data_step)) continue;
+                if (data_step) accumulate(le, make_float4(0.0f, 0.0f, 0.0f, cw));
+                if constexpr (LABELS) { // then the label step (AccumulateOneRaymarchLabelStep: unlit)
+                    const int lb = s_lb[(threadIdx.x & ~(kRayLanes - 1)) + t];
+                    if (lb >= 0) {
+                        float a;
+                        if (base + t < max_steps) a = s_lab[lb];
+                        else { // the fractional step (once per ray): its own a' with the step 100 * FinalStep
+                            const float raw = p.lab_colors[lb].w;
+                            a = raw != 0.0f ? one_minus_pow01_(1.0f - raw, 100.0f * final_step) : 0.0f;
+                        }
+                        accumulate(le, make_float4(0.0f, 0.0f, 0.0f, a));
+                    }
+                }
+                if (le[3] > h.threshold) { hit_slot = t; done = true; }
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+        if (hit_slot >= 0) { // (a slot with a step to take: its lane evaluated the sample)
+            found = true;
+            if (b == hit_slot) {
+                h.hits[2 * out_at] = make_uint4(__float_as_uint(q0), __float_as_uint(q1), __float_as_uint(q2), (uint32_t) idx);
+                h.hits[2 * out_at + 1] = make_uint4(__float_as_uint(le[3]), __float_as_uint(v), (uint32_t) (LABELS ? lab_at : -1), (uint32_t) max_steps);
+                if (h.depth) h.depth[out_at] = (((q0 - 0.5f) * h.dg[0] + (q1 - 0.5f) * h.dg[1]) + (q2 - 0.5f) * h.dg[2]) + h.d0;
+            }
+        }
+        if (base + kRayLanes >= n_samples) done = true;
+#include "tbrm_ray_leap.inc"
+    }
+    if (valid && b == 0 && !found) {
+        h.hits[2 * out_at] = make_uint4(0u, 0u, 0u, (uint32_t) -1);
+        h.hits[2 * out_at + 1] = make_uint4(__float_as_uint(le[3]), 0u, (uint32_t) -1, (uint32_t) max_steps);
+        if (h.depth) h.depth[out_at] = __builtin_inff();
+    }
+}
+
+template <int DFMT, int RL, bool TAB, bool LABELS>
+static hipError_t launch_hit3(const RayParams& p, const HitParams& h, size_t lds_bytes, hipStream_t s)
+{
+    const dim3 grid = ray_grid<RL>(p), block(256);
+    if (p.data_addr_mode == ADDR_CLAMP) hipLaunchKernelGGL((k_raymarch_hit<DFMT, ADDR_CLAMP, RL, TAB, LABELS>), grid, block, lds_bytes, s, p, h);
+    else hipLaunchKernelGGL((k_raymarch_hit<DFMT, ADDR_WRAP, RL, TAB, LABELS>), grid, block, lds_bytes, s, p, h);
+    return hipGetLastError();
+}
+template <int DFMT, int RL, bool LABELS>
+static hipError_t launch_hit2(const RayParams& p, const HitParams& h, hipStream_t s)
+{
+    // LABELS: the colour table's full-step a' and the exchanged label bytes, behind the tables (1.5 KiB)
+    constexpr size_t lab_bytes = LABELS ? 256 * sizeof(float) + 256 * sizeof(short) : 0;
+    const size_t tab_bytes = (size_t) ray_tab_entries(p.data.nx, p.data.ny, p.data.nz) * sizeof(uint2);
+    if (ray_tables_for(p)) return launch_hit3<DFMT, RL, true, LABELS>(p, h, tab_bytes + lab_bytes, s); // (the lit march's rule)
+    return launch_hit3<DFMT, RL, false, LABELS>(p, h, lab_bytes, s);
+}
+template <int DFMT>
+static hipError_t launch_hit1(const RayParams& p, const HitParams& h, hipStream_t s)
+{
+    const bool eight = ray_lanes_for(p) == 8; // (the lit march's rule)
+    if (p.labels) return eight ? launch_hit2<DFMT, 8, true>(p, h, s) : launch_hit2<DFMT, 4, true>(p, h, s);
+    return eight ? launch_hit2<DFMT, 8, false>(p, h, s) : launch_hit2<DFMT, 4, false>(p, h, s);
+}
+hipError_t launch_raymarch_hit(const RayParams& p, const HitParams& h, hipStream_t s)
+{
+    if (p.tile_w <= 0 || p.tile_h <= 0) return hipSuccess;
+    if (p.slab_on) return hipErrorInvalidValue; // (the host refuses slab-resident handles)
+    switch (p.data.fmt) {
+        case FMT_U8: return launch_hit1<FMT_U8>(p, h, s);
+        case FMT_U16: return launch_hit1<FMT_U16>(p, h, s);
+        default: return launch_hit1<FMT_F32>(p, h, s);
+    }
+}
 #elif defined(TBRM_RAY_REC_UNIT)
 hipError_t launch_raymarch_recording(const RayParams& p, bool fill, hipStream_t s)
 {

@@ -408,6 +408,11 @@ struct tbrm_resources {
     uint32_t* d_stats = nullptr;       // the scratch: histogram bins and tallies, then the 256 label records (ensure_stats_scratch)
     std::vector<uint32_t> stats_host;  // ... and where the host forms read it back to
     uint64_t stats_counters[4]{};      // tbrm_volume_stats_counters
+
+    // hit maps and picking (tbrm_api_hit.cpp; include/tbrm_hit.h)
+    char* d_hit = nullptr;             // staging of the host forms: the tile's records, then its depths; grown to the largest tile seen
+    size_t hit_bytes = 0;
+    uint64_t hit_counters[3]{};        // tbrm_hit_counters
 };
 
 
@@ -439,6 +444,11 @@ int ensure_skipping(tbrm_resources* r);
 // boxes, or as many bricks as the volume has — minmax_valid dropped so that ensure_skipping rebuilds all of it
 int refresh_dirty_minmax(tbrm_resources* r, const BrickParams& whole);
 int raymarch_clip_mode(const float cc[3], const float cd[3]);
+// the frame calls' view of a handle (tbrm_api_render.cpp; tbrm_api_hit.cpp marches the same rays): every RayParams field that does not
+// depend on the call's buffers, and — for a call that asks for it — the skipping metadata, brought up to date
+int build_ray_params(tbrm_resources* r, const tbrm_camera* cam, const tbrm_tile* tile, const tbrm_raymarch_params* rp,
+                     const tbrm_world_params* world, RayParams& p);
+int attach_skipping(tbrm_resources* r, const tbrm_raymarch_params* rp, RayParams& p);
 // the view cache (tbrm_api_render.cpp): its arena, pinned word and event, once per handle, under the factor-cache arena's free-memory
 // rule (eager: asked for by tbrm_resources_reserve); and their release (the stream must be idle)
 void ensure_view_arena(tbrm_resources* r, bool eager);
