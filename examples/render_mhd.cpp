@@ -5,12 +5,15 @@
 //
 //   g++ -std=c++17 -O2 -I include examples/render_mhd.cpp -o render_mhd -L tbraymarcherplugin_amd/lib -ltbrm -lz
 //       (plus -Wl,-rpath,$PWD/tbraymarcherplugin_amd/lib -Wl,-rpath,/opt/rocm/lib to run it in place)
-//   ./render_mhd volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y]
+//   ./render_mhd volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]]
 //       --light-color: the key light's colour (components in [0, 1]) on an RGB light volume (include/tbrm_color_lights.h); the fill stays white
 //       --auto-window: the window comes from the data (ARaymarchVolume::AutoWindow, include/tbrm_volume_stats.h): the span between
 //                      the LOW and HIGH percentiles of the value histogram, 0.01,0.99 when not given
 //       --pick: what the frame's pixel (X, Y) shows first (ARaymarchVolume::PickVolume, include/tbrm_hit.h): the spot where the ray's
 //                      accumulated opacity passes 0.5, printed as one "pick" line
+//       --grow: a click on the frame's pixel (X, Y) (ARaymarchVolume::GrowRegionAt, include/tbrm_segment.h): the voxels connected to the
+//                      one under it whose stored value (the 16-bit code) is within TOL of its own get label LABEL (1 when not given)
+//                      and the frame shows them in the label's colour; printed as one "grow" line with the label's mean value
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -45,6 +48,17 @@ int main(int argc, char** argv)
             argc -= 2;
             break;
         }
+    int grow_x = -1, grow_y = -1, grow_label = 1;
+    double grow_tol = 0.0;
+    bool grow = false;
+    for (int i = 1; i + 1 < argc; ++i)
+        if (!std::strcmp(argv[i], "--grow")) {
+            if (std::sscanf(argv[i + 1], "%d,%d,%lf,%d", &grow_x, &grow_y, &grow_tol, &grow_label) < 3) { argc = 0; break; }
+            grow = true;
+            for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
+            argc -= 2;
+            break;
+        }
     for (int i = 1; i + 1 < argc; ++i) // the option and its value leave the positional arguments
         if (!std::strcmp(argv[i], "--light-color")) {
             if (std::sscanf(argv[i + 1], "%f,%f,%f", &key_color[0], &key_color[1], &key_color[2]) != 3) { argc = 0; break; }
@@ -54,7 +68,7 @@ int main(int argc, char** argv)
             break;
         }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]]\n", argv[0]);
         return 2;
     }
     const int width = argc > 3 ? std::atoi(argv[3]) : 512, height = argc > 4 ? std::atoi(argv[4]) : 512;
@@ -104,6 +118,24 @@ int main(int argc, char** argv)
     cam.width = width;
     cam.height = height;
 
+    if (grow) { // before the frame, so that the frame shows the grown label
+        FGrowResult g;
+        if (!volume.GrowRegionAt(cam, grow_x, grow_y, 0.5f, grow_tol, grow_label, 6, g)) {
+            std::fprintf(stderr, "grow failed: %s\n", tbrm_last_error());
+            return 1;
+        }
+        std::vector<tbrm_label_stat> stats;
+        if (!g.bSeeded) std::printf("grow %d,%d miss\n", grow_x, grow_y);
+        else if (!volume.GetLabelStatistics(stats)) {
+            std::fprintf(stderr, "label statistics failed: %s\n", tbrm_last_error());
+            return 1;
+        } else {
+            const tbrm_label_stat& s = stats[(size_t) (grow_label & 255)];
+            std::printf("grow %d,%d seed %d %d %d range %.9g .. %.9g voxels %llu box %d %d %d .. %d %d %d label %d mean %.9g\n", grow_x, grow_y, g.Seed[0], g.Seed[1],
+                        g.Seed[2], g.LoUsed, g.HiUsed, (unsigned long long) g.Voxels, g.BoxMin[0], g.BoxMin[1], g.BoxMin[2], g.BoxMax[0], g.BoxMax[1], g.BoxMax[2],
+                        grow_label, s.count > s.nan_count ? s.sum / (double) (s.count - s.nan_count) : 0.0);
+        }
+    }
     std::vector<float> rgba((size_t) width * height * 4);
     if (!volume.RenderLit(cam, rgba.data())) {
         std::fprintf(stderr, "render failed: %s\n", tbrm_last_error());

@@ -204,7 +204,9 @@ TBRM_API int tbrm_device_count(int* out_count);   /* TBRM_ERR_NO_DEVICE when the
  * bands of n rows; 0 = in launch order, i.e. round-robin block by block: 10 % slower at 512^3),
  * stats_groups (0 = the statistics kernels of tbrm_volume_stats.h size their grid to the device; n > 0 = at most n workgroups: a test
  * hook and an A/B switch), view_cache_mb (1536 = MiB of records per handle from which a lit frame of an unchanged view is relit
- * instead of marched again, bit-identically: tbrm_view_cache.h; 0 = every frame marches). Unknown name: TBRM_ERR_INVALID_ARG. */
+ * instead of marched again, bit-identically: tbrm_view_cache.h; 0 = every frame marches), grow_batch (16 = propagation passes of
+ * tbrm_grow_region, tbrm_segment.h, enqueued between two read-backs of their changed-bricks words, 1 .. 64; 1 = a read-back per pass:
+ * a test hook; the result is the same for every value). Unknown name: TBRM_ERR_INVALID_ARG. */
 TBRM_API int tbrm_set_tunable(const char* name, int32_t value);
 TBRM_API int tbrm_get_tunable(const char* name, int32_t* value);
 

@@ -20,6 +20,7 @@
 #include "tbrm_volume_region.h"
 #include "tbrm_volume_stats.h"
 #include "tbrm_hit.h"
+#include "tbrm_segment.h"
 
 #include <algorithm>
 #include <cmath>
@@ -266,6 +267,17 @@ struct FVolumeHit {
     int Sample = -1;     // the sample's index along the ray
 };
 
+// What a region growing call found (include/tbrm_segment.h): ARaymarchVolume::GrowRegion / GrowRegionAt
+struct FGrowResult {
+    bool bSeeded = false;          // GrowRegionAt: the ray met the volume (else nothing was grown)
+    int Seed[3] = {-1, -1, -1};    // GrowRegionAt: the voxel under the pixel
+    uint64_t Voxels = 0;           // the region's size
+    uint64_t Relabelled = 0;       // label bytes that changed
+    int BoxMin[3] = {0, 0, 0}, BoxMax[3] = {-1, -1, -1}; // inclusive; an empty region: the volume's size and -1
+    int Passes = 0;
+    double LoUsed = 0.0, HiUsed = 0.0; // the value range applied, in stored units
+};
+
 class ARaymarchVolume {
 public:
     // ---- the reflected properties the hot path consumes (RaymarchVolume.h:60-266) ----
@@ -388,6 +400,53 @@ public:
         return RaymarchResources.Handle && tbrm_set_label_colors(RaymarchResources.Handle, Rgba256x4) == TBRM_OK;
     }
     bool ClearLabelVolume() { return RaymarchResources.Handle && tbrm_release_label_volume(RaymarchResources.Handle) == TBRM_OK; }
+
+    // Seeded region growing (include/tbrm_segment.h; no counterpart in the reference): the voxels with a stored value in [Lo, Hi]
+    // connected to a seed (NumSeeds voxels x, y, z; none: every such voxel) get NewLabel (-1: measured only), on the device. Like
+    // the other label edits it requests no recompute. A writing call attaches an empty label volume when none is attached.
+    bool GrowRegion(const int32_t* SeedsXYZ, int NumSeeds, double Lo, double Hi, int NewLabel, int Connectivity, FGrowResult& Out,
+                    bool bRelativeToSeed = false)
+    {
+        Out = FGrowResult{};
+        if (!RaymarchResources.Handle) return false;
+        if (NewLabel >= 0 && !tbrm_has_label_volume(RaymarchResources.Handle) && tbrm_attach_empty_label_volume(RaymarchResources.Handle) != TBRM_OK) return false;
+        tbrm_grow_desc d{};
+        d.connectivity = Connectivity;
+        d.new_label = NewLabel;
+        d.relative_to_seed = bRelativeToSeed ? 1 : 0;
+        d.lo = Lo;
+        d.hi = Hi;
+        for (uint32_t& w : d.writable) w = 0xffffffffu;
+        tbrm_grow_result r{};
+        if (tbrm_grow_region(RaymarchResources.Handle, &d, SeedsXYZ, NumSeeds, &r) != TBRM_OK) return false;
+        Out.Voxels = r.voxels;
+        Out.Relabelled = r.relabelled;
+        for (int c = 0; c < 3; ++c) { Out.BoxMin[c] = r.bbox_min[c]; Out.BoxMax[c] = r.bbox_max[c]; }
+        Out.Passes = r.passes;
+        Out.LoUsed = r.lo_used;
+        Out.HiUsed = r.hi_used;
+        return true;
+    }
+    // The click: the voxel the lit march first gets opaque at under pixel (Px, Py) (PickVolume's call, then tbrm_host_hit_voxel) and
+    // from it every connected voxel whose stored value is within Tolerance of that voxel's. A ray that meets nothing grows nothing
+    // (true, Out.bSeeded false).
+    bool GrowRegionAt(const tbrm_camera& Camera, int Px, int Py, float Threshold, double Tolerance, int NewLabel, int Connectivity, FGrowResult& Out)
+    {
+        Out = FGrowResult{};
+        if (!RaymarchResources.bIsInitialized) return false;
+        const tbrm_raymarch_params rp{RaymarchingSteps, -1, 1, 0};
+        const tbrm_world_params w = WorldParameters.abi();
+        tbrm_hit h{};
+        if (tbrm_pick(RaymarchResources.Handle, &Camera, Px, Py, &rp, &w, Threshold, &h, nullptr, nullptr) != TBRM_OK) return false;
+        if (h.sample < 0) return true;
+        const int32_t dims[3] = {RaymarchResources.SizeX, RaymarchResources.SizeY, RaymarchResources.SizeZ};
+        int32_t seed[3] = {0, 0, 0};
+        if (tbrm_host_hit_voxel(dims, &h, seed) != TBRM_OK) return false;
+        const bool ok = GrowRegion(seed, 1, -Tolerance, Tolerance, NewLabel, Connectivity, Out, true);
+        Out.bSeeded = true;
+        for (int c = 0; c < 3; ++c) Out.Seed[c] = seed[c];
+        return ok;
+    }
 
     // :746-784 — every windowing change requests a full recompute
     void SetWindowCenter(float Center) { if (Center != RaymarchResources.WindowingParameters.Center) { RaymarchResources.WindowingParameters.Center = Center; WindowingChanged(); } }

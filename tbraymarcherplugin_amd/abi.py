@@ -196,6 +196,25 @@ HIT_ABI_VERSION = 1  # TBRM_HIT_ABI_VERSION of include/tbrm_hit.h
 HIT_DTYPE = np.dtype([("uvw", np.float32, (3,)), ("sample", np.int32), ("alpha", np.float32), ("value", np.float32), ("label", np.int32),
                       ("full_steps", np.int32)])
 
+# every symbol include/tbrm_segment.h declares (seeded region growing; tests/test_segment_abi.py checks the header against this list)
+SEGMENT_SYMBOLS = [
+    "tbrm_segment_abi_version", "tbrm_grow_region", "tbrm_attach_empty_label_volume", "tbrm_host_hit_voxel", "tbrm_segment_counters",
+]
+
+SEGMENT_ABI_VERSION = 1  # TBRM_SEGMENT_ABI_VERSION of include/tbrm_segment.h
+GROW_MAX_SEEDS = 4096
+
+
+class GROW_DESC(C.Structure):  # tbrm_grow_desc
+    _fields_ = [("origin", C.c_int32 * 3), ("extent", C.c_int32 * 3), ("connectivity", C.c_int32), ("new_label", C.c_int32),
+                ("relative_to_seed", C.c_int32), ("reserved", C.c_int32), ("lo", C.c_double), ("hi", C.c_double), ("writable", C.c_uint32 * 8)]
+
+
+class GROW_RESULT(C.Structure):  # tbrm_grow_result
+    _fields_ = [("voxels", C.c_uint64), ("relabelled", C.c_uint64), ("bbox_min", C.c_int32 * 3), ("bbox_max", C.c_int32 * 3),
+                ("passes", C.c_int32), ("seeds_taken", C.c_int32), ("lo_used", C.c_double), ("hi_used", C.c_double)]
+
+
 _lib = None
 
 
@@ -336,6 +355,14 @@ def load():
     lib.tbrm_pick.argtypes = [vp, P(Camera), C.c_int32, C.c_int32, P(RaymarchParams), P(WorldParams), C.c_float, vp, P(C.c_double * 3), P(C.c_double)]
     lib.tbrm_host_hits_to_world.argtypes = [P(WorldParams), P(Camera), vp, C.c_size_t, vp, vp]
     lib.tbrm_hit_counters.argtypes = [vp, P(C.c_uint64 * 3)]
+    have = lib.tbrm_segment_abi_version() if hasattr(lib, "tbrm_segment_abi_version") else -1
+    if have != SEGMENT_ABI_VERSION:
+        raise ImportError(f"{LIB_PATH} has segment ABI version {have}, this binding is written against {SEGMENT_ABI_VERSION}: rebuild it "
+                          "(`python tbraymarcherplugin_amd/build.py --force`)")
+    lib.tbrm_grow_region.argtypes = [vp, P(GROW_DESC), vp, C.c_int32, P(GROW_RESULT)]
+    lib.tbrm_attach_empty_label_volume.argtypes = [vp]
+    lib.tbrm_host_hit_voxel.argtypes = [P(C.c_int32 * 3), vp, P(C.c_int32 * 3)]
+    lib.tbrm_segment_counters.argtypes = [vp, P(C.c_uint64 * 4)]
     _lib = lib
     return lib
 
@@ -438,6 +465,15 @@ def hits_to_world(world, camera, hits):
     depth = np.empty(hits.size, dtype=np.float64)
     check(load().tbrm_host_hits_to_world(C.byref(world), C.byref(camera), hits.ctypes.data, hits.size, xyz.ctypes.data, depth.ctypes.data))
     return xyz.reshape(shape + (3,)), depth.reshape(shape)
+
+
+def hit_voxel(dims, hit):
+    """tbrm_host_hit_voxel: the voxel (x, y, z) the label step reads at a hit record (a HIT_DTYPE scalar) of a volume `dims` (x, y, z)"""
+    rec = np.array([hit], dtype=HIT_DTYPE)
+    d = (C.c_int32 * 3)(*[int(v) for v in dims])
+    out = (C.c_int32 * 3)()
+    check(load().tbrm_host_hit_voxel(C.byref(d), rec.ctypes.data, C.byref(out)))
+    return tuple(out[:])
 
 
 def make_default_label_colors():
@@ -695,6 +731,42 @@ class Resources:
         out = (C.c_uint64 * 3)()
         check(self.lib.tbrm_hit_counters(self.handle, C.byref(out)))
         return {k: int(out[i]) for i, k in enumerate(self.HIT_COUNTERS)}
+
+    # seeded region growing (include/tbrm_segment.h): lo / hi in stored units, seeds and boxes as (x, y, z)
+    def grow_desc(self, lo, hi, label, connectivity=6, origin=None, extent=None, writable=None, relative=False):
+        """writable: the label values that may be grown over (None: every label); label -1: measure only"""
+        d = GROW_DESC()
+        if extent is not None:
+            d.origin[:] = [int(v) for v in (origin if origin is not None else (0, 0, 0))]
+            d.extent[:] = [int(v) for v in extent]
+        d.connectivity, d.new_label, d.relative_to_seed = int(connectivity), int(label), int(bool(relative))
+        d.lo, d.hi = float(lo), float(hi)
+        if writable is None:
+            d.writable[:] = [0xFFFFFFFF] * 8
+        else:
+            for l in writable:
+                d.writable[int(l) >> 5] |= 1 << (int(l) & 31)
+        return d
+
+    def grow_region(self, seeds, lo, hi, label, connectivity=6, origin=None, extent=None, writable=None, relative=False):
+        """tbrm_grow_region from `seeds` ([n, 3] voxels, or empty / None: plain thresholding): {"voxels", "relabelled", "bbox_min",
+        "bbox_max", "passes", "seeds_taken", "lo_used", "hi_used"}"""
+        d = self.grow_desc(lo, hi, label, connectivity, origin, extent, writable, relative)
+        s = np.ascontiguousarray(np.asarray(seeds if seeds is not None else [], dtype=np.int32).reshape(-1, 3))
+        out = GROW_RESULT()
+        check(self.lib.tbrm_grow_region(self.handle, C.byref(d), s.ctypes.data if len(s) else None, len(s), C.byref(out)))
+        return {"voxels": int(out.voxels), "relabelled": int(out.relabelled), "bbox_min": tuple(out.bbox_min[:]), "bbox_max": tuple(out.bbox_max[:]),
+                "passes": int(out.passes), "seeds_taken": int(out.seeds_taken), "lo_used": float(out.lo_used), "hi_used": float(out.hi_used)}
+
+    def attach_empty_labels(self):
+        check(self.lib.tbrm_attach_empty_label_volume(self.handle))
+
+    SEGMENT_COUNTERS = ("grow_calls", "passes", "brick_visits", "bricks_written")
+
+    def segment_counters(self):
+        out = (C.c_uint64 * 4)()
+        check(self.lib.tbrm_segment_counters(self.handle, C.byref(out)))
+        return {k: int(out[i]) for i, k in enumerate(self.SEGMENT_COUNTERS)}
 
     def is_initialized(self):
         return bool(self.lib.tbrm_resources_is_initialized(self.handle))

@@ -47,6 +47,10 @@ int put_colors(tbrm_resources* r, const float* rgba)
     return TBRM_OK;
 }
 
+} // namespace
+
+namespace tbrm_host {
+
 // the per-brick live bits and the volume's label set (from the per-brick sets); the merged metadata is stale after it
 int refresh_live(tbrm_resources* r)
 {
@@ -75,6 +79,10 @@ int brick_masks(tbrm_resources* r, const int b0[3], const int b1[3])
     HIP_TRY(launch_label_brick_masks(bp, r->stream));
     return TBRM_OK;
 }
+
+} // namespace tbrm_host
+
+namespace {
 
 // does some label present in the volume show (colour alpha > 0)?
 bool labels_visible(const tbrm_resources* r)
@@ -134,6 +142,27 @@ void release_labels(tbrm_resources* r)
     r->lab_skip_valid = false;
 }
 
+int allocate_labels(tbrm_resources* r)
+{
+    if (r->d_labels) return TBRM_OK;
+    // everything the label step and its skipping metadata use: rendering allocates nothing
+    const size_t nb = label_bricks(r), nb_pad = (nb + 255) / 256 * 256;
+    hipError_t e = hipMalloc((void**) &r->d_labels, nb * 512);
+    if (e == hipSuccess) e = hipMalloc((void**) &r->d_lab_mask, nb * 8 * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void**) &r->d_lab_present, 8 * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void**) &r->d_lab_live, nb_pad / 8);
+    if (e == hipSuccess) e = hipMalloc((void**) &r->d_empty_lab, nb_pad / 8);
+    for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipMalloc((void**) &r->d_dist_lab[k], nb_pad);
+    if (e == hipSuccess) e = hipMalloc((void**) &r->d_lab_colors, 256 * sizeof(float4));
+    if (e != hipSuccess) {
+        release_labels(r);
+        return fail(e == hipErrorOutOfMemory ? TBRM_ERR_OUT_OF_MEMORY : TBRM_ERR_NO_DEVICE, "label volume allocation failed: %s", hipGetErrorString(e));
+    }
+    default_label_colors(r->lab_colors);
+    if (int e2 = put_colors(r, r->lab_colors)) { release_labels(r); return e2; }
+    return TBRM_OK;
+}
+
 } // namespace tbrm_host
 
 extern "C" {
@@ -154,22 +183,7 @@ int tbrm_upload_label_volume(tbrm_resources* r, const uint8_t* host_labels, size
     if (!r || !host_labels) return fail(TBRM_ERR_INVALID_ARG, "null argument");
     if (n_bytes != label_voxels(r)) return fail(TBRM_ERR_INVALID_ARG, "label volume is %zu bytes, expected %zu", n_bytes, label_voxels(r));
     if (int e = bind(r)) return e;
-    if (!r->d_labels) { // everything the label step and its skipping metadata use: rendering allocates nothing
-        const size_t nb = label_bricks(r), nb_pad = (nb + 255) / 256 * 256;
-        hipError_t e = hipMalloc((void**) &r->d_labels, nb * 512);
-        if (e == hipSuccess) e = hipMalloc((void**) &r->d_lab_mask, nb * 8 * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void**) &r->d_lab_present, 8 * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void**) &r->d_lab_live, nb_pad / 8);
-        if (e == hipSuccess) e = hipMalloc((void**) &r->d_empty_lab, nb_pad / 8);
-        for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipMalloc((void**) &r->d_dist_lab[k], nb_pad);
-        if (e == hipSuccess) e = hipMalloc((void**) &r->d_lab_colors, 256 * sizeof(float4));
-        if (e != hipSuccess) {
-            release_labels(r);
-            return fail(e == hipErrorOutOfMemory ? TBRM_ERR_OUT_OF_MEMORY : TBRM_ERR_NO_DEVICE, "label volume allocation failed: %s", hipGetErrorString(e));
-        }
-        default_label_colors(r->lab_colors);
-        if (int e2 = put_colors(r, r->lab_colors)) { release_labels(r); return e2; }
-    }
+    if (int e = allocate_labels(r)) return e;
     DeviceScratch staging; // linear copy in HBM, re-laid out into bricks by the GPU (k_relayout, 1-byte elements)
     if (int e = staging.make(n_bytes)) return e;
     HIP_TRY(hipMemcpyAsync(staging.p, host_labels, n_bytes, hipMemcpyHostToDevice, r->stream));

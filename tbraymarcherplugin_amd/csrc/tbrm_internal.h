@@ -423,6 +423,8 @@ enum Tunable : int {
                              // keeps what they share (k_light_occlusion_runs; at most kOccRunMax); 1: one unit per workgroup (the A/B switch)
     TUNE_VIEW_CACHE_MB,      // HBM budget in MiB of the view cache's records (a still view under a moving light is relit from them: k_relight);
                              // 0: off, every frame marches
+    TUNE_GROW_BATCH,         // tbrm_grow_region: propagation passes enqueued between two read-backs of their changed-bricks words (1 .. 64;
+                             // 1: a read-back per pass — the test hook). The result does not depend on it
     TUNE_COUNT
 };
 int tune(Tunable t);
@@ -531,5 +533,42 @@ struct StatsParams {
 };
 hipError_t launch_volume_histogram(const StatsParams& p, bool masked, int grid, hipStream_t s);
 hipError_t launch_label_statistics(const StatsParams& p, int grid, hipStream_t s);
+
+// seeded region growing (tbrm_api_segment.cpp, tbrm_segment_kernels.hip; include/tbrm_segment.h)
+constexpr int kGrowMaxSeeds = 4096;
+constexpr int kGrowMaxBatch = 64;
+// the control words of a call (GrowParams::ctl; the host writes their start values and reads them back)
+enum GrowCtl : int {
+    GROW_VOXELS, GROW_RELABELLED, GROW_MIN_X, GROW_MIN_Y, GROW_MIN_Z, GROW_MAX_X, GROW_MAX_Y, GROW_MAX_Z, GROW_SEEDS_TAKEN,
+    GROW_BRICKS_WRITTEN, GROW_VISITS,
+    GROW_CHANGED = 16,        // kGrowMaxBatch words: bricks that changed in pass i of the batch
+    GROW_CTL_WORDS = GROW_CHANGED + kGrowMaxBatch
+};
+struct GrowParams {
+    const void* data;      // bricked data volume
+    uint8_t* labels;       // bricked label volume on the same grid (null: none, every voxel has label 0)
+    int fmt;
+    int bnx, bnxy;
+    int origin[3], end[3]; // the box [origin, end), inside the volume
+    int b0[3], nb[3];      // the bricks it touches: nb[c] from b0[c] on — the only bricks whose scratch a call reads or writes
+    uint32_t lo_code, hi_code; // UNORM: lo_code <= code <= hi_code (lo_code > hi_code: no candidate)
+    float lo_f, hi_f;          // R32_FLOAT: lo_f <= v <= hi_f (NaN voxels fail both)
+    uint32_t writable[8];
+    int all_join;          // n_seeds == 0: visited starts as the candidates
+    int conn26;
+    uint64_t* bits;        // per brick (global brick index) 16 words: candidate slices z = 0 .. 7, then visited slices; bit y * 8 + x
+    uint32_t* act[2];      // per brick: due in this pass ([0]: read and cleared) / in the next ([1]: set)
+    const int32_t* seeds;
+    int n_seeds;
+    int first_pass;        // the seeds' bricks count as changed
+    int changed_word;      // GROW_CHANGED + the pass's index in its batch
+    int new_label;
+    int32_t* ctl;          // GROW_CTL_WORDS words
+};
+hipError_t launch_grow_candidates(const GrowParams& p, hipStream_t s);
+hipError_t launch_grow_seeds(const GrowParams& p, hipStream_t s);
+hipError_t launch_grow_pass(const GrowParams& p, hipStream_t s);
+hipError_t launch_grow_measure(const GrowParams& p, hipStream_t s);
+hipError_t launch_grow_write(const GrowParams& p, const int wb0[3], const int wnb[3], hipStream_t s); // the bricks wnb from wb0 on
 
 } // namespace tbrm

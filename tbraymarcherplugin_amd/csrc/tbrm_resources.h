@@ -413,6 +413,10 @@ struct tbrm_resources {
     char* d_hit = nullptr;             // staging of the host forms: the tile's records, then its depths; grown to the largest tile seen
     size_t hit_bytes = 0;
     uint64_t hit_counters[3]{};        // tbrm_hit_counters
+
+    // seeded region growing (tbrm_api_segment.cpp; include/tbrm_segment.h)
+    char* d_grow = nullptr;            // the scratch: per brick the candidate and visited words, the two activity words; the seeds; the control words
+    uint64_t grow_counters[4]{};       // tbrm_segment_counters
 };
 
 
@@ -458,6 +462,11 @@ int ensure_stats_scratch(tbrm_resources* r, bool counted = true);
 // label overlay (tbrm_api_labels.cpp)
 int label_ray_params(tbrm_resources* r, RayParams& p); // the lit march's label step, when one is due (after the skipping metadata)
 void release_labels(tbrm_resources* r);                // (the stream must be idle)
+// everything the label step and its skipping metadata use, and the default colours: what the first tbrm_upload_label_volume takes
+// (the label bytes themselves are left as allocated); TBRM_OK at once when a label volume is attached
+int allocate_labels(tbrm_resources* r);
+int brick_masks(tbrm_resources* r, const int b0[3], const int b1[3]); // d_lab_mask of the bricks [b0, b1)
+int refresh_live(tbrm_resources* r);                   // the per-brick live bits and the volume's label set; the merged metadata goes stale
 RelayoutParams relayout_params(const void* src, void* dst, const int dims[3], const int bn[3], size_t elem, bool to_bricks);
 
 // ---- the light-pass layer (tbrm_light_plan.cpp, tbrm_factor_cache.cpp, tbrm_light_enqueue.cpp, tbrm_light_operators.cpp) ------------------------------------------------------------------------
