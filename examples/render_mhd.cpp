@@ -5,7 +5,7 @@
 //
 //   g++ -std=c++17 -O2 -I include examples/render_mhd.cpp -o render_mhd -L tbraymarcherplugin_amd/lib -ltbrm -lz
 //       (plus -Wl,-rpath,$PWD/tbraymarcherplugin_amd/lib -Wl,-rpath,/opt/rocm/lib to run it in place)
-//   ./render_mhd volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]]
+//   ./render_mhd volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]]
 //       --light-color: the key light's colour (components in [0, 1]) on an RGB light volume (include/tbrm_color_lights.h); the fill stays white
 //       --auto-window: the window comes from the data (ARaymarchVolume::AutoWindow, include/tbrm_volume_stats.h): the span between
 //                      the LOW and HIGH percentiles of the value histogram, 0.01,0.99 when not given
@@ -14,6 +14,9 @@
 //       --grow: a click on the frame's pixel (X, Y) (ARaymarchVolume::GrowRegionAt, include/tbrm_segment.h): the voxels connected to the
 //                      one under it whose stored value (the 16-bit code) is within TOL of its own get label LABEL (1 when not given)
 //                      and the frame shows them in the label's colour; printed as one "grow" line with the label's mean value
+//       --morph: after --grow, binary morphology of label LABEL (the grown label when not given) (ARaymarchVolume::MorphLabel,
+//                      include/tbrm_morphology.h): OP is dilate, erode, open or close, R the radius in unit steps of the 6-neighbour
+//                      cross; voxels that leave the label get label 0; printed as one "morph" line
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -59,6 +62,17 @@ int main(int argc, char** argv)
             argc -= 2;
             break;
         }
+    char morph_op[8] = "";
+    int morph_radius = 0, morph_label = -1;
+    bool morph = false;
+    for (int i = 1; i + 1 < argc; ++i)
+        if (!std::strcmp(argv[i], "--morph")) {
+            if (std::sscanf(argv[i + 1], "%7[a-z],%d,%d", morph_op, &morph_radius, &morph_label) < 2) { argc = 0; break; }
+            morph = true;
+            for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
+            argc -= 2;
+            break;
+        }
     for (int i = 1; i + 1 < argc; ++i) // the option and its value leave the positional arguments
         if (!std::strcmp(argv[i], "--light-color")) {
             if (std::sscanf(argv[i + 1], "%f,%f,%f", &key_color[0], &key_color[1], &key_color[2]) != 3) { argc = 0; break; }
@@ -68,7 +82,7 @@ int main(int argc, char** argv)
             break;
         }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]]\n", argv[0]);
         return 2;
     }
     const int width = argc > 3 ? std::atoi(argv[3]) : 512, height = argc > 4 ? std::atoi(argv[4]) : 512;
@@ -135,6 +149,21 @@ int main(int argc, char** argv)
                         g.Seed[2], g.LoUsed, g.HiUsed, (unsigned long long) g.Voxels, g.BoxMin[0], g.BoxMin[1], g.BoxMin[2], g.BoxMax[0], g.BoxMax[1], g.BoxMax[2],
                         grow_label, s.count > s.nan_count ? s.sum / (double) (s.count - s.nan_count) : 0.0);
         }
+    }
+    if (morph) { // after the grow, before the frame
+        static const char* const names[4] = {"dilate", "erode", "open", "close"};
+        int op = -1;
+        for (int k = 0; k < 4; ++k)
+            if (!std::strcmp(morph_op, names[k])) op = k;
+        if (morph_label < 0) morph_label = grow_label;
+        FMorphResult m;
+        if (!volume.MorphLabel(op, morph_radius, morph_label, m)) {
+            std::fprintf(stderr, "morph failed: %s\n", op < 0 ? "OP must be dilate, erode, open or close" : tbrm_last_error());
+            return 1;
+        }
+        std::printf("morph %s %d label %d source %llu result %llu added %llu removed %llu box %d %d %d .. %d %d %d launches %d\n", morph_op, morph_radius,
+                    morph_label, (unsigned long long) m.SourceVoxels, (unsigned long long) m.ResultVoxels, (unsigned long long) m.Added,
+                    (unsigned long long) m.Removed, m.BoxMin[0], m.BoxMin[1], m.BoxMin[2], m.BoxMax[0], m.BoxMax[1], m.BoxMax[2], m.Launches);
     }
     std::vector<float> rgba((size_t) width * height * 4);
     if (!volume.RenderLit(cam, rgba.data())) {

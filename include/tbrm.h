@@ -206,7 +206,8 @@ TBRM_API int tbrm_device_count(int* out_count);   /* TBRM_ERR_NO_DEVICE when the
  * hook and an A/B switch), view_cache_mb (1536 = MiB of records per handle from which a lit frame of an unchanged view is relit
  * instead of marched again, bit-identically: tbrm_view_cache.h; 0 = every frame marches), grow_batch (16 = propagation passes of
  * tbrm_grow_region, tbrm_segment.h, enqueued between two read-backs of their changed-bricks words, 1 .. 64; 1 = a read-back per pass:
- * a test hook; the result is the same for every value). Unknown name: TBRM_ERR_INVALID_ARG. */
+ * a test hook; the result is the same for every value), morph_steps (8 = unit steps of tbrm_morph_labels, tbrm_morphology.h, that one
+ * launch of its step kernel iterates, 1 .. 8; 1 = a launch per step: a test hook). Unknown name: TBRM_ERR_INVALID_ARG. */
 TBRM_API int tbrm_set_tunable(const char* name, int32_t value);
 TBRM_API int tbrm_get_tunable(const char* name, int32_t* value);
 

@@ -21,6 +21,7 @@
 #include "tbrm_volume_stats.h"
 #include "tbrm_hit.h"
 #include "tbrm_segment.h"
+#include "tbrm_morphology.h"
 
 #include <algorithm>
 #include <cmath>
@@ -278,6 +279,15 @@ struct FGrowResult {
     double LoUsed = 0.0, HiUsed = 0.0; // the value range applied, in stored units
 };
 
+// What a label morphology call found (include/tbrm_morphology.h): ARaymarchVolume::MorphLabel and its four named forms
+struct FMorphResult {
+    uint64_t SourceVoxels = 0, ResultVoxels = 0; // the label's voxels before and the operator's result, inside the box
+    uint64_t Added = 0, Removed = 0;             // voxels that joined / left the label
+    uint64_t Relabelled = 0;                     // label bytes that changed
+    int BoxMin[3] = {0, 0, 0}, BoxMax[3] = {-1, -1, -1}; // of what joined or left, inclusive; nothing: the volume's size and -1
+    int Launches = 0;
+};
+
 class ARaymarchVolume {
 public:
     // ---- the reflected properties the hot path consumes (RaymarchVolume.h:60-266) ----
@@ -447,6 +457,38 @@ public:
         for (int c = 0; c < 3; ++c) Out.Seed[c] = seed[c];
         return ok;
     }
+
+    // Binary morphology of one label (include/tbrm_morphology.h; no counterpart in the reference): Op (TBRM_MORPH_DILATE .. CLOSE)
+    // by Radius unit steps of the 6-neighbour cross or the 3 x 3 x 3 cube, on the device. Voxels that join get Label (over any
+    // label), voxels that leave get EraseLabel; bMeasureOnly counts them and writes nothing. Like the other label edits it requests
+    // no recompute. Needs a label volume.
+    bool MorphLabel(int Op, int Radius, int Label, FMorphResult& Out, int Connectivity = 6, int EraseLabel = 0, bool bMeasureOnly = false)
+    {
+        Out = FMorphResult{};
+        if (!RaymarchResources.Handle || Label < 0 || Label > 255) return false;
+        tbrm_morph_desc d{};
+        d.op = Op;
+        d.radius = Radius;
+        d.connectivity = Connectivity;
+        d.new_label = bMeasureOnly ? -1 : Label;
+        d.erase_label = EraseLabel;
+        d.source[Label >> 5] = 1u << (Label & 31);
+        for (uint32_t& w : d.writable) w = 0xffffffffu;
+        tbrm_morph_result r{};
+        if (tbrm_morph_labels(RaymarchResources.Handle, &d, &r) != TBRM_OK) return false;
+        Out.SourceVoxels = r.source_voxels;
+        Out.ResultVoxels = r.result_voxels;
+        Out.Added = r.added;
+        Out.Removed = r.removed;
+        Out.Relabelled = r.relabelled;
+        for (int c = 0; c < 3; ++c) { Out.BoxMin[c] = r.bbox_min[c]; Out.BoxMax[c] = r.bbox_max[c]; }
+        Out.Launches = r.launches;
+        return true;
+    }
+    bool DilateLabel(int Radius, int Label, FMorphResult& Out, int Connectivity = 6) { return MorphLabel(TBRM_MORPH_DILATE, Radius, Label, Out, Connectivity); }
+    bool ErodeLabel(int Radius, int Label, FMorphResult& Out, int Connectivity = 6) { return MorphLabel(TBRM_MORPH_ERODE, Radius, Label, Out, Connectivity); }
+    bool OpenLabel(int Radius, int Label, FMorphResult& Out, int Connectivity = 6) { return MorphLabel(TBRM_MORPH_OPEN, Radius, Label, Out, Connectivity); }
+    bool CloseLabel(int Radius, int Label, FMorphResult& Out, int Connectivity = 6) { return MorphLabel(TBRM_MORPH_CLOSE, Radius, Label, Out, Connectivity); }
 
     // :746-784 — every windowing change requests a full recompute
     void SetWindowCenter(float Center) { if (Center != RaymarchResources.WindowingParameters.Center) { RaymarchResources.WindowingParameters.Center = Center; WindowingChanged(); } }

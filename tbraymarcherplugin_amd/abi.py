@@ -215,6 +215,25 @@ class GROW_RESULT(C.Structure):  # tbrm_grow_result
                 ("passes", C.c_int32), ("seeds_taken", C.c_int32), ("lo_used", C.c_double), ("hi_used", C.c_double)]
 
 
+# every symbol include/tbrm_morphology.h declares (label morphology; tests/test_morph_abi.py checks the header against this list)
+MORPH_SYMBOLS = ["tbrm_morph_abi_version", "tbrm_morph_labels", "tbrm_morph_counters"]
+
+MORPH_ABI_VERSION = 1  # TBRM_MORPH_ABI_VERSION of include/tbrm_morphology.h
+MORPH_MAX_RADIUS = 64
+MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = range(4)
+MORPH_OPS = {"dilate": MORPH_DILATE, "erode": MORPH_ERODE, "open": MORPH_OPEN, "close": MORPH_CLOSE}
+
+
+class MORPH_DESC(C.Structure):  # tbrm_morph_desc
+    _fields_ = [("origin", C.c_int32 * 3), ("extent", C.c_int32 * 3), ("op", C.c_int32), ("radius", C.c_int32), ("connectivity", C.c_int32),
+                ("new_label", C.c_int32), ("erase_label", C.c_int32), ("reserved", C.c_int32), ("source", C.c_uint32 * 8), ("writable", C.c_uint32 * 8)]
+
+
+class MORPH_RESULT(C.Structure):  # tbrm_morph_result
+    _fields_ = [("source_voxels", C.c_uint64), ("result_voxels", C.c_uint64), ("added", C.c_uint64), ("removed", C.c_uint64), ("relabelled", C.c_uint64),
+                ("bbox_min", C.c_int32 * 3), ("bbox_max", C.c_int32 * 3), ("launches", C.c_int32), ("reserved", C.c_int32)]
+
+
 _lib = None
 
 
@@ -363,6 +382,12 @@ def load():
     lib.tbrm_attach_empty_label_volume.argtypes = [vp]
     lib.tbrm_host_hit_voxel.argtypes = [P(C.c_int32 * 3), vp, P(C.c_int32 * 3)]
     lib.tbrm_segment_counters.argtypes = [vp, P(C.c_uint64 * 4)]
+    have = lib.tbrm_morph_abi_version() if hasattr(lib, "tbrm_morph_abi_version") else -1
+    if have != MORPH_ABI_VERSION:
+        raise ImportError(f"{LIB_PATH} has morphology ABI version {have}, this binding is written against {MORPH_ABI_VERSION}: rebuild it "
+                          "(`python tbraymarcherplugin_amd/build.py --force`)")
+    lib.tbrm_morph_labels.argtypes = [vp, P(MORPH_DESC), P(MORPH_RESULT)]
+    lib.tbrm_morph_counters.argtypes = [vp, P(C.c_uint64 * 4)]
     _lib = lib
     return lib
 
@@ -767,6 +792,40 @@ class Resources:
         out = (C.c_uint64 * 4)()
         check(self.lib.tbrm_segment_counters(self.handle, C.byref(out)))
         return {k: int(out[i]) for i, k in enumerate(self.SEGMENT_COUNTERS)}
+
+    # label morphology (include/tbrm_morphology.h): boxes as (x, y, z)
+    def morph_desc(self, op, radius, source, new_label, connectivity=6, origin=None, extent=None, writable=None, erase_label=0):
+        """op: MORPH_DILATE .. MORPH_CLOSE or its name; source: the label values of the set; writable: the label values a joining voxel
+        may overwrite (None: every label); new_label -1: measure only"""
+        d = MORPH_DESC()
+        if extent is not None:
+            d.origin[:] = [int(v) for v in (origin if origin is not None else (0, 0, 0))]
+            d.extent[:] = [int(v) for v in extent]
+        d.op, d.radius, d.connectivity = int(MORPH_OPS.get(op, op)), int(radius), int(connectivity)
+        d.new_label, d.erase_label = int(new_label), int(erase_label)
+        for l in source:
+            d.source[int(l) >> 5] |= 1 << (int(l) & 31)
+        if writable is None:
+            d.writable[:] = [0xFFFFFFFF] * 8
+        else:
+            for l in writable:
+                d.writable[int(l) >> 5] |= 1 << (int(l) & 31)
+        return d
+
+    def morph_labels(self, op, radius, source, new_label, connectivity=6, origin=None, extent=None, writable=None, erase_label=0):
+        """tbrm_morph_labels: {"source_voxels", "result_voxels", "added", "removed", "relabelled", "bbox_min", "bbox_max", "launches"}"""
+        d = self.morph_desc(op, radius, source, new_label, connectivity, origin, extent, writable, erase_label)
+        out = MORPH_RESULT()
+        check(self.lib.tbrm_morph_labels(self.handle, C.byref(d), C.byref(out)))
+        return {"source_voxels": int(out.source_voxels), "result_voxels": int(out.result_voxels), "added": int(out.added), "removed": int(out.removed),
+                "relabelled": int(out.relabelled), "bbox_min": tuple(out.bbox_min[:]), "bbox_max": tuple(out.bbox_max[:]), "launches": int(out.launches)}
+
+    MORPH_COUNTERS = ("morph_calls", "step_launches", "windows", "bricks_written")
+
+    def morph_counters(self):
+        out = (C.c_uint64 * 4)()
+        check(self.lib.tbrm_morph_counters(self.handle, C.byref(out)))
+        return {k: int(out[i]) for i, k in enumerate(self.MORPH_COUNTERS)}
 
     def is_initialized(self):
         return bool(self.lib.tbrm_resources_is_initialized(self.handle))

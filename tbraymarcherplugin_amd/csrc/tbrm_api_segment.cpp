@@ -20,14 +20,11 @@ namespace {
 
 size_t grow_bricks(const tbrm_resources* r) { return (size_t) r->dbn[0] * r->dbn[1] * r->dbn[2]; }
 
+} // namespace
+
+namespace tbrm_host {
+
 // the scratch, in one allocation: [bits: 16 words per brick][activity: 2 words per brick][seeds][control words], each part 256-byte aligned
-struct GrowScratch {
-    uint64_t* bits;
-    uint32_t* act[2];
-    int32_t* seeds;
-    int32_t* ctl;
-    size_t bytes;
-};
 GrowScratch grow_scratch(const tbrm_resources* r)
 {
     const size_t nb = grow_bricks(r);
@@ -51,6 +48,10 @@ int ensure_grow_scratch(tbrm_resources* r)
     HIP_TRY(hipMalloc((void**) &r->d_grow, grow_scratch(r).bytes));
     return TBRM_OK;
 }
+
+} // namespace tbrm_host
+
+namespace {
 
 // the stored value of one voxel, as the double the header's units carry it in
 int read_voxel(tbrm_resources* r, const int32_t xyz[3], double* out)

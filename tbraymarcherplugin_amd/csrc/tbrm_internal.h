@@ -425,6 +425,8 @@ enum Tunable : int {
                              // 0: off, every frame marches
     TUNE_GROW_BATCH,         // tbrm_grow_region: propagation passes enqueued between two read-backs of their changed-bricks words (1 .. 64;
                              // 1: a read-back per pass — the test hook). The result does not depend on it
+    TUNE_MORPH_STEPS,        // tbrm_morph_labels: unit steps one launch of k_morph_steps iterates in a brick's 24^3 window (1 .. 8; 1: a launch
+                             // per step — the test hook and the A/B switch). The result does not depend on it
     TUNE_COUNT
 };
 int tune(Tunable t);
@@ -570,5 +572,36 @@ hipError_t launch_grow_seeds(const GrowParams& p, hipStream_t s);
 hipError_t launch_grow_pass(const GrowParams& p, hipStream_t s);
 hipError_t launch_grow_measure(const GrowParams& p, hipStream_t s);
 hipError_t launch_grow_write(const GrowParams& p, const int wb0[3], const int wnb[3], hipStream_t s); // the bricks wnb from wb0 on
+
+// label morphology (tbrm_api_morph.cpp, tbrm_morph_kernels.hip; include/tbrm_morphology.h). It works in the scratch of region growing:
+// the 16 words of a brick are two boards of 8 slice words (bit y * 8 + x of word z), the two activity words are the boards' classes.
+enum : uint32_t { MORPH_EMPTY = 0, MORPH_FULL = 1, MORPH_MIXED = 2 }; // of a board: no bit, every in-volume bit, neither
+// the control words of a call (MorphParams::ctl), inside the GROW_CTL_WORDS words of the scratch: 64-bit counts, then the 32-bit box
+enum MorphCtl : int {
+    MORPH_SOURCE, MORPH_RESULT, MORPH_ADDED, MORPH_REMOVED, MORPH_RELABELLED, MORPH_WINDOWS, MORPH_BRICKS_WRITTEN, MORPH_CTL_COUNTS, // uint64 each
+    MORPH_MIN_X = 2 * MORPH_CTL_COUNTS, MORPH_MIN_Y, MORPH_MIN_Z, MORPH_MAX_X, MORPH_MAX_Y, MORPH_MAX_Z, MORPH_CTL_WORDS             // int32 each
+};
+static_assert((int) MORPH_CTL_WORDS <= (int) GROW_CTL_WORDS, "the morphology control words live in the region growing scratch");
+struct MorphParams {
+    uint8_t* labels;       // bricked label volume
+    int bnx, bnxy;
+    int dims[3];           // the volume in voxels: bits outside it are never set
+    int origin[3], end[3]; // the box [origin, end) that may change
+    int b0[3], nb[3];      // the bricks of the box grown by the operator's reach: the only bricks whose scratch a call reads or writes
+    int wb0[3], wnb[3];    // the bricks of the box
+    uint32_t source[8], writable[8];
+    uint64_t* bits;        // per brick (global brick index) 16 words: board 0, board 1
+    uint32_t* cls[2];      // per brick: the class of board 0 / 1
+    int from;              // k_morph_steps reads board `from` and writes the other; k_morph_write reads board `from`
+    int steps;             // unit steps of this launch, 1 .. 8
+    int erode;             // the steps erode: the same loop on the complement inside the volume
+    int conn26;
+    int new_label;         // -1: count only
+    int erase_label;
+    int32_t* ctl;
+};
+hipError_t launch_morph_load(const MorphParams& p, hipStream_t s);
+hipError_t launch_morph_steps(const MorphParams& p, hipStream_t s);
+hipError_t launch_morph_write(const MorphParams& p, hipStream_t s);
 
 } // namespace tbrm

@@ -417,6 +417,7 @@ struct tbrm_resources {
     // seeded region growing (tbrm_api_segment.cpp; include/tbrm_segment.h)
     char* d_grow = nullptr;            // the scratch: per brick the candidate and visited words, the two activity words; the seeds; the control words
     uint64_t grow_counters[4]{};       // tbrm_segment_counters
+    uint64_t morph_counters[4]{};      // tbrm_morph_counters (include/tbrm_morphology.h; the call works in d_grow)
 };
 
 
@@ -467,6 +468,17 @@ void release_labels(tbrm_resources* r);                // (the stream must be id
 int allocate_labels(tbrm_resources* r);
 int brick_masks(tbrm_resources* r, const int b0[3], const int b1[3]); // d_lab_mask of the bricks [b0, b1)
 int refresh_live(tbrm_resources* r);                   // the per-brick live bits and the volume's label set; the merged metadata goes stale
+// the scratch of region growing (tbrm_api_segment.cpp), which label morphology (tbrm_api_morph.cpp) works in too: where its parts lie,
+// and the handle's one allocation of it (counted as an operator allocation)
+struct GrowScratch {
+    uint64_t* bits;
+    uint32_t* act[2];
+    int32_t* seeds;
+    int32_t* ctl;
+    size_t bytes;
+};
+GrowScratch grow_scratch(const tbrm_resources* r);
+int ensure_grow_scratch(tbrm_resources* r);
 RelayoutParams relayout_params(const void* src, void* dst, const int dims[3], const int bn[3], size_t elem, bool to_bricks);
 
 // ---- the light-pass layer (tbrm_light_plan.cpp, tbrm_factor_cache.cpp, tbrm_light_enqueue.cpp, tbrm_light_operators.cpp) ------------------------------------------------------------------------
