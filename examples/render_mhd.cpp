@@ -5,7 +5,7 @@
 //
 //   g++ -std=c++17 -O2 -I include examples/render_mhd.cpp -o render_mhd -L tbraymarcherplugin_amd/lib -ltbrm -lz
 //       (plus -Wl,-rpath,$PWD/tbraymarcherplugin_amd/lib -Wl,-rpath,/opt/rocm/lib to run it in place)
-//   ./render_mhd volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]]
+//   ./render_mhd volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]] [--islands OP,N[,LABEL]]
 //       --light-color: the key light's colour (components in [0, 1]) on an RGB light volume (include/tbrm_color_lights.h); the fill stays white
 //       --auto-window: the window comes from the data (ARaymarchVolume::AutoWindow, include/tbrm_volume_stats.h): the span between
 //                      the LOW and HIGH percentiles of the value histogram, 0.01,0.99 when not given
@@ -17,6 +17,10 @@
 //       --morph: after --grow, binary morphology of label LABEL (the grown label when not given) (ARaymarchVolume::MorphLabel,
 //                      include/tbrm_morphology.h): OP is dilate, erode, open or close, R the radius in unit steps of the 6-neighbour
 //                      cross; voxels that leave the label get label 0; printed as one "morph" line
+//       --islands: after --grow and --morph, the islands of label LABEL (the grown label when not given) (ARaymarchVolume::KeepLargestIslands
+//                      and its kin, include/tbrm_islands.h), 6-connected: OP is keep (the N largest stay, the others get label 0), remove
+//                      (islands of fewer than N voxels get label 0), split (the N largest get LABEL, LABEL + 1, ..) or fill (what the
+//                      label encloses, up to N voxels a hole, 0: of any size, joins it); printed as one "islands" line
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -73,6 +77,18 @@ int main(int argc, char** argv)
             argc -= 2;
             break;
         }
+    char islands_op[8] = "";
+    long long islands_n = 0;
+    int islands_label = -1;
+    bool islands = false;
+    for (int i = 1; i + 1 < argc; ++i)
+        if (!std::strcmp(argv[i], "--islands")) {
+            if (std::sscanf(argv[i + 1], "%7[a-z],%lld,%d", islands_op, &islands_n, &islands_label) < 2) { argc = 0; break; }
+            islands = true;
+            for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
+            argc -= 2;
+            break;
+        }
     for (int i = 1; i + 1 < argc; ++i) // the option and its value leave the positional arguments
         if (!std::strcmp(argv[i], "--light-color")) {
             if (std::sscanf(argv[i + 1], "%f,%f,%f", &key_color[0], &key_color[1], &key_color[2]) != 3) { argc = 0; break; }
@@ -82,7 +98,7 @@ int main(int argc, char** argv)
             break;
         }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]] [--islands OP,N[,LABEL]]\n", argv[0]);
         return 2;
     }
     const int width = argc > 3 ? std::atoi(argv[3]) : 512, height = argc > 4 ? std::atoi(argv[4]) : 512;
@@ -164,6 +180,25 @@ int main(int argc, char** argv)
         std::printf("morph %s %d label %d source %llu result %llu added %llu removed %llu box %d %d %d .. %d %d %d launches %d\n", morph_op, morph_radius,
                     morph_label, (unsigned long long) m.SourceVoxels, (unsigned long long) m.ResultVoxels, (unsigned long long) m.Added,
                     (unsigned long long) m.Removed, m.BoxMin[0], m.BoxMin[1], m.BoxMin[2], m.BoxMax[0], m.BoxMax[1], m.BoxMax[2], m.Launches);
+    }
+    if (islands) { // after the grow and the morphology, before the frame
+        if (islands_label < 0) islands_label = grow_label;
+        FIslandsResult r;
+        bool known = true, ok = false;
+        if (islands_n < 0 || islands_n > 0x7fffffff) known = false;
+        else if (!std::strcmp(islands_op, "keep")) ok = volume.KeepLargestIslands(islands_label, (int) islands_n, r);
+        else if (!std::strcmp(islands_op, "remove")) ok = volume.RemoveSmallIslands(islands_label, (uint64_t) islands_n, r);
+        else if (!std::strcmp(islands_op, "split")) ok = volume.SplitIslands(islands_label, islands_label, (int) islands_n, r);
+        else if (!std::strcmp(islands_op, "fill")) ok = volume.FillLabelHoles(islands_label, r, islands_n == 0 ? UINT64_MAX : (uint64_t) islands_n);
+        else known = false;
+        if (!ok) {
+            std::fprintf(stderr, "islands failed: %s\n", known ? tbrm_last_error() : "OP must be keep, remove, split or fill, N >= 0");
+            return 1;
+        }
+        std::printf("islands %s %lld label %d set %llu islands %llu spared %llu kept %llu dropped %llu kept_voxels %llu dropped_voxels %llu largest %llu relabelled %llu box %d %d %d .. %d %d %d\n",
+                    islands_op, islands_n, islands_label, (unsigned long long) r.SetVoxels, (unsigned long long) r.Islands, (unsigned long long) r.Spared,
+                    (unsigned long long) r.Kept, (unsigned long long) r.Dropped, (unsigned long long) r.KeptVoxels, (unsigned long long) r.DroppedVoxels,
+                    (unsigned long long) r.Largest, (unsigned long long) r.Relabelled, r.BoxMin[0], r.BoxMin[1], r.BoxMin[2], r.BoxMax[0], r.BoxMax[1], r.BoxMax[2]);
     }
     std::vector<float> rgba((size_t) width * height * 4);
     if (!volume.RenderLit(cam, rgba.data())) {

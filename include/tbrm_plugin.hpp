@@ -22,6 +22,7 @@
 #include "tbrm_hit.h"
 #include "tbrm_segment.h"
 #include "tbrm_morphology.h"
+#include "tbrm_islands.h"
 
 #include <algorithm>
 #include <cmath>
@@ -288,6 +289,17 @@ struct FMorphResult {
     int Launches = 0;
 };
 
+// What an island call found (include/tbrm_islands.h): ARaymarchVolume::KeepLargestIslands / RemoveSmallIslands / SplitIslands /
+// FillLabelHoles
+struct FIslandsResult {
+    uint64_t SetVoxels = 0;                      // the voxels the islands were taken of
+    uint64_t Islands = 0, Spared = 0;            // islands in the order; islands on a face of the volume left out of it (FillLabelHoles)
+    uint64_t Kept = 0, Dropped = 0, KeptVoxels = 0, DroppedVoxels = 0;
+    uint64_t Largest = 0;                        // voxels of the largest island
+    uint64_t Relabelled = 0;                     // label bytes that changed
+    int BoxMin[3] = {0, 0, 0}, BoxMax[3] = {-1, -1, -1}; // of the changed bytes, inclusive; none: the volume's size and -1
+};
+
 class ARaymarchVolume {
 public:
     // ---- the reflected properties the hot path consumes (RaymarchVolume.h:60-266) ----
@@ -490,6 +502,73 @@ public:
     bool OpenLabel(int Radius, int Label, FMorphResult& Out, int Connectivity = 6) { return MorphLabel(TBRM_MORPH_OPEN, Radius, Label, Out, Connectivity); }
     bool CloseLabel(int Radius, int Label, FMorphResult& Out, int Connectivity = 6) { return MorphLabel(TBRM_MORPH_CLOSE, Radius, Label, Out, Connectivity); }
 
+    // The islands of one label (include/tbrm_islands.h; no counterpart in the reference): its connected components, ordered by size,
+    // on the device. The four tools are parameter sets of one rule. Like the other label edits they request no recompute. They need a
+    // label volume.
+    bool LabelIslands(const tbrm_islands_desc& Desc, FIslandsResult& Out, tbrm_island* Table = nullptr, int Capacity = 0)
+    {
+        Out = FIslandsResult{};
+        if (!RaymarchResources.Handle) return false;
+        tbrm_islands_result r{};
+        if (tbrm_label_islands(RaymarchResources.Handle, &Desc, Table, Capacity, &r) != TBRM_OK) return false;
+        Out.SetVoxels = r.set_voxels;
+        Out.Islands = r.islands;
+        Out.Spared = r.spared;
+        Out.Kept = r.kept;
+        Out.Dropped = r.dropped;
+        Out.KeptVoxels = r.kept_voxels;
+        Out.DroppedVoxels = r.dropped_voxels;
+        Out.Largest = r.largest;
+        Out.Relabelled = r.relabelled;
+        for (int c = 0; c < 3; ++c) { Out.BoxMin[c] = r.bbox_min[c]; Out.BoxMax[c] = r.bbox_max[c]; }
+        return true;
+    }
+    // the Count largest islands of Label stay, the others get EraseLabel
+    bool KeepLargestIslands(int Label, int Count, FIslandsResult& Out, int Connectivity = 6, int EraseLabel = 0)
+    {
+        Out = FIslandsResult{};
+        if (Label < 0 || Label > 255 || Count < 1) return false;
+        tbrm_islands_desc d = IslandsOf(Label, Connectivity);
+        d.max_islands = Count;
+        d.drop_label = EraseLabel;
+        return LabelIslands(d, Out);
+    }
+    // islands of Label with fewer than MinVoxels voxels get EraseLabel
+    bool RemoveSmallIslands(int Label, uint64_t MinVoxels, FIslandsResult& Out, int Connectivity = 6, int EraseLabel = 0)
+    {
+        Out = FIslandsResult{};
+        if (Label < 0 || Label > 255) return false;
+        tbrm_islands_desc d = IslandsOf(Label, Connectivity);
+        d.min_voxels = MinVoxels;
+        d.drop_label = EraseLabel;
+        return LabelIslands(d, Out);
+    }
+    // the MaxIslands largest islands of Label get FirstLabel, FirstLabel + 1, ..; the others DropLabel (-1: they stay as they are)
+    bool SplitIslands(int Label, int FirstLabel, int MaxIslands, FIslandsResult& Out, int Connectivity = 6, int DropLabel = -1)
+    {
+        Out = FIslandsResult{};
+        if (Label < 0 || Label > 255) return false;
+        tbrm_islands_desc d = IslandsOf(Label, Connectivity);
+        d.max_islands = MaxIslands;
+        d.keep_label = FirstLabel;
+        d.label_step = 1;
+        d.drop_label = DropLabel;
+        return LabelIslands(d, Out);
+    }
+    // what Label encloses — the islands of every other label that touch no face of the volume, of at most MaxVoxels voxels
+    // (UINT64_MAX: of any size) — gets Label; Connectivity is that of the enclosed background
+    bool FillLabelHoles(int Label, FIslandsResult& Out, uint64_t MaxVoxels = UINT64_MAX, int Connectivity = 6)
+    {
+        Out = FIslandsResult{};
+        if (Label < 0 || Label > 255) return false;
+        tbrm_islands_desc d = IslandsOf(Label, Connectivity);
+        for (uint32_t& w : d.source) w = ~w;
+        d.spare_border = 1;
+        d.min_voxels = MaxVoxels == UINT64_MAX ? UINT64_MAX : MaxVoxels + 1;
+        d.drop_label = Label;
+        return LabelIslands(d, Out);
+    }
+
     // :746-784 — every windowing change requests a full recompute
     void SetWindowCenter(float Center) { if (Center != RaymarchResources.WindowingParameters.Center) { RaymarchResources.WindowingParameters.Center = Center; WindowingChanged(); } }
     void SetWindowWidth(float Width) { if (Width != RaymarchResources.WindowingParameters.Width) { RaymarchResources.WindowingParameters.Width = Width; WindowingChanged(); } }
@@ -677,6 +756,16 @@ public:
 private:
     std::map<ARaymarchLight*, FDirLightParameters> LightParametersMap;
     bool bHasTF = false;
+    // the islands of one label, nothing written yet: every island kept, every byte left
+    static tbrm_islands_desc IslandsOf(int Label, int Connectivity)
+    {
+        tbrm_islands_desc d{};
+        d.connectivity = Connectivity;
+        d.keep_label = -1;
+        d.drop_label = -1;
+        d.source[Label >> 5] = 1u << (Label & 31);
+        return d;
+    }
     // the histogram of ComputeHistogram and the value range [Lo, Hi] its bins cover (stored units)
     bool HistogramWithRange(int NumBins, std::vector<uint64_t>& Out, double& Lo, double& Hi)
     {

@@ -234,6 +234,31 @@ class MORPH_RESULT(C.Structure):  # tbrm_morph_result
                 ("bbox_min", C.c_int32 * 3), ("bbox_max", C.c_int32 * 3), ("launches", C.c_int32), ("reserved", C.c_int32)]
 
 
+# every symbol include/tbrm_islands.h declares (the islands of a label; tests/test_islands_abi.py checks the header against this list)
+ISLANDS_SYMBOLS = ["tbrm_islands_abi_version", "tbrm_label_islands", "tbrm_islands_counters"]
+
+ISLANDS_ABI_VERSION = 1  # TBRM_ISLANDS_ABI_VERSION of include/tbrm_islands.h
+ISLANDS_MEASURE = 1      # tbrm_islands_desc::flags
+ISLAND_KEPT, ISLAND_BORDER = 1, 2  # tbrm_island::flags
+ISLANDS_ANY_SIZE = 0xFFFFFFFFFFFFFFFF  # min_voxels of fill_label_holes: holes of any size
+
+
+class ISLANDS_DESC(C.Structure):  # tbrm_islands_desc
+    _fields_ = [("origin", C.c_int32 * 3), ("extent", C.c_int32 * 3), ("connectivity", C.c_int32), ("max_islands", C.c_int32), ("min_voxels", C.c_uint64),
+                ("keep_label", C.c_int32), ("label_step", C.c_int32), ("drop_label", C.c_int32), ("spare_border", C.c_int32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32), ("source", C.c_uint32 * 8)]
+
+
+class ISLANDS_RESULT(C.Structure):  # tbrm_islands_result
+    _fields_ = [("set_voxels", C.c_uint64), ("islands", C.c_uint64), ("spared", C.c_uint64), ("kept", C.c_uint64), ("dropped", C.c_uint64),
+                ("kept_voxels", C.c_uint64), ("dropped_voxels", C.c_uint64), ("largest", C.c_uint64), ("relabelled", C.c_uint64),
+                ("bbox_min", C.c_int32 * 3), ("bbox_max", C.c_int32 * 3), ("table_entries", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ISLAND(C.Structure):  # tbrm_island
+    _fields_ = [("voxels", C.c_uint64), ("first", C.c_int32 * 3), ("label", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 _lib = None
 
 
@@ -388,6 +413,12 @@ def load():
                           "(`python tbraymarcherplugin_amd/build.py --force`)")
     lib.tbrm_morph_labels.argtypes = [vp, P(MORPH_DESC), P(MORPH_RESULT)]
     lib.tbrm_morph_counters.argtypes = [vp, P(C.c_uint64 * 4)]
+    have = lib.tbrm_islands_abi_version() if hasattr(lib, "tbrm_islands_abi_version") else -1
+    if have != ISLANDS_ABI_VERSION:
+        raise ImportError(f"{LIB_PATH} has islands ABI version {have}, this binding is written against {ISLANDS_ABI_VERSION}: rebuild it "
+                          "(`python tbraymarcherplugin_amd/build.py --force`)")
+    lib.tbrm_label_islands.argtypes = [vp, P(ISLANDS_DESC), P(ISLAND), C.c_int32, P(ISLANDS_RESULT)]
+    lib.tbrm_islands_counters.argtypes = [vp, P(C.c_uint64 * 6)]
     _lib = lib
     return lib
 
@@ -826,6 +857,64 @@ class Resources:
         out = (C.c_uint64 * 4)()
         check(self.lib.tbrm_morph_counters(self.handle, C.byref(out)))
         return {k: int(out[i]) for i, k in enumerate(self.MORPH_COUNTERS)}
+
+    # the islands of a label (include/tbrm_islands.h): boxes and first voxels as (x, y, z)
+    def islands_desc(self, source, connectivity=6, max_islands=0, min_voxels=0, keep_label=-1, label_step=0, drop_label=-1, spare_border=False,
+                     measure=False, origin=None, extent=None):
+        """source: the label values of the set, or a ready 8-word mask (a tuple of 8 ints)"""
+        d = ISLANDS_DESC()
+        if extent is not None:
+            d.origin[:] = [int(v) for v in (origin if origin is not None else (0, 0, 0))]
+            d.extent[:] = [int(v) for v in extent]
+        d.connectivity, d.max_islands, d.min_voxels = int(connectivity), int(max_islands), int(min_voxels)
+        d.keep_label, d.label_step, d.drop_label = int(keep_label), int(label_step), int(drop_label)
+        d.spare_border, d.flags = int(spare_border), ISLANDS_MEASURE if measure else 0
+        for l in source:
+            d.source[int(l) >> 5] |= 1 << (int(l) & 31)
+        return d
+
+    ISLANDS_FIELDS = ("set_voxels", "islands", "spared", "kept", "dropped", "kept_voxels", "dropped_voxels", "largest", "relabelled")
+
+    def label_islands(self, source, connectivity=6, max_islands=0, min_voxels=0, keep_label=-1, label_step=0, drop_label=-1, spare_border=False,
+                      measure=False, origin=None, extent=None, table=0):
+        """tbrm_label_islands: the result's fields, "bbox_min", "bbox_max", "table_entries" and "table": the first `table` islands of the
+        order as dicts {"voxels", "first", "label", "kept", "border"}"""
+        d = self.islands_desc(source, connectivity, max_islands, min_voxels, keep_label, label_step, drop_label, spare_border, measure, origin, extent)
+        out = ISLANDS_RESULT()
+        entries = (ISLAND * int(table))() if table > 0 else None
+        check(self.lib.tbrm_label_islands(self.handle, C.byref(d), entries, int(table), C.byref(out)))
+        res = {k: int(getattr(out, k)) for k in self.ISLANDS_FIELDS}
+        res.update(bbox_min=tuple(out.bbox_min[:]), bbox_max=tuple(out.bbox_max[:]), table_entries=int(out.table_entries))
+        res["table"] = [{"voxels": int(e.voxels), "first": tuple(e.first[:]), "label": int(e.label), "kept": bool(e.flags & ISLAND_KEPT),
+                         "border": bool(e.flags & ISLAND_BORDER)} for e in (entries[:out.table_entries] if entries is not None else [])]
+        return res
+
+    # the four tools: parameter sets of the one rule
+    def keep_largest_islands(self, label, n=1, erase_label=0, connectivity=6, **kw):
+        """the n largest islands of `label` stay, the others get erase_label"""
+        return self.label_islands([label], connectivity, max_islands=n, keep_label=-1, drop_label=erase_label, **kw)
+
+    def remove_small_islands(self, label, min_voxels, erase_label=0, connectivity=6, **kw):
+        """islands of `label` with fewer than min_voxels voxels get erase_label"""
+        return self.label_islands([label], connectivity, max_islands=0, min_voxels=min_voxels, keep_label=-1, drop_label=erase_label, **kw)
+
+    def split_islands(self, label, first_label, max_islands, drop_label=-1, connectivity=6, **kw):
+        """the max_islands largest islands of `label` get first_label, first_label + 1, ..; the others drop_label (-1: they stay)"""
+        return self.label_islands([label], connectivity, max_islands=max_islands, keep_label=first_label, label_step=1, drop_label=drop_label, **kw)
+
+    def fill_label_holes(self, label, max_voxels=None, connectivity=6, **kw):
+        """the islands of everything but `label` that touch no face of the box and have at most max_voxels voxels (None: any size)
+        get `label`; connectivity is the background's"""
+        others = [l for l in range(256) if l != label]
+        return self.label_islands(others, connectivity, max_islands=0, min_voxels=ISLANDS_ANY_SIZE if max_voxels is None else int(max_voxels) + 1,
+                                  keep_label=-1, drop_label=label, spare_border=True, **kw)
+
+    ISLANDS_COUNTERS = ("islands_calls", "islands_found", "bricks_written", "local_components", "scratch_bytes", "scratch_allocations")
+
+    def islands_counters(self):
+        out = (C.c_uint64 * 6)()
+        check(self.lib.tbrm_islands_counters(self.handle, C.byref(out)))
+        return {k: int(out[i]) for i, k in enumerate(self.ISLANDS_COUNTERS)}
 
     def is_initialized(self):
         return bool(self.lib.tbrm_resources_is_initialized(self.handle))

@@ -536,6 +536,7 @@ int tbrm_resources_destroy(tbrm_resources* r)
     (void) hipFree(r->d_stats);
     (void) hipFree(r->d_hit);
     (void) hipFree(r->d_grow);
+    for (char* d : r->d_islands) (void) hipFree(d);
     (void) hipFree(r->d_alpha_prefix);
     (void) hipFree(r->d_counter);
     (void) hipFree(r->d_ray_tab);

@@ -418,6 +418,11 @@ struct tbrm_resources {
     char* d_grow = nullptr;            // the scratch: per brick the candidate and visited words, the two activity words; the seeds; the control words
     uint64_t grow_counters[4]{};       // tbrm_segment_counters
     uint64_t morph_counters[4]{};      // tbrm_morph_counters (include/tbrm_morphology.h; the call works in d_grow)
+    // the islands of a label (tbrm_api_islands.cpp; include/tbrm_islands.h): the scratch per brick of the box, per slot and per island,
+    // each taken on demand and only ever grown
+    char* d_islands[3] = {nullptr, nullptr, nullptr};
+    size_t islands_bytes[3]{};
+    uint64_t islands_counters[6]{};    // tbrm_islands_counters ([4] is computed from islands_bytes)
 };
 
 
