@@ -4,8 +4,7 @@
 // A call is: the set's boards and the bricks' own components (k_islands_local), the scan of the local counts (read back: the slot
 // tables are sized from it), the slots, the merge across brick faces, the roots (read back: the sort is sized from it), the order,
 // the rule, and — a writing call, or one that wants the table's labels — the pass over the set's voxels (k_islands_write); behind a
-// write that changed a byte what tbrm_update_label_region does after its own: brick_masks over the bricks of the bounding box and
-// refresh_live. Nothing on the data side is touched, nothing waits for the occlusion stream.
+// write that changed a byte what every label write ends with (labels_changed). Nothing on the data side is touched, nothing waits for the occlusion stream.
 #include "tbrm_resources.h"
 #include "tbrm_islands_kernels.h"
 #include "../../include/tbrm_islands.h"
@@ -34,18 +33,6 @@ int ensure_islands_scratch(tbrm_resources* r, int which, size_t bytes)
     ++r->islands_counters[5];
     return TBRM_OK;
 }
-
-// carves 256-byte aligned parts out of a buffer (or only adds them up: base == nullptr)
-struct Carver {
-    char* base;
-    size_t off = 0;
-    template <class T> T* take(size_t n)
-    {
-        T* const at = base ? (T*) (base + off) : nullptr;
-        off += (n * sizeof(T) + 255) / 256 * 256;
-        return at;
-    }
-};
 
 void carve_bricks(IslandsParams& p, Carver& c)
 {
@@ -100,33 +87,26 @@ int tbrm_label_islands(tbrm_resources* r, const tbrm_islands_desc* d, tbrm_islan
     if (!r || !d || !out) return fail(TBRM_ERR_INVALID_ARG, "null argument");
     if (capacity < 0) return fail(TBRM_ERR_INVALID_ARG, "table capacity %d: must be >= 0", (int) capacity);
     if (capacity > 0 && !table) return fail(TBRM_ERR_INVALID_ARG, "null table with capacity %d", (int) capacity);
-    if (r->resident) return fail(TBRM_ERR_UNSUPPORTED, "slab-resident handle: it holds only some layers of the volume");
+    if (int e = refuse_resident(r)) return e;
     const tbrm_resources::Dims dims = r->data_dims();
     IslandsParams p{};
     for (int c = 0; c < 3; ++c) p.dims[c] = dims[c];
     if (const char* what = islands_validate(p.dims, d->origin, d->extent, d->connectivity, d->max_islands, d->keep_label, d->label_step, d->drop_label,
-                                            d->spare_border, d->flags, d->reserved, p.origin, p.end))
+                                            d->spare_border, d->flags, d->reserved, p.box.origin, p.box.end))
         return fail(TBRM_ERR_INVALID_ARG, "%s (connectivity %d, max_islands %d, keep_label %d, label_step %d, drop_label %d, spare_border %d, flags %u, reserved %u, box %d %d %d + %d %d %d in %d %d %d)",
                     what, (int) d->connectivity, (int) d->max_islands, (int) d->keep_label, (int) d->label_step, (int) d->drop_label, (int) d->spare_border,
                     (unsigned) d->flags, (unsigned) d->reserved, (int) d->origin[0], (int) d->origin[1], (int) d->origin[2], (int) d->extent[0], (int) d->extent[1],
                     (int) d->extent[2], dims[0], dims[1], dims[2]);
-    if (!r->has_volume) return fail(TBRM_ERR_NOT_INITIALIZED, "no volume: upload one with tbrm_upload_volume");
-    if (!r->d_labels) return fail(TBRM_ERR_NOT_INITIALIZED, "no label volume: tbrm_attach_empty_label_volume or tbrm_upload_label_volume");
+    if (int e = begin_label_edit(r, "no label volume")) return e;
     if ((uint64_t) dims[0] * (uint64_t) dims[1] * (uint64_t) dims[2] >= (1ull << 32))
         return fail(TBRM_ERR_UNSUPPORTED, "a volume of 2^32 voxels or more: an island's size and first voxel are 32-bit sort keys");
-    if (int e = bind(r)) return e;
 
     const bool measure = (d->flags & TBRM_ISLANDS_MEASURE) != 0;
     p.labels = r->d_labels;
     p.bnx = r->dbn[0];
     p.bnxy = r->dbn[0] * r->dbn[1];
-    uint64_t nbox = 1;
-    for (int c = 0; c < 3; ++c) {
-        p.b0[c] = p.origin[c] >> kBrickShift;
-        p.nb[c] = ((p.end[c] - 1) >> kBrickShift) - p.b0[c] + 1;
-        nbox *= (uint64_t) p.nb[c];
-    }
-    p.nbox = (uint32_t) nbox; // (fewer than 2^32 voxels: fewer than 2^23 bricks)
+    for (int c = 0; c < 3; ++c) axis_bricks(p.box.origin[c], p.box.end[c], p.range.b0[c], p.range.nb[c]);
+    p.nbox = (uint32_t) range_bricks(p.range); // (fewer than 2^32 voxels: fewer than 2^23 bricks)
     for (int w = 0; w < 8; ++w) p.source[w] = d->source[w];
     p.conn26 = d->connectivity == 26;
     p.spare = d->spare_border;
@@ -144,8 +124,8 @@ int tbrm_label_islands(tbrm_resources* r, const tbrm_islands_desc* d, tbrm_islan
         Carver at{r->d_islands[0]};
         carve_bricks(p, at);
     }
-    int32_t ctl[ISL_CTL_WORDS] = {};
-    for (int c = 0; c < 3; ++c) { ctl[ISL_MIN_X + c] = dims[c]; ctl[ISL_MAX_X + c] = -1; }
+    int32_t ctl[ISL_CTL_WORDS];
+    ctl_start(ctl, ISL_CTL_WORDS, ISL_MIN_X, dims);
     HIP_TRY(hipMemcpyAsync(p.ctl, ctl, sizeof(ctl), hipMemcpyHostToDevice, r->stream));
     HIP_TRY(launch_islands_local(p, r->stream));
     HIP_TRY(launch_islands_scan(p, r->stream));
@@ -219,15 +199,7 @@ int tbrm_label_islands(tbrm_resources* r, const tbrm_islands_desc* d, tbrm_islan
     r->islands_counters[2] += counts[ISL_BRICKS_WRITTEN];
     r->islands_counters[3] += p.total;
 
-    if (!measure && out->bbox_max[0] >= 0) { // a byte changed: the bricks the bounding box touches
-        int wb0[3], wb1[3];
-        for (int c = 0; c < 3; ++c) {
-            wb0[c] = out->bbox_min[c] >> kBrickShift;
-            wb1[c] = (out->bbox_max[c] >> kBrickShift) + 1;
-        }
-        if (int e = brick_masks(r, wb0, wb1)) return e;
-        if (int e = refresh_live(r)) return e;
-    }
+    if (!measure) return labels_changed(r, out->bbox_min, out->bbox_max); // (no byte changed: nothing to do)
     return TBRM_OK;
 }
 

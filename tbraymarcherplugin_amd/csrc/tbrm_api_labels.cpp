@@ -80,6 +80,37 @@ int brick_masks(tbrm_resources* r, const int b0[3], const int b1[3])
     return TBRM_OK;
 }
 
+int fail_box(const BoxVerdict& v, bool zero_is_whole, const int* dims, const int32_t* origin, const int32_t* extent)
+{
+    const int c = v.axis;
+    char wide[32] = "not looked at yet";
+    if (dims) snprintf(wide, sizeof(wide), "%d wide", dims[c]);
+    return fail(TBRM_ERR_INVALID_ARG, "%s: [%d, %d + %d) along axis %d of a volume %s", box_refusal_text(v.what, zero_is_whole), origin ? (int) origin[c] : 0,
+                origin ? (int) origin[c] : 0, extent ? (int) extent[c] : 0, c, wide);
+}
+
+int refuse_resident(const tbrm_resources* r)
+{
+    if (r->resident) return fail(TBRM_ERR_UNSUPPORTED, "slab-resident handle: it holds only some layers of the volume");
+    return TBRM_OK;
+}
+
+int begin_label_edit(const tbrm_resources* r, const char* no_labels)
+{
+    if (!r->has_volume) return fail(TBRM_ERR_NOT_INITIALIZED, "no volume: upload one with tbrm_upload_volume");
+    if (no_labels && !r->d_labels) return fail(TBRM_ERR_NOT_INITIALIZED, "%s: tbrm_attach_empty_label_volume or tbrm_upload_label_volume", no_labels);
+    return bind(r);
+}
+
+int labels_changed(tbrm_resources* r, const int32_t bbox_min[3], const int32_t bbox_max[3])
+{
+    if (bbox_max[0] < 0) return TBRM_OK;
+    int b0[3], b1[3];
+    bbox_bricks(bbox_min, bbox_max, b0, b1);
+    if (int e = brick_masks(r, b0, b1)) return e;
+    return refresh_live(r);
+}
+
 } // namespace tbrm_host
 
 namespace {
@@ -199,12 +230,10 @@ int tbrm_update_label_region(tbrm_resources* r, const int32_t origin[3], const i
     if (!r || !origin || !extent || !host_labels) return fail(TBRM_ERR_INVALID_ARG, "null argument");
     if (!r->d_labels) return fail(TBRM_ERR_NOT_INITIALIZED, "no label volume: upload one with tbrm_upload_label_volume");
     const tbrm_resources::Dims dims = r->data_dims();
-    size_t n = 1;
-    for (int c = 0; c < 3; ++c) {
-        if (origin[c] < 0 || extent[c] <= 0 || extent[c] > dims[c] - origin[c])
-            return fail(TBRM_ERR_INVALID_ARG, "region [%d, %d + %d) along axis %d of a volume %d wide", origin[c], origin[c], extent[c], c, dims[c]);
-        n *= (size_t) extent[c];
-    }
+    VoxelBox box;
+    const BoxVerdict v = box_resolve(dims, origin, extent, false, &box, nullptr);
+    if (v.what != BOX_OK) return fail_box(v, false, dims, origin, extent);
+    const size_t n = (size_t) extent[0] * (size_t) extent[1] * (size_t) extent[2];
     if (n_bytes != n) return fail(TBRM_ERR_INVALID_ARG, "region is %zu bytes, expected %zu", n_bytes, n);
     if (int e = bind(r)) return e;
     DeviceScratch staging;
@@ -218,10 +247,8 @@ int tbrm_update_label_region(tbrm_resources* r, const int32_t origin[3], const i
     HIP_TRY(hipMemcpyAsync(staging.p, host_labels, n_bytes, hipMemcpyHostToDevice, r->stream));
     HIP_TRY(launch_label_region(rp, r->stream));
     HIP_TRY(hipStreamSynchronize(r->stream));
-    int b0[3], b1[3]; // the bricks the box touches
-    for (int c = 0; c < 3; ++c) { b0[c] = origin[c] / kBrick; b1[c] = (origin[c] + extent[c] - 1) / kBrick + 1; }
-    if (int e = brick_masks(r, b0, b1)) return e;
-    return refresh_live(r);
+    const int32_t last[3] = {box.end[0] - 1, box.end[1] - 1, box.end[2] - 1};
+    return labels_changed(r, box.origin, last);
 }
 
 int tbrm_download_label_volume(tbrm_resources* r, uint8_t* host_out, size_t n_bytes)

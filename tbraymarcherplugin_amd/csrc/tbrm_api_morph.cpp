@@ -3,8 +3,8 @@
 //
 // A call is: the source set of the planned bricks from the label bytes into board 0 (k_morph_load), the plan's step launches
 // ping-ponging between the two boards (k_morph_steps, up to morph_steps unit steps each), the comparison of the final board with the
-// label bytes inside the box (k_morph_write: counts, bounding box and — a writing call — the bytes), and behind a write what
-// tbrm_update_label_region does after its own: brick_masks over the bricks of the bounding box and refresh_live. It works in the
+// label bytes inside the box (k_morph_write: counts, bounding box and — a writing call — the bytes), and behind a write what every
+// label write ends with (labels_changed). It works in the
 // scratch of region growing; nothing on the data side is touched, nothing waits for the occlusion stream.
 #include "tbrm_resources.h"
 #include "tbrm_morph_plan.h"
@@ -32,7 +32,7 @@ int tbrm_morph_counters(const tbrm_resources* r, uint64_t out[4])
 int tbrm_morph_labels(tbrm_resources* r, const tbrm_morph_desc* d, tbrm_morph_result* out)
 {
     if (!r || !d || !out) return fail(TBRM_ERR_INVALID_ARG, "null argument");
-    if (r->resident) return fail(TBRM_ERR_UNSUPPORTED, "slab-resident handle: it holds only some layers of the volume");
+    if (int e = refuse_resident(r)) return e;
     if (d->op < TBRM_MORPH_DILATE || d->op > TBRM_MORPH_CLOSE) return fail(TBRM_ERR_INVALID_ARG, "op %d: must be TBRM_MORPH_DILATE .. TBRM_MORPH_CLOSE", (int) d->op);
     if (d->radius < 1 || d->radius > TBRM_MORPH_MAX_RADIUS) return fail(TBRM_ERR_INVALID_ARG, "radius %d: must be 1 .. %d", (int) d->radius, TBRM_MORPH_MAX_RADIUS);
     if (d->connectivity != 6 && d->connectivity != 26) return fail(TBRM_ERR_INVALID_ARG, "connectivity %d: must be 6 or 26", (int) d->connectivity);
@@ -40,28 +40,20 @@ int tbrm_morph_labels(tbrm_resources* r, const tbrm_morph_desc* d, tbrm_morph_re
     if (d->erase_label < 0 || d->erase_label > 255) return fail(TBRM_ERR_INVALID_ARG, "erase_label %d: must be 0 .. 255", (int) d->erase_label);
     if (d->reserved != 0) return fail(TBRM_ERR_INVALID_ARG, "reserved = %d: must be 0", (int) d->reserved);
     const tbrm_resources::Dims dims = r->data_dims();
-    const bool whole = d->extent[0] == 0 && d->extent[1] == 0 && d->extent[2] == 0;
     MorphParams p{};
-    for (int c = 0; c < 3; ++c) {
-        const int o = whole ? 0 : d->origin[c], e = whole ? dims[c] : d->extent[c];
-        if (e <= 0) return fail(TBRM_ERR_INVALID_ARG, "box extent %d along axis %d: must be > 0 (or all three 0: the whole volume)", e, c);
-        if (o < 0 || e > dims[c] - o) return fail(TBRM_ERR_INVALID_ARG, "box [%d, %d + %d) along axis %d leaves a volume %d wide", o, o, e, c, dims[c]);
-        p.dims[c] = dims[c];
-        p.origin[c] = o;
-        p.end[c] = o + e;
-    }
-    if (!r->has_volume) return fail(TBRM_ERR_NOT_INITIALIZED, "no volume: upload one with tbrm_upload_volume");
-    if (!r->d_labels) return fail(TBRM_ERR_NOT_INITIALIZED, "no label volume: tbrm_attach_empty_label_volume or tbrm_upload_label_volume");
+    const BoxVerdict v = box_resolve(dims, d->origin, d->extent, true, &p.box, nullptr);
+    if (v.what != BOX_OK) return fail_box(v, true, dims, d->origin, d->extent);
+    for (int c = 0; c < 3; ++c) p.dims[c] = dims[c];
+    if (int e = begin_label_edit(r, "no label volume")) return e;
     MorphPlan plan;
-    if (!morph_plan(p.dims, p.origin, p.end, d->op, d->radius, tune(TUNE_MORPH_STEPS), &plan)) return fail(TBRM_ERR_INVALID_ARG, "no step plan for these arguments");
-    if (int e = bind(r)) return e;
+    if (!morph_plan(p.dims, p.box.origin, p.box.end, d->op, d->radius, tune(TUNE_MORPH_STEPS), &plan)) return fail(TBRM_ERR_INVALID_ARG, "no step plan for these arguments");
     if (int e = ensure_grow_scratch(r)) return e;
 
     const GrowScratch g = grow_scratch(r);
     p.labels = r->d_labels;
     p.bnx = r->dbn[0];
     p.bnxy = r->dbn[0] * r->dbn[1];
-    for (int c = 0; c < 3; ++c) { p.b0[c] = plan.b0[c]; p.nb[c] = plan.nb[c]; p.wb0[c] = plan.wb0[c]; p.wnb[c] = plan.wnb[c]; }
+    for (int c = 0; c < 3; ++c) { p.range.b0[c] = plan.b0[c]; p.range.nb[c] = plan.nb[c]; p.wrange.b0[c] = plan.wb0[c]; p.wrange.nb[c] = plan.wnb[c]; }
     for (int w = 0; w < 8; ++w) { p.source[w] = d->source[w]; p.writable[w] = d->writable[w]; }
     p.bits = g.bits;
     p.cls[0] = g.act[0];
@@ -71,8 +63,8 @@ int tbrm_morph_labels(tbrm_resources* r, const tbrm_morph_desc* d, tbrm_morph_re
     p.erase_label = d->erase_label;
     p.ctl = g.ctl;
 
-    int32_t ctl[MORPH_CTL_WORDS] = {};
-    for (int c = 0; c < 3; ++c) { ctl[MORPH_MIN_X + c] = dims[c]; ctl[MORPH_MAX_X + c] = -1; }
+    int32_t ctl[MORPH_CTL_WORDS];
+    ctl_start(ctl, MORPH_CTL_WORDS, MORPH_MIN_X, dims);
     HIP_TRY(hipMemcpyAsync(g.ctl, ctl, sizeof(ctl), hipMemcpyHostToDevice, r->stream));
     HIP_TRY(launch_morph_load(p, r->stream));
     for (int i = 0; i < plan.launches; ++i) {
@@ -101,15 +93,7 @@ int tbrm_morph_labels(tbrm_resources* r, const tbrm_morph_desc* d, tbrm_morph_re
     r->morph_counters[2] += counts[MORPH_WINDOWS];
     r->morph_counters[3] += counts[MORPH_BRICKS_WRITTEN];
 
-    if (d->new_label >= 0 && out->bbox_max[0] >= 0) { // something joined or left: the bricks its bounding box touches
-        int wb0[3], wb1[3];
-        for (int c = 0; c < 3; ++c) {
-            wb0[c] = out->bbox_min[c] >> kBrickShift;
-            wb1[c] = (out->bbox_max[c] >> kBrickShift) + 1;
-        }
-        if (int e = brick_masks(r, wb0, wb1)) return e;
-        if (int e = refresh_live(r)) return e;
-    }
+    if (d->new_label >= 0) return labels_changed(r, out->bbox_min, out->bbox_max); // (nothing joined or left: nothing to do)
     return TBRM_OK;
 }
 

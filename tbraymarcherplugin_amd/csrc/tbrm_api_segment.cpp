@@ -3,7 +3,7 @@
 //
 // A call is: the candidate bits of the box's bricks (the only pass over voxels and labels), the seeds, propagation passes until a
 // pass changes no brick, the region's size and bounding box, and — a writing call — new_label into the bricks of that bounding box,
-// followed by what tbrm_update_label_region does after its write: the touched bricks' label sets (brick_masks) and refresh_live.
+// followed by what every label write ends with (labels_changed).
 // The passes are enqueued grow_batch at a time and their changed-bricks words read back together; passes behind the fixed point
 // find no brick due and do nothing, so the result does not depend on the batch. Nothing on the data side is touched, nothing waits
 // for the occlusion stream (it reads neither the label volume nor the scratch).
@@ -28,16 +28,14 @@ namespace tbrm_host {
 GrowScratch grow_scratch(const tbrm_resources* r)
 {
     const size_t nb = grow_bricks(r);
-    const auto up = [](size_t n) { return (n + 255) / 256 * 256; };
-    size_t off = 0;
+    Carver c{r->d_grow};
     GrowScratch g{};
-    char* const base = r->d_grow;
-    g.bits = (uint64_t*) (base + off); off += up(nb * 16 * sizeof(uint64_t));
-    g.act[0] = (uint32_t*) (base + off); off += up(nb * sizeof(uint32_t));
-    g.act[1] = (uint32_t*) (base + off); off += up(nb * sizeof(uint32_t));
-    g.seeds = (int32_t*) (base + off); off += up((size_t) kGrowMaxSeeds * 3 * sizeof(int32_t));
-    g.ctl = (int32_t*) (base + off); off += up((size_t) GROW_CTL_WORDS * sizeof(int32_t));
-    g.bytes = off;
+    g.bits = c.take<uint64_t>(nb * 16);
+    g.act[0] = c.take<uint32_t>(nb);
+    g.act[1] = c.take<uint32_t>(nb);
+    g.seeds = c.take<int32_t>((size_t) kGrowMaxSeeds * 3);
+    g.ctl = c.take<int32_t>(GROW_CTL_WORDS);
+    g.bytes = c.off;
     return g;
 }
 
@@ -116,7 +114,7 @@ int tbrm_attach_empty_label_volume(tbrm_resources* r)
 int tbrm_grow_region(tbrm_resources* r, const tbrm_grow_desc* d, const int32_t* seeds_xyz, int32_t n_seeds, tbrm_grow_result* out)
 {
     if (!r || !d || !out || (n_seeds > 0 && !seeds_xyz)) return fail(TBRM_ERR_INVALID_ARG, "null argument");
-    if (r->resident) return fail(TBRM_ERR_UNSUPPORTED, "slab-resident handle: it holds only some layers of the volume");
+    if (int e = refuse_resident(r)) return e;
     if (d->connectivity != 6 && d->connectivity != 26) return fail(TBRM_ERR_INVALID_ARG, "connectivity %d: must be 6 or 26", (int) d->connectivity);
     if (d->new_label < -1 || d->new_label > 255) return fail(TBRM_ERR_INVALID_ARG, "new_label %d: must be 0 .. 255, or -1 to measure only", (int) d->new_label);
     if (n_seeds < 0 || n_seeds > TBRM_GROW_MAX_SEEDS) return fail(TBRM_ERR_INVALID_ARG, "n_seeds %d: must be 0 .. %d", (int) n_seeds, TBRM_GROW_MAX_SEEDS);
@@ -128,18 +126,10 @@ int tbrm_grow_region(tbrm_resources* r, const tbrm_grow_desc* d, const int32_t* 
                 return fail(TBRM_ERR_INVALID_ARG, "seed %d lies outside the volume: coordinate %d along axis %d of %d", (int) s, (int) seeds_xyz[3 * s + c], c, dims[c]);
 
     GrowParams p{};
-    const bool whole = d->extent[0] == 0 && d->extent[1] == 0 && d->extent[2] == 0;
+    const BoxVerdict v = box_resolve(dims, d->origin, d->extent, true, &p.box, &p.range);
+    if (v.what != BOX_OK) return fail_box(v, true, dims, d->origin, d->extent);
     uint64_t box_voxels = 1;
-    for (int c = 0; c < 3; ++c) {
-        const int o = whole ? 0 : d->origin[c], e = whole ? dims[c] : d->extent[c];
-        if (e <= 0) return fail(TBRM_ERR_INVALID_ARG, "box extent %d along axis %d: must be > 0 (or all three 0: the whole volume)", e, c);
-        if (o < 0 || e > dims[c] - o) return fail(TBRM_ERR_INVALID_ARG, "box [%d, %d + %d) along axis %d leaves a volume %d wide", o, o, e, c, dims[c]);
-        p.origin[c] = o;
-        p.end[c] = o + e;
-        p.b0[c] = o >> kBrickShift;
-        p.nb[c] = ((o + e - 1) >> kBrickShift) - p.b0[c] + 1;
-        box_voxels *= (uint64_t) e;
-    }
+    for (int c = 0; c < 3; ++c) box_voxels *= (uint64_t) (p.box.end[c] - p.box.origin[c]);
     const bool is_float = r->desc.data_format == TBRM_FMT_R32_FLOAT;
     const double top = r->desc.data_format == TBRM_FMT_G8 ? 255.0 : 65535.0;
     if (!(d->lo <= d->hi)) return fail(TBRM_ERR_INVALID_ARG, "range [%g, %g]: needs lo <= hi", d->lo, d->hi);
@@ -151,11 +141,8 @@ int tbrm_grow_region(tbrm_resources* r, const tbrm_grow_desc* d, const int32_t* 
         if (!(d->lo >= least && d->hi <= top) || d->lo != std::floor(d->lo) || d->hi != std::floor(d->hi))
             return fail(TBRM_ERR_INVALID_ARG, "range [%g, %g]: needs integral codes with %g <= lo <= hi <= %g", d->lo, d->hi, least, top);
     }
-    if (!r->has_volume) return fail(TBRM_ERR_NOT_INITIALIZED, "no volume: upload one with tbrm_upload_volume");
     const bool writes = d->new_label >= 0;
-    if (writes && !r->d_labels)
-        return fail(TBRM_ERR_NOT_INITIALIZED, "no label volume to write to: tbrm_attach_empty_label_volume or tbrm_upload_label_volume");
-    if (int e = bind(r)) return e;
+    if (int e = begin_label_edit(r, writes ? "no label volume to write to" : nullptr)) return e;
     if (int e = ensure_grow_scratch(r)) return e;
 
     // the range in use
@@ -197,8 +184,8 @@ int tbrm_grow_region(tbrm_resources* r, const tbrm_grow_desc* d, const int32_t* 
     p.new_label = d->new_label;
     p.ctl = g.ctl;
 
-    int32_t ctl[GROW_CTL_WORDS] = {};
-    for (int c = 0; c < 3; ++c) { ctl[GROW_MIN_X + c] = dims[c]; ctl[GROW_MAX_X + c] = -1; }
+    int32_t ctl[GROW_CTL_WORDS];
+    ctl_start(ctl, GROW_CTL_WORDS, GROW_MIN_X, dims);
     HIP_TRY(hipMemcpyAsync(g.ctl, ctl, sizeof(ctl), hipMemcpyHostToDevice, r->stream));
     if (n_seeds > 0) HIP_TRY(hipMemcpyAsync(g.seeds, seeds_xyz, (size_t) n_seeds * 3 * sizeof(int32_t), hipMemcpyHostToDevice, r->stream));
     HIP_TRY(launch_grow_candidates(p, r->stream));
@@ -247,16 +234,13 @@ int tbrm_grow_region(tbrm_resources* r, const tbrm_grow_desc* d, const int32_t* 
     r->grow_counters[2] += visits;
 
     if (writes && out->voxels > 0) {
-        int wb0[3], wb1[3], wnb[3]; // the bricks the bounding box touches
-        for (int c = 0; c < 3; ++c) {
-            wb0[c] = out->bbox_min[c] >> kBrickShift;
-            wb1[c] = (out->bbox_max[c] >> kBrickShift) + 1;
-            wnb[c] = wb1[c] - wb0[c];
-        }
-        HIP_TRY(launch_grow_write(p, wb0, wnb, r->stream));
+        BrickRange w; // the bricks the bounding box touches
+        int wb1[3];
+        bbox_bricks(out->bbox_min, out->bbox_max, w.b0, wb1);
+        for (int c = 0; c < 3; ++c) w.nb[c] = wb1[c] - w.b0[c];
+        HIP_TRY(launch_grow_write(p, w, r->stream));
         HIP_TRY(hipMemcpyAsync(ctl, g.ctl, GROW_CHANGED * sizeof(int32_t), hipMemcpyDeviceToHost, r->stream));
-        if (int e = brick_masks(r, wb0, wb1)) return e;
-        if (int e = refresh_live(r)) return e; // (waits for the stream: ctl has arrived)
+        if (int e = labels_changed(r, out->bbox_min, out->bbox_max)) return e; // (refresh_live waits for the stream: ctl has arrived)
         out->relabelled = (uint32_t) ctl[GROW_RELABELLED];
         r->grow_counters[3] += (uint32_t) ctl[GROW_BRICKS_WRITTEN];
     }

@@ -21,20 +21,15 @@ namespace {
 int region_args(const tbrm_resources* r, const int32_t origin[3], const int32_t extent[3], const void* voxels, size_t n_bytes, size_t* n_voxels)
 {
     if (!origin || !extent || !voxels) return fail(TBRM_ERR_INVALID_ARG, "null argument");
-    for (int c = 0; c < 3; ++c) {
-        if (extent[c] <= 0) return fail(TBRM_ERR_INVALID_ARG, "region extent %d along axis %d: must be > 0", extent[c], c);
-        if (origin[c] < 0) return fail(TBRM_ERR_INVALID_ARG, "region origin %d along axis %d: the box leaves the volume", origin[c], c);
-    }
+    BoxVerdict v = box_resolve(nullptr, origin, extent, false, nullptr, nullptr); // (what no volume can hold)
+    if (v.what != BOX_OK) return fail_box(v, false, nullptr, origin, extent);
     if (!r) return fail(TBRM_ERR_INVALID_ARG, "null argument");
     if (r->resident) return fail(TBRM_ERR_UNSUPPORTED, "slab-resident handle: its layers are uploaded with tbrm_upload_volume_slices");
     if (!r->has_volume) return fail(TBRM_ERR_NOT_INITIALIZED, "no volume: upload one with tbrm_upload_volume");
     const tbrm_resources::Dims dims = r->data_dims();
-    size_t n = 1;
-    for (int c = 0; c < 3; ++c) {
-        if (extent[c] > dims[c] - origin[c])
-            return fail(TBRM_ERR_INVALID_ARG, "region [%d, %d + %d) along axis %d leaves a volume %d wide", origin[c], origin[c], extent[c], c, dims[c]);
-        n *= (size_t) extent[c];
-    }
+    v = box_resolve(dims, origin, extent, false, nullptr, nullptr);
+    if (v.what != BOX_OK) return fail_box(v, false, dims, origin, extent);
+    const size_t n = (size_t) extent[0] * (size_t) extent[1] * (size_t) extent[2];
     const size_t want = n * format_bytes(r->desc.data_format);
     if (n_bytes != want) return fail(TBRM_ERR_INVALID_ARG, "region is %zu bytes, expected %zu", n_bytes, want);
     *n_voxels = n;

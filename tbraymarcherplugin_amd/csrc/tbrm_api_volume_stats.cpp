@@ -24,7 +24,7 @@ constexpr size_t kScratchWords = kLabelOffsetWords + kStatsLabelWords;
 // what every statistics call checks about the handle
 int stats_handle(const tbrm_resources* r)
 {
-    if (r->resident) return fail(TBRM_ERR_UNSUPPORTED, "slab-resident handle: it holds only some layers of the volume");
+    if (int e = refuse_resident(r)) return e;
     if (!r->has_volume) return fail(TBRM_ERR_NOT_INITIALIZED, "no volume: upload one with tbrm_upload_volume");
     return TBRM_OK;
 }
@@ -33,16 +33,8 @@ int stats_handle(const tbrm_resources* r)
 int stats_box(const tbrm_resources* r, const int32_t* origin, const int32_t* extent, StatsParams& p)
 {
     const tbrm_resources::Dims dims = r->data_dims();
-    const bool whole = !extent || (extent[0] == 0 && extent[1] == 0 && extent[2] == 0);
-    for (int c = 0; c < 3; ++c) {
-        const int o = whole ? 0 : origin[c], e = whole ? dims[c] : extent[c];
-        if (e <= 0) return fail(TBRM_ERR_INVALID_ARG, "box extent %d along axis %d: must be > 0 (or all three 0: the whole volume)", e, c);
-        if (o < 0 || e > dims[c] - o) return fail(TBRM_ERR_INVALID_ARG, "box [%d, %d + %d) along axis %d leaves a volume %d wide", o, o, e, c, dims[c]);
-        p.origin[c] = o;
-        p.end[c] = o + e;
-        p.b0[c] = o >> kBrickShift;
-        p.nb[c] = ((o + e - 1) >> kBrickShift) - p.b0[c] + 1;
-    }
+    const BoxVerdict v = box_resolve(dims, origin, extent, true, &p.box, &p.range);
+    if (v.what != BOX_OK) return fail_box(v, true, dims, origin, extent);
     p.data = r->d_data;
     p.fmt = r->desc.data_format == TBRM_FMT_G8 ? FMT_U8 : (r->desc.data_format == TBRM_FMT_G16 ? FMT_U16 : FMT_F32);
     p.bnx = r->dbn[0];
@@ -87,7 +79,7 @@ int histogram_params(const tbrm_resources* r, const tbrm_histogram_desc* d, Stat
 // then takes many bricks of a small volume).
 int stats_grid(const tbrm_resources* r, const StatsParams& p, int per_cu)
 {
-    const uint64_t bricks = (uint64_t) p.nb[0] * p.nb[1] * p.nb[2];
+    const uint64_t bricks = range_bricks(p.range);
     uint64_t groups = (uint64_t) std::max(r->n_cus, 1) * (uint64_t) per_cu;
     if (tune(TUNE_STATS_GROUPS) > 0) groups = std::min<uint64_t>(groups, (uint64_t) tune(TUNE_STATS_GROUPS));
     return (int) std::min<uint64_t>((bricks + 3) / 4, groups);
@@ -97,9 +89,9 @@ void count_bricks(tbrm_resources* r, const StatsParams& p)
 {
     uint64_t whole = 1, all = 1;
     for (int c = 0; c < 3; ++c) { // along an axis the whole bricks are those with [8b, 8b + 8) inside [origin, end)
-        const int first = (p.origin[c] + kBrick - 1) >> kBrickShift, last = p.end[c] >> kBrickShift; // [first, last)
+        const int first = (p.box.origin[c] + kBrick - 1) >> kBrickShift, last = p.box.end[c] >> kBrickShift; // [first, last)
         whole *= (uint64_t) std::max(last - first, 0);
-        all *= (uint64_t) p.nb[c];
+        all *= (uint64_t) p.range.nb[c];
     }
     r->stats_counters[2] += whole;
     r->stats_counters[3] += all - whole;

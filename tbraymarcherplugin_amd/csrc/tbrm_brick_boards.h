@@ -1,0 +1,180 @@
+// tbrm_brick_boards.h — the index rules that the brick-per-wave kernels of the statistics, region growing, label morphology and label
+// islands share, stated once. A board is the 512 voxels of an 8^3 brick as 8 uint64 slice words: word k is the slice
+// z = k, bit y * 8 + x; on this little-endian target byte i of a board's 64 bytes is the x row (y, z) = (i & 7, i >> 3), the row
+// that lane i of a brick's wave holds, and that row's 8 label bytes are one uint2.
+//
+// Everything above the device-only part is integer arithmetic that also compiles as plain host C++:
+// tests/cpp/brick_boards_test.cpp checks it voxel by voxel under the sanitizers.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define TBRM_BOARDS_HD __host__ __device__ __forceinline__
+#define TBRM_BOARDS_UNROLL _Pragma("unroll")
+#else
+#define TBRM_BOARDS_HD inline
+#define TBRM_BOARDS_UNROLL
+#endif
+
+namespace tbrm {
+
+constexpr int kBrick = 8;      // empty-space-skipping brick edge in voxels
+constexpr int kBrickShift = 3;
+
+struct BrickRange { int b0[3], nb[3]; };      // the bricks nb[c] from b0[c] on, on the volume's brick grid; position k runs x fastest
+struct VoxelBox { int origin[3], end[3]; };   // the voxels [origin, end)
+
+// ---- brick ranges and the brick grid -----------------------------------------------------------------------------------------------
+TBRM_BOARDS_HD uint64_t range_bricks(const BrickRange& r) { return (uint64_t) r.nb[0] * (uint64_t) r.nb[1] * (uint64_t) r.nb[2]; }
+
+// position k of the range -> brick coordinates
+TBRM_BOARDS_HD void range_brick(const BrickRange& r, uint32_t k, int& bx, int& by, int& bz)
+{
+    const uint32_t ix = k % (uint32_t) r.nb[0], q = k / (uint32_t) r.nb[0];
+    bx = r.b0[0] + (int) ix;
+    by = r.b0[1] + (int) (q % (uint32_t) r.nb[1]);
+    bz = r.b0[2] + (int) (q / (uint32_t) r.nb[1]);
+}
+
+TBRM_BOARDS_HD bool range_holds(const BrickRange& r, int bx, int by, int bz)
+{
+    return bx >= r.b0[0] && bx < r.b0[0] + r.nb[0] && by >= r.b0[1] && by < r.b0[1] + r.nb[1] && bz >= r.b0[2] && bz < r.b0[2] + r.nb[2];
+}
+
+// brick coordinates -> position in the range (which holds the brick)
+TBRM_BOARDS_HD uint32_t range_position(const BrickRange& r, int bx, int by, int bz)
+{
+    return ((uint32_t) (bz - r.b0[2]) * (uint32_t) r.nb[1] + (uint32_t) (by - r.b0[1])) * (uint32_t) r.nb[0] + (uint32_t) (bx - r.b0[0]);
+}
+
+// brick coordinates -> index on the volume's brick grid (bnx bricks along x, bnxy to a z layer)
+TBRM_BOARDS_HD size_t grid_index(int bnx, int bnxy, int bx, int by, int bz)
+{
+    return (size_t) bz * (size_t) bnxy + (size_t) by * (size_t) bnx + (size_t) bx;
+}
+
+// ---- row and slice masks -----------------------------------------------------------------------------------------------------------
+// The x row of brick column bx at the voxel coordinates (y, z): bit i is the voxel x = bx * 8 + i.
+TBRM_BOARDS_HD uint32_t row_bits(int lo, int hi) // the bits [lo, hi) of a row, clipped to it
+{
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > kBrick ? kBrick : hi;
+    if (hi <= lo) return 0u;
+    return (0xffu >> (kBrick - hi)) & (0xffu << lo) & 0xffu;
+}
+
+// the bits of the row that lie inside the box; 0 for a row the box does not touch
+TBRM_BOARDS_HD uint32_t row_in_box(const VoxelBox& b, int bx, int y, int z)
+{
+    if (y < b.origin[1] || y >= b.end[1] || z < b.origin[2] || z >= b.end[2]) return 0u;
+    return row_bits(b.origin[0] - bx * kBrick, b.end[0] - bx * kBrick);
+}
+
+// the bits of the row that lie inside the volume (bx, y, z >= 0)
+TBRM_BOARDS_HD uint32_t row_in_volume(const int dims[3], int bx, int y, int z)
+{
+    if (y >= dims[1] || z >= dims[2]) return 0u;
+    return row_bits(0, dims[0] - bx * kBrick);
+}
+
+// the bits of the slice z of the brick column (bx, by) that lie inside the volume
+TBRM_BOARDS_HD uint64_t slice_in_volume(const int dims[3], int bx, int by, int z)
+{
+    if (z >= dims[2]) return 0ull;
+    const uint64_t xs = (uint64_t) row_bits(0, dims[0] - bx * kBrick) * 0x0101010101010101ull;
+    const int rows = dims[1] - by * kBrick;
+    return rows >= kBrick ? xs : (rows <= 0 ? 0ull : xs & ((1ull << (8 * rows)) - 1ull));
+}
+
+// ---- the 8 bytes of a row (Row8: uint2, or anything with 32-bit x and y) -------------------------------------------------------------
+template <class Row8> TBRM_BOARDS_HD uint32_t byte_of(const Row8& v, int i) { return ((i < 4 ? v.x : v.y) >> (8 * (i & 3))) & 255u; }
+
+template <class Row8> TBRM_BOARDS_HD void set_byte(Row8& v, int i, uint32_t to)
+{
+    const int sh = 8 * (i & 3);
+    if (i < 4) v.x = (v.x & ~(255u << sh)) | (to << sh);
+    else v.y = (v.y & ~(255u << sh)) | (to << sh);
+}
+
+// bit i: label byte i of the row has its bit in the 256-bit mask
+template <class Row8> TBRM_BOARDS_HD uint32_t row_in_mask(const Row8& l, const uint32_t* mask)
+{
+    uint32_t m = 0u;
+    TBRM_BOARDS_UNROLL
+    for (int i = 0; i < 8; ++i) {
+        const uint32_t L = byte_of(l, i);
+        m |= ((mask[L >> 5] >> (L & 31)) & 1u) << i;
+    }
+    return m;
+}
+
+// ---- the in-slice part of a dilation -------------------------------------------------------------------------------------------------
+constexpr uint64_t kSliceX0 = 0x0101010101010101ull, kSliceX7 = 0x8080808080808080ull; // a slice's columns x = 0 and x = 7
+
+// what a slice word reaches inside its own slice: 6: the word and its four shifts; 26: the 3 x 3 neighbourhood of every bit
+template <int CONN26> TBRM_BOARDS_HD uint64_t slice_spread(uint64_t w)
+{
+    const uint64_t x3 = w | ((w << 1) & ~kSliceX0) | ((w >> 1) & ~kSliceX7);
+    if constexpr (!CONN26) return x3 | (w << 8) | (w >> 8);
+    else return x3 | (x3 << 8) | (x3 >> 8);
+}
+
+#if defined(__HIPCC__)
+// ---- device only: reductions over the wave -------------------------------------------------------------------------------------------
+template <typename T> __device__ __forceinline__ T wave_sum(T v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// The bounding box of the voxels a wave moved. A lane takes its bits, the wave reduces, lane 0 commits to the call's six
+// consecutive control words MIN_X, MIN_Y, MIN_Z, MAX_X, MAX_Y, MAX_Z (which start as the volume's dims and -1).
+struct WaveBounds {
+    int mn[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, mx[3] = {-1, -1, -1};
+
+    // the bits of the x row (y, z) of brick column bx
+    __device__ __forceinline__ void take_row(uint32_t bits, int bx, int y, int z)
+    {
+        if (!bits) return;
+        mn[0] = bx * kBrick + (__ffs((int) bits) - 1);
+        mx[0] = bx * kBrick + (31 - __clz((int) bits));
+        mn[1] = mx[1] = y;
+        mn[2] = mx[2] = z;
+    }
+    // the bits of the slice z of brick column (bx, by)
+    __device__ __forceinline__ void take_slice(uint64_t w, int bx, int by, int z)
+    {
+        if (!w) return;
+        uint32_t cols = (uint32_t) (w | (w >> 32)); // the OR of the eight rows
+        cols |= cols >> 16;
+        take_row((cols | (cols >> 8)) & 0xffu, bx, 0, z);
+        mn[1] = by * kBrick + ((__ffsll((long long) w) - 1) >> 3);
+        mx[1] = by * kBrick + ((63 - __clzll((long long) w)) >> 3);
+    }
+    __device__ __forceinline__ void reduce()
+    {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                mn[c] = min(mn[c], __shfl_xor(mn[c], o, 64));
+                mx[c] = max(mx[c], __shfl_xor(mx[c], o, 64));
+            }
+    }
+    // after reduce(): lane 0 commits, when the wave took a bit at all
+    __device__ __forceinline__ void commit(int32_t* min_x, int lane) const
+    {
+        if (lane != 0 || mx[0] < 0) return;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            atomicMin(min_x + c, mn[c]);
+            atomicMax(min_x + 3 + c, mx[c]);
+        }
+    }
+};
+#endif
+
+} // namespace tbrm

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tbrm_brick_boards.h"
+
 namespace tbrm {
 
 enum : int { FMT_U8 = 0, FMT_U16 = 1, FMT_F32 = 2 };
@@ -17,9 +19,6 @@ enum : int { ADDR_WRAP = 0, ADDR_CLAMP = 1, ADDR_BORDER = 2 };
 // PASS_PLANES is a sweep mode only: one stream propagated, the light volume untouched — what the launch leaves behind is its
 // hand-off records (SweepParams::r_from_records of the launch after it).
 enum : int { PASS_ADD = 0, PASS_CHANGE = 1, PASS_ADD2 = 2, PASS_CHANGE_ONE = 3, PASS_PLANES = 5 };
-
-constexpr int kBrick = 8;      // empty-space-skipping brick edge in voxels
-constexpr int kBrickShift = 3;
 
 struct VolumeDev {
     const void* data; // bricked layout (tbrm_device_sampling.h)
@@ -522,8 +521,8 @@ struct StatsParams {
     const uint8_t* labels; // bricked label volume on the same grid (null: none)
     int fmt;
     int bnx, bnxy;
-    int origin[3], end[3]; // the box [origin, end), inside the volume
-    int b0[3], nb[3];      // the bricks it touches: nb[c] from b0[c] on
+    VoxelBox box;          // inside the volume
+    BrickRange range;      // the bricks it touches
     // histogram: the binning rule of tbrm_volume_stats.h
     uint32_t n_bins;
     uint32_t lo_code, hi_code;
@@ -546,13 +545,14 @@ enum GrowCtl : int {
     GROW_CHANGED = 16,        // kGrowMaxBatch words: bricks that changed in pass i of the batch
     GROW_CTL_WORDS = GROW_CHANGED + kGrowMaxBatch
 };
+static_assert(GROW_MAX_Z == GROW_MIN_X + 5, "WaveBounds commits to six consecutive words");
 struct GrowParams {
     const void* data;      // bricked data volume
     uint8_t* labels;       // bricked label volume on the same grid (null: none, every voxel has label 0)
     int fmt;
     int bnx, bnxy;
-    int origin[3], end[3]; // the box [origin, end), inside the volume
-    int b0[3], nb[3];      // the bricks it touches: nb[c] from b0[c] on — the only bricks whose scratch a call reads or writes
+    VoxelBox box;          // inside the volume
+    BrickRange range;      // the bricks it touches — the only bricks whose scratch a call reads or writes
     uint32_t lo_code, hi_code; // UNORM: lo_code <= code <= hi_code (lo_code > hi_code: no candidate)
     float lo_f, hi_f;          // R32_FLOAT: lo_f <= v <= hi_f (NaN voxels fail both)
     uint32_t writable[8];
@@ -571,7 +571,7 @@ hipError_t launch_grow_candidates(const GrowParams& p, hipStream_t s);
 hipError_t launch_grow_seeds(const GrowParams& p, hipStream_t s);
 hipError_t launch_grow_pass(const GrowParams& p, hipStream_t s);
 hipError_t launch_grow_measure(const GrowParams& p, hipStream_t s);
-hipError_t launch_grow_write(const GrowParams& p, const int wb0[3], const int wnb[3], hipStream_t s); // the bricks wnb from wb0 on
+hipError_t launch_grow_write(const GrowParams& p, const BrickRange& w, hipStream_t s); // into the bricks w
 
 // label morphology (tbrm_api_morph.cpp, tbrm_morph_kernels.hip; include/tbrm_morphology.h). It works in the scratch of region growing:
 // the 16 words of a brick are two boards of 8 slice words (bit y * 8 + x of word z), the two activity words are the boards' classes.
@@ -581,14 +581,15 @@ enum MorphCtl : int {
     MORPH_SOURCE, MORPH_RESULT, MORPH_ADDED, MORPH_REMOVED, MORPH_RELABELLED, MORPH_WINDOWS, MORPH_BRICKS_WRITTEN, MORPH_CTL_COUNTS, // uint64 each
     MORPH_MIN_X = 2 * MORPH_CTL_COUNTS, MORPH_MIN_Y, MORPH_MIN_Z, MORPH_MAX_X, MORPH_MAX_Y, MORPH_MAX_Z, MORPH_CTL_WORDS             // int32 each
 };
+static_assert(MORPH_MAX_Z == MORPH_MIN_X + 5, "WaveBounds commits to six consecutive words");
 static_assert((int) MORPH_CTL_WORDS <= (int) GROW_CTL_WORDS, "the morphology control words live in the region growing scratch");
 struct MorphParams {
     uint8_t* labels;       // bricked label volume
     int bnx, bnxy;
     int dims[3];           // the volume in voxels: bits outside it are never set
-    int origin[3], end[3]; // the box [origin, end) that may change
-    int b0[3], nb[3];      // the bricks of the box grown by the operator's reach: the only bricks whose scratch a call reads or writes
-    int wb0[3], wnb[3];    // the bricks of the box
+    VoxelBox box;          // what may change
+    BrickRange range;      // the bricks of the box grown by the operator's reach: the only bricks whose scratch a call reads or writes
+    BrickRange wrange;     // the bricks of the box
     uint32_t source[8], writable[8];
     uint64_t* bits;        // per brick (global brick index) 16 words: board 0, board 1
     uint32_t* cls[2];      // per brick: the class of board 0 / 1

@@ -15,6 +15,7 @@ enum IslandsCtl : int {
     ISL_ROOTS, ISL_SPARED, ISL_LARGEST,
     ISL_MIN_X, ISL_MIN_Y, ISL_MIN_Z, ISL_MAX_X, ISL_MAX_Y, ISL_MAX_Z, ISL_CTL_WORDS // int32 each
 };
+static_assert(ISL_MAX_Z == ISL_MIN_X + 5, "WaveBounds commits to six consecutive words");
 
 struct IslandsEntry { // an island of the table as the device leaves it; the host turns it into a tbrm_island
     uint32_t voxels, first;
@@ -27,8 +28,8 @@ struct IslandsParams {
     uint8_t* labels;       // bricked label volume
     int bnx, bnxy;
     int dims[3];           // the volume in voxels
-    int origin[3], end[3]; // the box [origin, end)
-    int b0[3], nb[3];      // the bricks of the box; a brick's scratch is indexed by its position k in this range, x fastest
+    VoxelBox box;
+    BrickRange range;      // the bricks of the box; a brick's scratch is indexed by its position k in this range
     uint32_t nbox;         // nb[0] * nb[1] * nb[2]
     uint32_t source[8];
     int conn26, spare, write;

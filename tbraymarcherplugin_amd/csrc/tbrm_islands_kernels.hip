@@ -12,8 +12,7 @@
 //   k_islands_rule        a thread per island: the rule (tbrm_islands_rule.h), the counts, the table
 //   k_islands_write       a wave per set brick: voxel -> local id -> slot -> root -> label; rows stored where a byte changes
 //
-// The boards are those of region growing (tbrm_segment_kernels.hip): a brick's 512 voxels are 8 uint64 words, word k is z slice k,
-// bit y * 8 + x. The union-find forest keeps parent[s] <= s; during the merge its words are shared between workgroups of one launch
+// The boards and their index rules are tbrm_brick_boards.h's. The union-find forest keeps parent[s] <= s; during the merge its words are shared between workgroups of one launch
 // and are read and written with relaxed agent-scope atomics only, no workgroup waits for another, and every loop over it carries a
 // hard bound. Which slot becomes a root depends on timing; nothing that leaves these kernels does: the order, the labels and the
 // table come from sizes and first voxels alone.
@@ -32,43 +31,6 @@ namespace {
 constexpr int kWaveThreads = 256; // four bricks to a workgroup, a wave each
 constexpr int kWaves = kWaveThreads / 64;
 constexpr int kSlotThreads = 256; // the per-slot kernels
-constexpr uint64_t kNotX0 = ~0x0101010101010101ull, kNotX7 = ~0x8080808080808080ull; // a slice without its column x = 0 / x = 7
-
-__device__ __forceinline__ void box_brick(const IslandsParams& p, uint32_t k, int& bx, int& by, int& bz)
-{
-    const uint32_t ix = k % (uint32_t) p.nb[0], r = k / (uint32_t) p.nb[0];
-    bx = p.b0[0] + (int) ix;
-    by = p.b0[1] + (int) (r % (uint32_t) p.nb[1]);
-    bz = p.b0[2] + (int) (r / (uint32_t) p.nb[1]);
-}
-
-__device__ __forceinline__ size_t volume_brick(const IslandsParams& p, int bx, int by, int bz)
-{
-    return (size_t) bz * (size_t) p.bnxy + (size_t) by * (size_t) p.bnx + (size_t) bx;
-}
-
-// the bits of the x row (y, z) of the brick (bx, by, bz) that lie inside the box (which lies inside the volume)
-__device__ __forceinline__ uint32_t box_row(const IslandsParams& p, int bx, int y, int z)
-{
-    if (y < p.origin[1] || y >= p.end[1] || z < p.origin[2] || z >= p.end[2]) return 0u;
-    const int lo = max(p.origin[0] - bx * kBrick, 0), hi = min(p.end[0] - bx * kBrick, kBrick);
-    if (hi <= lo) return 0u;
-    return (0xffu >> (kBrick - hi)) & (0xffu << lo) & 0xffu;
-}
-
-// bit i: label byte i of the row has its bit in the mask
-__device__ __forceinline__ uint32_t row_in_mask(const uint2 l, const uint32_t* mask)
-{
-    uint32_t m = 0u;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const uint32_t L = ((i < 4 ? l.x : l.y) >> (8 * (i & 3))) & 255u;
-        m |= ((mask[L >> 5] >> (L & 31)) & 1u) << i;
-    }
-    return m;
-}
-
-__device__ __forceinline__ uint32_t byte_of(const uint2 v, int i) { return ((i < 4 ? v.x : v.y) >> (8 * (i & 3))) & 255u; }
 
 __device__ __forceinline__ uint64_t uniform64(uint64_t v)
 {
@@ -142,10 +104,10 @@ __global__ __launch_bounds__(kWaveThreads) void k_islands_local(const IslandsPar
     uint32_t set = 0u;
     if (valid) {
         int bx, by, bz;
-        box_brick(p, k, bx, by, bz);
-        const uint32_t box = box_row(p, bx, by * kBrick + (lane & 7), bz * kBrick + (lane >> 3));
+        range_brick(p.range, k, bx, by, bz);
+        const uint32_t box = row_in_box(p.box, bx, by * kBrick + (lane & 7), bz * kBrick + (lane >> 3)); // (the box lies inside the volume)
         if (box) {
-            const uint2 l = *reinterpret_cast<const uint2*>(p.labels + volume_brick(p, bx, by, bz) * 512 + (size_t) lane * 8);
+            const uint2 l = *reinterpret_cast<const uint2*>(p.labels + grid_index(p.bnx, p.bnxy, bx, by, bz) * 512 + (size_t) lane * 8);
             set = row_in_mask(l, s_source) & box;
         }
     }
@@ -179,14 +141,8 @@ __global__ __launch_bounds__(kWaveThreads) void k_islands_local(const IslandsPar
                 for (int s = 0; s < 8; ++s) {
                     const uint64_t below = s > 0 ? m[s - 1] : 0ull, above = s < 7 ? m[s + 1] : 0ull;
                     uint64_t n;
-                    if constexpr (CONN26) {
-                        uint64_t t = m[s] | below | above;
-                        t |= ((t << 1) & kNotX0) | ((t >> 1) & kNotX7);
-                        n = t | (t << 8) | (t >> 8);
-                    } else {
-                        const uint64_t w = m[s];
-                        n = w | ((w << 1) & kNotX0) | ((w >> 1) & kNotX7) | (w << 8) | (w >> 8) | below | above;
-                    }
+                    if constexpr (CONN26) n = slice_spread<1>(m[s] | below | above);
+                    else n = slice_spread<0>(m[s]) | below | above;
                     n &= S[s];
                     changed = changed || n != m[s];
                     m[s] = n;
@@ -303,12 +259,12 @@ __global__ __launch_bounds__(kWaveThreads) void k_islands_slots(const IslandsPar
     __syncthreads();
     if (count) {
         int bx, by, bz;
-        box_brick(p, k, bx, by, bz);
+        range_brick(p.range, k, bx, by, bz);
         const uint32_t set = reinterpret_cast<const uint8_t*>(p.boards + (size_t) k * 8)[lane];
         if (set) {
             const uint2 ids = *reinterpret_cast<const uint2*>(p.lid + (size_t) k * 512 + (size_t) lane * 8);
             const int y = by * kBrick + (lane & 7), z = bz * kBrick + (lane >> 3);
-            const bool face_yz = y == p.origin[1] || y == p.end[1] - 1 || z == p.origin[2] || z == p.end[2] - 1;
+            const bool face_yz = y == p.box.origin[1] || y == p.box.end[1] - 1 || z == p.box.origin[2] || z == p.box.end[2] - 1;
             const uint32_t row = (uint32_t) (((uint64_t) z * (uint64_t) p.dims[1] + (uint64_t) y) * (uint64_t) p.dims[0]); // (the volume has fewer than 2^32 voxels)
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
@@ -317,7 +273,7 @@ __global__ __launch_bounds__(kWaveThreads) void k_islands_slots(const IslandsPar
                 const int x = bx * kBrick + i;
                 atomicAdd(&s_size[wave][c], 1u);
                 atomicMin(&s_first[wave][c], row + (uint32_t) x);
-                if (face_yz || x == p.origin[0] || x == p.end[0] - 1) atomicOr(&s_border[wave][c], 1u);
+                if (face_yz || x == p.box.origin[0] || x == p.box.end[0] - 1) atomicOr(&s_border[wave][c], 1u);
             }
         }
     }
@@ -358,7 +314,7 @@ __global__ __launch_bounds__(kWaveThreads) void k_islands_merge(const IslandsPar
     const uint32_t k = blockIdx.x * kWaves + (uint32_t) wave;
     const uint32_t count = k < p.nbox ? p.cnt[k] : 0u;
     int bx = 0, by = 0, bz = 0;
-    if (count) box_brick(p, k, bx, by, bz);
+    if (count) range_brick(p.range, k, bx, by, bz);
     if (lane < 18) {
         int32_t at = -1;
         uint32_t base = 0u;
@@ -366,9 +322,8 @@ __global__ __launch_bounds__(kWaveThreads) void k_islands_merge(const IslandsPar
         // 26: a half step can lead into every brick of this and the next brick layer but the brick itself; 6: into +x, +y, +z
         const bool needed = CONN26 ? lane != 4 : ((cx == 1 && cy == 0 && cz == 0) || (cx == 0 && cy == 1 && cz == 0) || (cx == 0 && cy == 0 && cz == 1));
         if (count && needed) {
-            const int ix = bx - p.b0[0] + cx, iy = by - p.b0[1] + cy, iz = bz - p.b0[2] + cz;
-            if (ix >= 0 && ix < p.nb[0] && iy >= 0 && iy < p.nb[1] && iz >= 0 && iz < p.nb[2]) {
-                const uint32_t kn = ((uint32_t) iz * (uint32_t) p.nb[1] + (uint32_t) iy) * (uint32_t) p.nb[0] + (uint32_t) ix;
+            if (range_holds(p.range, bx + cx, by + cy, bz + cz)) {
+                const uint32_t kn = range_position(p.range, bx + cx, by + cy, bz + cz);
                 if (p.cnt[kn]) {
                     at = (int32_t) kn;
                     base = slot_base(p, kn);
@@ -619,14 +574,14 @@ __global__ __launch_bounds__(kWaveThreads) void k_islands_write(const IslandsPar
     }
     __syncthreads();
     int changed = 0;
-    int mn[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, mx[3] = {-1, -1, -1};
+    WaveBounds bounds;
     if (count) {
         int bx, by, bz;
-        box_brick(p, k, bx, by, bz);
+        range_brick(p.range, k, bx, by, bz);
         const uint32_t set = reinterpret_cast<const uint8_t*>(p.boards + (size_t) k * 8)[lane];
         if (set) {
             const uint2 ids = *reinterpret_cast<const uint2*>(p.lid + (size_t) k * 512 + (size_t) lane * 8);
-            uint2* const bytes = reinterpret_cast<uint2*>(p.labels + volume_brick(p, bx, by, bz) * 512 + (size_t) lane * 8);
+            uint2* const bytes = reinterpret_cast<uint2*>(p.labels + grid_index(p.bnx, p.bnxy, bx, by, bz) * 512 + (size_t) lane * 8);
             const uint2 old = *bytes;
             uint2 l = old;
             uint32_t moved = 0u;
@@ -640,20 +595,13 @@ __global__ __launch_bounds__(kWaveThreads) void k_islands_write(const IslandsPar
                 }
                 const int to = s_act[wave][c];
                 if (p.write && to >= 0 && (uint32_t) to != was) {
-                    uint32_t& half = i < 4 ? l.x : l.y;
-                    const int sh = 8 * (i & 3);
-                    half = (half & ~(255u << sh)) | ((uint32_t) to << sh);
+                    set_byte(l, i, (uint32_t) to);
                     moved |= 1u << i;
                     ++changed;
                 }
             }
-            if (moved) {
-                *bytes = l;
-                mn[0] = bx * kBrick + (__ffs((int) moved) - 1);
-                mx[0] = bx * kBrick + (31 - __clz((int) moved));
-                mn[1] = mx[1] = by * kBrick + (lane & 7);
-                mn[2] = mx[2] = bz * kBrick + (lane >> 3);
-            }
+            if (moved) *bytes = l;
+            bounds.take_row(moved, bx, by * kBrick + (lane & 7), bz * kBrick + (lane >> 3));
         }
     }
     __syncthreads();
@@ -666,25 +614,14 @@ __global__ __launch_bounds__(kWaveThreads) void k_islands_write(const IslandsPar
             }
         }
     if (__ballot(changed != 0) == 0ull) return;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        changed += __shfl_xor(changed, o, 64);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            mn[c] = min(mn[c], __shfl_xor(mn[c], o, 64));
-            mx[c] = max(mx[c], __shfl_xor(mx[c], o, 64));
-        }
-    }
+    changed = wave_sum(changed);
+    bounds.reduce();
     if (lane == 0) {
         unsigned long long* const counts = reinterpret_cast<unsigned long long*>(p.ctl);
         atomicAdd(counts + ISL_RELABELLED, (unsigned long long) changed);
         atomicAdd(counts + ISL_BRICKS_WRITTEN, 1ull);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            atomicMin(p.ctl + ISL_MIN_X + c, mn[c]);
-            atomicMax(p.ctl + ISL_MAX_X + c, mx[c]);
-        }
     }
+    bounds.commit(p.ctl + ISL_MIN_X, lane);
 }
 
 hipError_t launch_islands_write(const IslandsParams& p, hipStream_t s)

@@ -4,6 +4,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "tbrm_box.h"
+
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define TBRM_ISLANDS_HD __host__ __device__
 #else
@@ -62,17 +64,12 @@ inline const char* islands_validate(const int dims[3], const int32_t origin[3], 
     if (spare_border != 0 && spare_border != 1) return "spare_border: must be 0 or 1";
     if (flags & ~kIslandsMeasure) return "flags: unknown bits";
     if (reserved != 0) return "reserved: must be 0";
-    const bool whole = extent[0] == 0 && extent[1] == 0 && extent[2] == 0;
-    int o[3], e[3];
-    for (int c = 0; c < 3; ++c) {
+    for (int c = 0; c < 3; ++c)
         if (dims[c] < 1) return "the volume is empty";
-        o[c] = whole ? 0 : origin[c];
-        const int n = whole ? dims[c] : extent[c];
-        if (n <= 0) return "box extent: must be > 0 along every axis (or all three 0: the whole volume)";
-        if (o[c] < 0 || n > dims[c] - o[c]) return "the box leaves the volume";
-        e[c] = o[c] + n;
-    }
-    for (int c = 0; c < 3; ++c) { box_origin[c] = o[c]; box_end[c] = e[c]; }
+    VoxelBox box;
+    const BoxVerdict v = box_resolve(dims, origin, extent, true, &box, nullptr);
+    if (v.what != BOX_OK) return box_refusal_text(v.what, true);
+    for (int c = 0; c < 3; ++c) { box_origin[c] = box.origin[c]; box_end[c] = box.end[c]; }
     return nullptr;
 }
 

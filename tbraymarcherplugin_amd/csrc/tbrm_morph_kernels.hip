@@ -2,8 +2,7 @@
 // label bytes (k_morph_load), the unit steps (k_morph_steps) and the comparison with the label bytes, the counts and the write
 // (k_morph_write).
 //
-// The boards are those of region growing (tbrm_segment_kernels.hip): a brick's 512 voxels are 8 uint64 words, word k is z slice k,
-// bit y * 8 + x, so byte i of a board's 64 bytes is the x row (y, z) = (i & 7, i >> 3). A brick has two boards in the scratch; a
+// The boards and their index rules are tbrm_brick_boards.h's. A brick has two boards in the scratch; a
 // launch of k_morph_steps reads one of every brick and writes the other of its own brick, so within a launch nothing that is read
 // is written: the kernel boundary is the only hand-off between bricks. Bits outside the volume — the padding of ragged edge
 // bricks — are never set in a board.
@@ -43,47 +42,6 @@ constexpr int kStepThreads = TBRM_MORPH_STEP_THREADS;
 constexpr int kStepRows = kWinRows / kStepThreads; // rows to a thread
 static_assert(kStepThreads % 64 == 0 && kStepRows * kStepThreads == kWinRows, "whole waves, whole rows");
 
-__device__ __forceinline__ void morph_box_brick(const int b0[3], const int nb[3], uint32_t k, int& bx, int& by, int& bz)
-{
-    const uint32_t ix = k % (uint32_t) nb[0], r = k / (uint32_t) nb[0];
-    bx = b0[0] + (int) ix;
-    by = b0[1] + (int) (r % (uint32_t) nb[1]);
-    bz = b0[2] + (int) (r / (uint32_t) nb[1]);
-}
-
-__device__ __forceinline__ size_t morph_brick_index(const MorphParams& p, int bx, int by, int bz)
-{
-    return (size_t) bz * (size_t) p.bnxy + (size_t) by * (size_t) p.bnx + (size_t) bx;
-}
-
-// the in-volume bits of the x row (y, z) of the brick (bx, by, bz), a brick of the volume's grid
-__device__ __forceinline__ uint32_t volume_row(const MorphParams& p, int bx, int by, int bz, int y, int z)
-{
-    if (by * kBrick + y >= p.dims[1] || bz * kBrick + z >= p.dims[2]) return 0u;
-    return 0xffu >> (kBrick - min(p.dims[0] - bx * kBrick, kBrick));
-}
-
-// the in-volume bits of slice s of that brick
-__device__ __forceinline__ uint64_t volume_slice(const MorphParams& p, int bx, int by, int bz, int s)
-{
-    if (bz * kBrick + s >= p.dims[2]) return 0ull;
-    const uint64_t xs = (uint64_t) (0xffu >> (kBrick - min(p.dims[0] - bx * kBrick, kBrick))) * 0x0101010101010101ull;
-    const int rows = min(p.dims[1] - by * kBrick, kBrick);
-    return rows == kBrick ? xs : xs & ((1ull << (8 * rows)) - 1ull);
-}
-
-// bit i: label byte i of the row has its bit in the mask
-__device__ __forceinline__ uint32_t row_in_mask(const uint2 l, const uint32_t* mask)
-{
-    uint32_t m = 0u;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const uint32_t L = ((i < 4 ? l.x : l.y) >> (8 * (i & 3))) & 255u;
-        m |= ((mask[L >> 5] >> (L & 31)) & 1u) << i;
-    }
-    return m;
-}
-
 __device__ __forceinline__ uint32_t board_class(bool any, bool all) { return !any ? MORPH_EMPTY : (all ? MORPH_FULL : MORPH_MIXED); }
 
 } // namespace
@@ -97,13 +55,13 @@ __global__ __launch_bounds__(kMorphWaveThreads) void k_morph_load(const MorphPar
     const int tid = threadIdx.x, lane = tid & 63;
     if (tid < 8) s_source[tid] = p.source[tid];
     __syncthreads();
-    const uint32_t total = (uint32_t) p.nb[0] * (uint32_t) p.nb[1] * (uint32_t) p.nb[2];
+    const uint32_t total = (uint32_t) range_bricks(p.range);
     const uint32_t k = blockIdx.x * (kMorphWaveThreads / 64) + (uint32_t) (tid >> 6);
     if (k >= total) return;
     int bx, by, bz;
-    morph_box_brick(p.b0, p.nb, k, bx, by, bz);
-    const size_t b = morph_brick_index(p, bx, by, bz);
-    const uint32_t vol = volume_row(p, bx, by, bz, lane & 7, lane >> 3);
+    range_brick(p.range, k, bx, by, bz);
+    const size_t b = grid_index(p.bnx, p.bnxy, bx, by, bz);
+    const uint32_t vol = row_in_volume(p.dims, bx, by * kBrick + (lane & 7), bz * kBrick + (lane >> 3));
     const uint2 l = *reinterpret_cast<const uint2*>(p.labels + b * 512 + (size_t) lane * 8);
     const uint32_t set = row_in_mask(l, s_source) & vol;
     reinterpret_cast<uint8_t*>(p.bits + b * 16)[lane] = (uint8_t) set;
@@ -113,7 +71,7 @@ __global__ __launch_bounds__(kMorphWaveThreads) void k_morph_load(const MorphPar
 
 hipError_t launch_morph_load(const MorphParams& p, hipStream_t s)
 {
-    const uint64_t total = (uint64_t) p.nb[0] * p.nb[1] * p.nb[2];
+    const uint64_t total = range_bricks(p.range);
     if (total == 0) return hipSuccess;
     hipLaunchKernelGGL(k_morph_load, dim3((unsigned) ((total + 3) / 4)), dim3(kMorphWaveThreads), 0, s, p);
     return hipGetLastError();
@@ -128,8 +86,8 @@ __global__ __launch_bounds__(kStepThreads) void k_morph_steps(const MorphParams 
     __shared__ uint32_t s_cls[27];              // the neighbours' classes in working form
     const int tid = threadIdx.x;
     int bx, by, bz;
-    morph_box_brick(p.b0, p.nb, blockIdx.x, bx, by, bz); // (the grid is the brick range)
-    const size_t b = morph_brick_index(p, bx, by, bz);
+    range_brick(p.range, blockIdx.x, bx, by, bz); // (the grid is the brick range)
+    const size_t b = grid_index(p.bnx, p.bnxy, bx, by, bz);
     const uint64_t* const in = p.bits + 8 * p.from;
     uint8_t* const out = reinterpret_cast<uint8_t*>(p.bits + b * 16 + 8 * (1 - p.from));
     const uint32_t* const cls_in = p.cls[p.from];
@@ -140,13 +98,13 @@ __global__ __launch_bounds__(kStepThreads) void k_morph_steps(const MorphParams 
         nx = bx + c % 3 - 1;
         ny = by + (c / 3) % 3 - 1;
         nz = bz + c / 9 - 1;
-        return nx >= p.b0[0] && nx < p.b0[0] + p.nb[0] && ny >= p.b0[1] && ny < p.b0[1] + p.nb[1] && nz >= p.b0[2] && nz < p.b0[2] + p.nb[2];
+        return range_holds(p.range, nx, ny, nz);
     };
     uint32_t mine = MORPH_EMPTY;
     if (tid < 27) {
         int nx, ny, nz;
         if (neighbour(tid, nx, ny, nz)) {
-            mine = cls_in[morph_brick_index(p, nx, ny, nz)];
+            mine = cls_in[grid_index(p.bnx, p.bnxy, nx, ny, nz)];
             if (erode && mine != MORPH_MIXED) mine ^= 1u; // the complement of an empty board is full, of a full one empty
         }
         s_cls[tid] = mine;
@@ -155,7 +113,7 @@ __global__ __launch_bounds__(kStepThreads) void k_morph_steps(const MorphParams 
     const uint32_t centre = s_cls[13];
     if (centre == MORPH_FULL || !some) { // the working set stays full here, or nothing can reach this brick: no window
         const bool full = (centre == MORPH_FULL) != erode; // of the set itself
-        if (tid < 64) out[tid] = full ? (uint8_t) volume_row(p, bx, by, bz, tid & 7, tid >> 3) : (uint8_t) 0;
+        if (tid < 64) out[tid] = full ? (uint8_t) row_in_volume(p.dims, bx, by * kBrick + (tid & 7), bz * kBrick + (tid >> 3)) : (uint8_t) 0;
         if (tid == 0) p.cls[1 - p.from][b] = full ? MORPH_FULL : MORPH_EMPTY;
         return;
     }
@@ -167,10 +125,10 @@ __global__ __launch_bounds__(kStepThreads) void k_morph_steps(const MorphParams 
         if (cl != MORPH_EMPTY) { // (a neighbour outside the range was given the class empty)
             int nx, ny, nz;
             neighbour(c, nx, ny, nz);
-            const uint64_t vol = volume_slice(p, nx, ny, nz, s);
+            const uint64_t vol = slice_in_volume(p.dims, nx, ny, nz * kBrick + s);
             if (cl == MORPH_FULL) w = vol;
             else {
-                w = in[morph_brick_index(p, nx, ny, nz) * 16 + s];
+                w = in[grid_index(p.bnx, p.bnxy, nx, ny, nz) * 16 + s];
                 if (erode) w = ~w & vol;
             }
         }
@@ -230,7 +188,7 @@ __global__ __launch_bounds__(kStepThreads) void k_morph_steps(const MorphParams 
     uint32_t row = 0u, vol = 0u;
     if (tid < 64) {
         const int y = tid & 7, s = tid >> 3;
-        vol = volume_row(p, bx, by, bz, y, s);
+        vol = row_in_volume(p.dims, bx, by * kBrick + y, bz * kBrick + s);
         row = (s_win[steps & 1][(kBrick + s) * kWin + kBrick + y] >> kBrick) & 0xffu;
         if (erode) row = ~row & vol;
         out[tid] = (uint8_t) row;
@@ -244,7 +202,7 @@ __global__ __launch_bounds__(kStepThreads) void k_morph_steps(const MorphParams 
 
 hipError_t launch_morph_steps(const MorphParams& p, hipStream_t s)
 {
-    const uint64_t total = (uint64_t) p.nb[0] * p.nb[1] * p.nb[2];
+    const uint64_t total = range_bricks(p.range);
     if (total == 0) return hipSuccess;
     if (p.conn26) hipLaunchKernelGGL(k_morph_steps<1>, dim3((unsigned) total), dim3(kStepThreads), 0, s, p);
     else hipLaunchKernelGGL(k_morph_steps<0>, dim3((unsigned) total), dim3(kStepThreads), 0, s, p);
@@ -262,18 +220,14 @@ __global__ __launch_bounds__(kMorphWaveThreads) void k_morph_write(const MorphPa
     const int tid = threadIdx.x, lane = tid & 63;
     if (tid < 8) { s_source[tid] = p.source[tid]; s_writable[tid] = p.writable[tid]; }
     __syncthreads();
-    const uint32_t total = (uint32_t) p.wnb[0] * (uint32_t) p.wnb[1] * (uint32_t) p.wnb[2];
+    const uint32_t total = (uint32_t) range_bricks(p.wrange);
     const uint32_t k = blockIdx.x * (kMorphWaveThreads / 64) + (uint32_t) (tid >> 6);
     if (k >= total) return;
     int bx, by, bz;
-    morph_box_brick(p.wb0, p.wnb, k, bx, by, bz);
-    const size_t b = morph_brick_index(p, bx, by, bz);
+    range_brick(p.wrange, k, bx, by, bz);
+    const size_t b = grid_index(p.bnx, p.bnxy, bx, by, bz);
     const int y = by * kBrick + (lane & 7), z = bz * kBrick + (lane >> 3);
-    uint32_t box = 0u; // bit i: voxel i of the row lies inside the box (which lies inside the volume)
-    if (y >= p.origin[1] && y < p.end[1] && z >= p.origin[2] && z < p.end[2]) {
-        const int lo = max(p.origin[0] - bx * kBrick, 0), hi = min(p.end[0] - bx * kBrick, kBrick); // hi > lo: the box touches the brick
-        box = (0xffu >> (kBrick - hi)) & (0xffu << lo) & 0xffu;
-    }
+    const uint32_t box = row_in_box(p.box, bx, y, z); // (the box lies inside the volume)
     uint2* const bytes = reinterpret_cast<uint2*>(p.labels + b * 512 + (size_t) lane * 8);
     const uint2 old = *bytes;
     const uint32_t S = row_in_mask(old, s_source) & box;
@@ -287,52 +241,32 @@ __global__ __launch_bounds__(kMorphWaveThreads) void k_morph_write(const MorphPa
         for (int i = 0; i < 8; ++i) {
             if (!((moved >> i) & 1u)) continue;
             const uint32_t to = (uint32_t) (((joins >> i) & 1u) ? p.new_label : p.erase_label);
-            uint32_t& half = i < 4 ? l.x : l.y;
-            const int sh = 8 * (i & 3);
-            changed += ((half >> sh) & 255u) != to;
-            half = (half & ~(255u << sh)) | (to << sh);
+            changed += byte_of(l, i) != to;
+            set_byte(l, i, to);
         }
         if (changed) *bytes = l;
     }
     int n[5] = {(int) __popc(S), (int) __popc(R), (int) __popc(joins), (int) __popc(leaves), changed};
-    int mn[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, mx[3] = {-1, -1, -1};
-    if (moved) {
-        mn[0] = bx * kBrick + (__ffs((int) moved) - 1);
-        mx[0] = bx * kBrick + (31 - __clz((int) moved));
-        mn[1] = mx[1] = y;
-        mn[2] = mx[2] = z;
-    }
+    WaveBounds bounds;
+    bounds.take_row(moved, bx, y, z);
     const bool wrote = __ballot(changed != 0) != 0ull;
     if (__ballot((S | R) != 0u) == 0ull) return; // nothing to count (and then nothing moved)
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int c = 0; c < 5; ++c) n[c] += __shfl_xor(n[c], o, 64);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            mn[c] = min(mn[c], __shfl_xor(mn[c], o, 64));
-            mx[c] = max(mx[c], __shfl_xor(mx[c], o, 64));
-        }
-    }
+    for (int c = 0; c < 5; ++c) n[c] = wave_sum(n[c]);
+    bounds.reduce();
     if (lane == 0) {
         unsigned long long* const counts = reinterpret_cast<unsigned long long*>(p.ctl);
 #pragma unroll
         for (int c = 0; c < 5; ++c)
             if (n[c]) atomicAdd(counts + MORPH_SOURCE + c, (unsigned long long) n[c]);
         if (wrote) atomicAdd(counts + MORPH_BRICKS_WRITTEN, 1ull);
-        if (mx[0] >= 0) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                atomicMin(p.ctl + MORPH_MIN_X + c, mn[c]);
-                atomicMax(p.ctl + MORPH_MAX_X + c, mx[c]);
-            }
-        }
     }
+    bounds.commit(p.ctl + MORPH_MIN_X, lane);
 }
 
 hipError_t launch_morph_write(const MorphParams& p, hipStream_t s)
 {
-    const uint64_t total = (uint64_t) p.wnb[0] * p.wnb[1] * p.wnb[2];
+    const uint64_t total = range_bricks(p.wrange);
     if (total == 0) return hipSuccess;
     hipLaunchKernelGGL(k_morph_write, dim3((unsigned) ((total + 3) / 4)), dim3(kMorphWaveThreads), 0, s, p);
     return hipGetLastError();

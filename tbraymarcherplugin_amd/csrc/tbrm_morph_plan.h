@@ -8,6 +8,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "tbrm_box.h"
+
 namespace tbrm {
 
 constexpr int kMorphMaxRadius = 64;
@@ -40,10 +42,8 @@ inline bool morph_plan(const int dims[3], const int origin[3], const int end[3],
     for (int c = 0; c < 3; ++c) {
         const int lo = origin[c] - p.reach < 0 ? 0 : origin[c] - p.reach;
         const int hi = end[c] > dims[c] - p.reach ? dims[c] : end[c] + p.reach; // (no overflow: dims[c] - reach is formed, not end + reach)
-        p.b0[c] = lo >> 3;
-        p.nb[c] = ((hi - 1) >> 3) - p.b0[c] + 1;
-        p.wb0[c] = origin[c] >> 3;
-        p.wnb[c] = ((end[c] - 1) >> 3) - p.wb0[c] + 1;
+        axis_bricks(lo, hi, p.b0[c], p.nb[c]);
+        axis_bricks(origin[c], end[c], p.wb0[c], p.wnb[c]);
     }
     const int first_erodes = op == MORPH_ERODE || op == MORPH_OPEN;
     for (int phase = 0; phase < (two ? 2 : 1); ++phase)

@@ -5,6 +5,7 @@
 
 #include "../../include/tbrm.h"
 #include "../../include/tbrm_color_lights.h"
+#include "tbrm_box.h"
 #include "tbrm_host_math.h"
 #include "tbrm_internal.h"
 
@@ -473,6 +474,32 @@ void release_labels(tbrm_resources* r);                // (the stream must be id
 int allocate_labels(tbrm_resources* r);
 int brick_masks(tbrm_resources* r, const int b0[3], const int b1[3]); // d_lab_mask of the bricks [b0, b1)
 int refresh_live(tbrm_resources* r);                   // the per-brick live bits and the volume's label set; the merged metadata goes stale
+// ---- label edits: what tbrm_grow_region, tbrm_morph_labels, tbrm_label_islands and the region calls share ----
+// a refused box (tbrm_box.h) as the call's error: the axis, the caller's origin and extent, the volume's width (dims null: not known yet)
+int fail_box(const BoxVerdict& v, bool zero_is_whole, const int* dims, const int32_t* origin, const int32_t* extent);
+int refuse_resident(const tbrm_resources* r);          // slab-resident handles hold only some layers: TBRM_ERR_UNSUPPORTED
+// the handle at the beginning of an edit, after the arguments: a volume, a label volume (no_labels: what to say without one; null:
+// none is needed), the device bound
+int begin_label_edit(const tbrm_resources* r, const char* no_labels);
+// after label bytes inside the voxels [bbox_min, bbox_max] changed (bbox_max[0] < 0: none did): the touched bricks' label sets, then refresh_live
+int labels_changed(tbrm_resources* r, const int32_t bbox_min[3], const int32_t bbox_max[3]);
+// the start values of a call's control words: zeros, and the bounding box at min_x .. min_x + 5 as (dims, -1)
+inline void ctl_start(int32_t* ctl, int words, int min_x, const int dims[3])
+{
+    std::fill(ctl, ctl + words, 0);
+    for (int c = 0; c < 3; ++c) { ctl[min_x + c] = dims[c]; ctl[min_x + 3 + c] = -1; }
+}
+// carves 256-byte aligned parts out of a buffer (or only adds them up: base == nullptr)
+struct Carver {
+    char* base;
+    size_t off = 0;
+    template <class T> T* take(size_t n)
+    {
+        T* const at = base ? (T*) (base + off) : nullptr;
+        off += (n * sizeof(T) + 255) / 256 * 256;
+        return at;
+    }
+};
 // the scratch of region growing (tbrm_api_segment.cpp), which label morphology (tbrm_api_morph.cpp) works in too: where its parts lie,
 // and the handle's one allocation of it (counted as an operator allocation)
 struct GrowScratch {

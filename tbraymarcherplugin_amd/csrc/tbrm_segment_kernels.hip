@@ -2,10 +2,8 @@
 // bits (k_grow_candidates), the seeds (k_grow_seeds), the propagation passes (k_grow_pass), the region's size and bounding box
 // (k_grow_measure) and the label write (k_grow_write).
 //
-// The fill is bit-parallel. A brick's 512 voxels are 8 uint64 words: word k is z slice k, bit y * 8 + x — on this little-endian
-// target byte y of word k is the x row (y, k), so byte i of a brick's 64 bytes is the row (y, z) = (i & 7, i >> 3): the row a lane
-// of the brick-per-wave kernels holds (as in tbrm_stats_kernels.hip). Per brick the scratch holds the candidate words and the
-// visited words; visited is a subset of candidate at all times and bits are only ever set.
+// The fill is bit-parallel on the boards of tbrm_brick_boards.h. Per brick the scratch holds the candidate words
+// and the visited words; visited is a subset of candidate at all times and bits are only ever set.
 //
 // A propagation pass looks at the activity words of 64 bricks per wave and gives each due brick 8 lanes, one per slice word, 8 bricks
 // at a time. A brick reads the facing bits of its neighbours' visited words ONCE (the halo: a face word, a bit column, a single
@@ -26,38 +24,7 @@
 
 namespace tbrm {
 
-namespace {
-
 constexpr int kGrowThreads = 256;
-constexpr uint64_t kCol0 = 0x0101010101010101ull, kCol7 = 0x8080808080808080ull;
-
-// brick k of the box's brick list -> its coordinates on the volume's brick grid
-__device__ __forceinline__ void box_brick(const int b0[3], const int nb[3], uint32_t k, int& bx, int& by, int& bz)
-{
-    const uint32_t ix = k % (uint32_t) nb[0], r = k / (uint32_t) nb[0];
-    bx = b0[0] + (int) ix;
-    by = b0[1] + (int) (r % (uint32_t) nb[1]);
-    bz = b0[2] + (int) (r / (uint32_t) nb[1]);
-}
-
-__device__ __forceinline__ size_t brick_index(const GrowParams& p, int bx, int by, int bz)
-{
-    return (size_t) bz * (size_t) p.bnxy + (size_t) by * (size_t) p.bnx + (size_t) bx;
-}
-
-__device__ __forceinline__ bool in_box_bricks(const GrowParams& p, int bx, int by, int bz)
-{
-    return bx >= p.b0[0] && bx < p.b0[0] + p.nb[0] && by >= p.b0[1] && by < p.b0[1] + p.nb[1] && bz >= p.b0[2] && bz < p.b0[2] + p.nb[2];
-}
-
-template <typename T> __device__ __forceinline__ T wave_sum(T v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-} // namespace
 
 // ---- candidates -------------------------------------------------------------------------------------------------------------------
 // The only pass over voxel values and label bytes. A wave per brick of the box, lane l on the row (y, z) = (l & 7, l >> 3): its
@@ -71,28 +38,21 @@ __global__ __launch_bounds__(kGrowThreads) void k_grow_candidates(const GrowPara
     const int tid = threadIdx.x, lane = tid & 63;
     if (tid < 8) s_writable[tid] = p.writable[tid];
     __syncthreads();
-    const uint32_t total = (uint32_t) p.nb[0] * (uint32_t) p.nb[1] * (uint32_t) p.nb[2];
+    const uint32_t total = (uint32_t) range_bricks(p.range);
     const uint32_t k = blockIdx.x * (kGrowThreads / 64) + (uint32_t) (tid >> 6);
     if (k >= total) return;
     int bx, by, bz;
-    box_brick(p.b0, p.nb, k, bx, by, bz);
-    const size_t b = brick_index(p, bx, by, bz);
+    range_brick(p.range, k, bx, by, bz);
+    const size_t b = grid_index(p.bnx, p.bnxy, bx, by, bz);
     const size_t first = b * 512 + (size_t) lane * 8;
 
-    uint32_t inside = 0u; // bit i: voxel i of the row lies inside the box
-    {
-        const int y = by * kBrick + (lane & 7), z = bz * kBrick + (lane >> 3);
-        if (y >= p.origin[1] && y < p.end[1] && z >= p.origin[2] && z < p.end[2]) {
-            const int lo = max(p.origin[0] - bx * kBrick, 0), hi = min(p.end[0] - bx * kBrick, kBrick); // hi > lo: the box touches the brick
-            inside = (0xffu >> (kBrick - hi)) & (0xffu << lo) & 0xffu;
-        }
-    }
+    const uint32_t inside = row_in_box(p.box, bx, by * kBrick + (lane & 7), bz * kBrick + (lane >> 3));
     uint32_t in_range = 0u;
     if constexpr (FMT == FMT_U8) {
         const uint2 v = *reinterpret_cast<const uint2*>((const uint8_t*) p.data + first);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            const uint32_t c = ((i < 4 ? v.x : v.y) >> (8 * (i & 3))) & 255u;
+            const uint32_t c = byte_of(v, i);
             in_range |= (uint32_t) (c >= p.lo_code && c <= p.hi_code) << i;
         }
     } else if constexpr (FMT == FMT_U16) {
@@ -111,14 +71,8 @@ __global__ __launch_bounds__(kGrowThreads) void k_grow_candidates(const GrowPara
         for (int i = 0; i < 8; ++i) in_range |= (uint32_t) (f[i] >= p.lo_f && f[i] <= p.hi_f) << i; // (a NaN fails both)
     }
     uint32_t may = 0u; // bit i: the voxel's label may be grown over
-    if (p.labels) {
-        const uint2 l = *reinterpret_cast<const uint2*>(p.labels + first);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const uint32_t L = ((i < 4 ? l.x : l.y) >> (8 * (i & 3))) & 255u;
-            may |= ((s_writable[L >> 5] >> (L & 31)) & 1u) << i;
-        }
-    } else may = (s_writable[0] & 1u) ? 0xffu : 0u;
+    if (p.labels) may = row_in_mask(*reinterpret_cast<const uint2*>(p.labels + first), s_writable);
+    else may = (s_writable[0] & 1u) ? 0xffu : 0u;
     const uint8_t cand = (uint8_t) (inside & in_range & may);
     uint8_t* const bytes = reinterpret_cast<uint8_t*>(p.bits + b * 16);
     bytes[lane] = cand;
@@ -128,7 +82,7 @@ __global__ __launch_bounds__(kGrowThreads) void k_grow_candidates(const GrowPara
 
 hipError_t launch_grow_candidates(const GrowParams& p, hipStream_t s)
 {
-    const uint64_t total = (uint64_t) p.nb[0] * p.nb[1] * p.nb[2];
+    const uint64_t total = range_bricks(p.range);
     if (total == 0) return hipSuccess;
     const dim3 grid((unsigned) ((total + 3) / 4)), block(kGrowThreads);
     switch (p.fmt) {
@@ -147,8 +101,8 @@ __global__ __launch_bounds__(kGrowThreads) void k_grow_seeds(const GrowParams p)
     const int i = blockIdx.x * kGrowThreads + threadIdx.x;
     if (i >= p.n_seeds) return;
     const int x = p.seeds[3 * i], y = p.seeds[3 * i + 1], z = p.seeds[3 * i + 2];
-    if (x < p.origin[0] || x >= p.end[0] || y < p.origin[1] || y >= p.end[1] || z < p.origin[2] || z >= p.end[2]) return;
-    const size_t b = brick_index(p, x >> kBrickShift, y >> kBrickShift, z >> kBrickShift);
+    if (x < p.box.origin[0] || x >= p.box.end[0] || y < p.box.origin[1] || y >= p.box.end[1] || z < p.box.origin[2] || z >= p.box.end[2]) return;
+    const size_t b = grid_index(p.bnx, p.bnxy, x >> kBrickShift, y >> kBrickShift, z >> kBrickShift);
     uint64_t* const words = p.bits + b * 16;
     const uint64_t bit = 1ull << ((y & 7) * 8 + (x & 7));
     if (!(words[z & 7] & bit)) return;
@@ -179,7 +133,7 @@ struct SliceHalo {
 template <int CONN26>
 __device__ __forceinline__ SliceHalo slice_halo(uint64_t l, uint64_t r, uint64_t t, uint64_t d, uint64_t tl, uint64_t tr, uint64_t dl, uint64_t dr)
 {
-    const uint64_t lc = (l >> 7) & kCol0, rc = (r << 7) & kCol7; // l's column 7 at our column 0, r's column 0 at our column 7
+    const uint64_t lc = (l >> 7) & kSliceX0, rc = (r << 7) & kSliceX7; // l's column 7 at our column 0, r's column 0 at our column 7
     SliceHalo h;
     if constexpr (!CONN26) h.fixed = lc | rc | (t >> 56) | (d << 56); // t's row 7 at our row 0, d's row 0 at our row 7
     else {
@@ -192,12 +146,7 @@ __device__ __forceinline__ SliceHalo slice_halo(uint64_t l, uint64_t r, uint64_t
     return h;
 }
 
-template <int CONN26> __device__ __forceinline__ uint64_t slice_dilate(uint64_t w, const SliceHalo& h)
-{
-    const uint64_t x3 = w | ((w << 1) & ~kCol0) | ((w >> 1) & ~kCol7);
-    if constexpr (!CONN26) return x3 | (w << 8) | (w >> 8) | h.fixed;
-    else return x3 | (x3 << 8) | (x3 >> 8) | h.fixed;
-}
+template <int CONN26> __device__ __forceinline__ uint64_t slice_dilate(uint64_t w, const SliceHalo& h) { return slice_spread<CONN26>(w) | h.fixed; }
 
 } // namespace
 
@@ -205,15 +154,15 @@ template <int CONN26>
 __global__ __launch_bounds__(kGrowThreads) void k_grow_pass(const GrowParams p)
 {
     const int tid = threadIdx.x, lane = tid & 63, j = tid & 7; // j: this lane's slice
-    const uint32_t total = (uint32_t) p.nb[0] * (uint32_t) p.nb[1] * (uint32_t) p.nb[2];
+    const uint32_t total = (uint32_t) range_bricks(p.range);
     // The wave's 64 bricks of the box's brick list, a lane each: which are due? Most of a pass's waves find none and end here, at the
     // cost of one coalesced 256-byte load. (No other workgroup writes this pass's activity array in this launch.)
     const uint32_t base = (blockIdx.x * (kGrowThreads / 64) + (uint32_t) (tid >> 6)) * 64u;
     bool mine_due = false;
     if (base + (uint32_t) lane < total) {
         int bx, by, bz;
-        box_brick(p.b0, p.nb, base + (uint32_t) lane, bx, by, bz);
-        const size_t b = brick_index(p, bx, by, bz);
+        range_brick(p.range, base + (uint32_t) lane, bx, by, bz);
+        const size_t b = grid_index(p.bnx, p.bnxy, bx, by, bz);
         mine_due = p.act[0][b] != 0u;
         if (mine_due) p.act[0][b] = 0u;
     }
@@ -235,8 +184,8 @@ __global__ __launch_bounds__(kGrowThreads) void k_grow_pass(const GrowParams p)
         int bx = 0, by = 0, bz = 0;
         size_t b = 0;
         if (due) {
-            box_brick(p.b0, p.nb, base + (uint32_t) pick, bx, by, bz);
-            b = brick_index(p, bx, by, bz);
+            range_brick(p.range, base + (uint32_t) pick, bx, by, bz);
+            b = grid_index(p.bnx, p.bnxy, bx, by, bz);
         }
         uint64_t* const words = p.bits + b * 16;
         uint64_t cand = 0ull, vis = 0ull;
@@ -248,8 +197,8 @@ __global__ __launch_bounds__(kGrowThreads) void k_grow_pass(const GrowParams p)
             // slice `s` of the visited words of the brick at (dx, dy, dz) from this one; zero outside the box's bricks
             auto nbr = [&](int dx, int dy, int dz, int s) -> uint64_t {
                 const int nx = bx + dx, ny = by + dy, nz = bz + dz;
-                if (!in_box_bricks(p, nx, ny, nz)) return 0ull;
-                return p.bits[brick_index(p, nx, ny, nz) * 16 + 8 + s];
+                if (!range_holds(p.range, nx, ny, nz)) return 0ull;
+                return p.bits[grid_index(p.bnx, p.bnxy, nx, ny, nz) * 16 + 8 + s];
             };
             if constexpr (!CONN26) {
                 halo = slice_halo<0>(nbr(-1, 0, 0, j), nbr(1, 0, 0, j), nbr(0, -1, 0, j), nbr(0, 1, 0, j), 0ull, 0ull, 0ull, 0ull);
@@ -293,7 +242,7 @@ __global__ __launch_bounds__(kGrowThreads) void k_grow_pass(const GrowParams p)
             for (int c = j; c < 27; c += 8) {
                 const int dx = c % 3 - 1, dy = (c / 3) % 3 - 1, dz = c / 9 - 1;
                 if (!CONN26 && (dx != 0) + (dy != 0) + (dz != 0) > 1) continue;
-                if (in_box_bricks(p, bx + dx, by + dy, bz + dz)) p.act[1][brick_index(p, bx + dx, by + dy, bz + dz)] = 1u;
+                if (range_holds(p.range, bx + dx, by + dy, bz + dz)) p.act[1][grid_index(p.bnx, p.bnxy, bx + dx, by + dy, bz + dz)] = 1u;
             }
         }
         changed_bricks += (int) __popcll(__ballot(changed && j == 0));
@@ -303,7 +252,7 @@ __global__ __launch_bounds__(kGrowThreads) void k_grow_pass(const GrowParams p)
 
 hipError_t launch_grow_pass(const GrowParams& p, hipStream_t s)
 {
-    const uint64_t total = (uint64_t) p.nb[0] * p.nb[1] * p.nb[2];
+    const uint64_t total = range_bricks(p.range);
     if (total == 0) return hipSuccess;
     const dim3 grid((unsigned) ((total + 255) / 256)), block(kGrowThreads); // 64 bricks to a wave
     if (p.conn26) hipLaunchKernelGGL(k_grow_pass<1>, grid, block, 0, s, p);
@@ -317,49 +266,26 @@ hipError_t launch_grow_pass(const GrowParams& p, hipStream_t s)
 __global__ __launch_bounds__(kGrowThreads) void k_grow_measure(const GrowParams p)
 {
     const int tid = threadIdx.x, j = tid & 7;
-    const uint32_t total = (uint32_t) p.nb[0] * (uint32_t) p.nb[1] * (uint32_t) p.nb[2];
+    const uint32_t total = (uint32_t) range_bricks(p.range);
     const uint32_t k = blockIdx.x * (kGrowThreads / 8) + (uint32_t) (tid >> 3);
     uint64_t w = 0ull;
     int bx = 0, by = 0, bz = 0;
     if (k < total) {
-        box_brick(p.b0, p.nb, k, bx, by, bz);
-        w = p.bits[brick_index(p, bx, by, bz) * 16 + 8 + j];
+        range_brick(p.range, k, bx, by, bz);
+        w = p.bits[grid_index(p.bnx, p.bnxy, bx, by, bz) * 16 + 8 + j];
     }
     if (__ballot(w != 0ull) == 0ull) return;
-    int n = __popcll(w);
-    int mn[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, mx[3] = {-1, -1, -1};
-    if (w) {
-        uint32_t cols = (uint32_t) (w | (w >> 32)); // the OR of the eight rows
-        cols |= cols >> 16;
-        cols = (cols | (cols >> 8)) & 0xffu;
-        mn[0] = bx * kBrick + (__ffs((int) cols) - 1);
-        mx[0] = bx * kBrick + (31 - __clz((int) cols));
-        mn[1] = by * kBrick + ((__ffsll((long long) w) - 1) >> 3);
-        mx[1] = by * kBrick + ((63 - __clzll((long long) w)) >> 3);
-        mn[2] = mx[2] = bz * kBrick + j;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        n += __shfl_xor(n, o, 64);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            mn[c] = min(mn[c], __shfl_xor(mn[c], o, 64));
-            mx[c] = max(mx[c], __shfl_xor(mx[c], o, 64));
-        }
-    }
-    if ((tid & 63) == 0) {
-        atomicAdd(p.ctl + GROW_VOXELS, n);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            atomicMin(p.ctl + GROW_MIN_X + c, mn[c]);
-            atomicMax(p.ctl + GROW_MAX_X + c, mx[c]);
-        }
-    }
+    const int n = wave_sum((int) __popcll(w));
+    WaveBounds bounds;
+    bounds.take_slice(w, bx, by, bz * kBrick + j);
+    bounds.reduce();
+    if ((tid & 63) == 0) atomicAdd(p.ctl + GROW_VOXELS, n);
+    bounds.commit(p.ctl + GROW_MIN_X, tid & 63);
 }
 
 hipError_t launch_grow_measure(const GrowParams& p, hipStream_t s)
 {
-    const uint64_t total = (uint64_t) p.nb[0] * p.nb[1] * p.nb[2];
+    const uint64_t total = range_bricks(p.range);
     if (total == 0) return hipSuccess;
     hipLaunchKernelGGL(k_grow_measure, dim3((unsigned) ((total + 31) / 32)), dim3(kGrowThreads), 0, s, p);
     return hipGetLastError();
@@ -368,31 +294,26 @@ hipError_t launch_grow_measure(const GrowParams& p, hipStream_t s)
 // ---- the label write ----------------------------------------------------------------------------------------------------------------
 // A wave per brick of the region's bounding box, lane l on the row (l & 7, l >> 3) as above: new_label where the row's visited byte
 // has a bit, the row stored where it has any. Counts the bytes that changed and the bricks that held region voxels.
-__global__ __launch_bounds__(kGrowThreads) void k_grow_write(const GrowParams p, const int wb0x, const int wb0y, const int wb0z, const int wnx,
-                                                             const int wny, const int wnz)
+__global__ __launch_bounds__(kGrowThreads) void k_grow_write(const GrowParams p, const BrickRange w)
 {
     const int tid = threadIdx.x, lane = tid & 63;
-    const uint32_t total = (uint32_t) wnx * (uint32_t) wny * (uint32_t) wnz;
+    const uint32_t total = (uint32_t) range_bricks(w);
     const uint32_t k = blockIdx.x * (kGrowThreads / 64) + (uint32_t) (tid >> 6);
     if (k >= total) return;
-    const int wb0[3] = {wb0x, wb0y, wb0z}, wnb[3] = {wnx, wny, wnz};
     int bx, by, bz;
-    box_brick(wb0, wnb, k, bx, by, bz);
-    const size_t b = brick_index(p, bx, by, bz);
+    range_brick(w, k, bx, by, bz);
+    const size_t b = grid_index(p.bnx, p.bnxy, bx, by, bz);
     const uint32_t vis = reinterpret_cast<const uint8_t*>(p.bits + b * 16)[64 + lane];
     if (__ballot(vis != 0u) == 0ull) return;
     int changed = 0;
     if (vis) {
         uint2* const row = reinterpret_cast<uint2*>(p.labels + b * 512 + (size_t) lane * 8);
-        const uint2 old = *row;
-        uint2 l = old;
+        uint2 l = *row;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             if (!((vis >> i) & 1u)) continue;
-            uint32_t& half = i < 4 ? l.x : l.y;
-            const int sh = 8 * (i & 3);
-            changed += ((half >> sh) & 255u) != (uint32_t) p.new_label;
-            half = (half & ~(255u << sh)) | ((uint32_t) p.new_label << sh);
+            changed += byte_of(l, i) != (uint32_t) p.new_label;
+            set_byte(l, i, (uint32_t) p.new_label);
         }
         *row = l;
     }
@@ -403,11 +324,11 @@ __global__ __launch_bounds__(kGrowThreads) void k_grow_write(const GrowParams p,
     }
 }
 
-hipError_t launch_grow_write(const GrowParams& p, const int wb0[3], const int wnb[3], hipStream_t s)
+hipError_t launch_grow_write(const GrowParams& p, const BrickRange& w, hipStream_t s)
 {
-    const uint64_t total = (uint64_t) wnb[0] * wnb[1] * wnb[2];
+    const uint64_t total = range_bricks(w);
     if (total == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_grow_write, dim3((unsigned) ((total + 3) / 4)), dim3(kGrowThreads), 0, s, p, wb0[0], wb0[1], wb0[2], wnb[0], wnb[1], wnb[2]);
+    hipLaunchKernelGGL(k_grow_write, dim3((unsigned) ((total + 3) / 4)), dim3(kGrowThreads), 0, s, p, w);
     return hipGetLastError();
 }
 

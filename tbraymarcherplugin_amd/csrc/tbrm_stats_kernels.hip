@@ -2,8 +2,8 @@
 // (k_volume_histogram) and the per-label count / sum / min / max (k_label_statistics). Both read the volume as it lies, and the
 // bricked label volume on the same grid.
 //
-// Common shape. The work is the list of the bricks the box touches. A wave takes one brick at a time: lane l holds the x row
-// (y, z) = (l & 7, l >> 3) of the brick, 8 voxels — one 16-byte load for UNORM16 (the whole 1 KiB brick in one wave instruction),
+// Common shape. The work is the list of the bricks the box touches (the range and row rules are tbrm_brick_boards.h's, DESIGN.md
+// §17). A wave takes one brick at a time: lane l holds the x row (y, z) = (l & 7, l >> 3) of the brick, 8 voxels — one 16-byte load for UNORM16 (the whole 1 KiB brick in one wave instruction),
 // 8 bytes for UNORM8 and for the labels, two 16-byte loads for float32 — and the next brick's row is requested before this one
 // is counted. The grid is sized to the device (a few workgroups per compute unit, the waves striding over the bricks), so what
 // the workgroups flush to global memory at the end is bounded by the grid, not by the volume.
@@ -29,7 +29,7 @@ template <int FMT> struct Row;
 template <> struct Row<FMT_U8> {
     uint2 v;
     __device__ __forceinline__ void load(const void* data, size_t first) { v = *reinterpret_cast<const uint2*>((const uint8_t*) data + first); }
-    __device__ __forceinline__ uint32_t code(int i) const { return ((i < 4 ? v.x : v.y) >> (8 * (i & 3))) & 255u; }
+    __device__ __forceinline__ uint32_t code(int i) const { return byte_of(v, i); }
 };
 template <> struct Row<FMT_U16> {
     uint4 v;
@@ -56,38 +56,20 @@ template <> struct Row<FMT_F32> {
 
 struct BrickAt {
     size_t first;  // element index of the brick's first voxel
-    int x0, y0, z0;
+    int bx, by, bz;
     bool whole;
 };
 
 // brick k of the box's brick list (k is uniform over the wave)
 __device__ __forceinline__ BrickAt brick_at(const StatsParams& p, uint32_t k)
 {
-    const uint32_t ix = k % (uint32_t) p.nb[0], r = k / (uint32_t) p.nb[0];
-    const uint32_t iy = r % (uint32_t) p.nb[1], iz = r / (uint32_t) p.nb[1];
-    const int bx = p.b0[0] + (int) ix, by = p.b0[1] + (int) iy, bz = p.b0[2] + (int) iz;
     BrickAt b;
-    b.first = ((size_t) bz * (size_t) p.bnxy + (size_t) by * (size_t) p.bnx + (size_t) bx) * 512;
-    b.x0 = bx * kBrick; b.y0 = by * kBrick; b.z0 = bz * kBrick;
-    b.whole = b.x0 >= p.origin[0] && b.x0 + kBrick <= p.end[0] && b.y0 >= p.origin[1] && b.y0 + kBrick <= p.end[1] &&
-              b.z0 >= p.origin[2] && b.z0 + kBrick <= p.end[2];
+    range_brick(p.range, k, b.bx, b.by, b.bz);
+    b.first = grid_index(p.bnx, p.bnxy, b.bx, b.by, b.bz) * 512;
+    const int x0 = b.bx * kBrick, y0 = b.by * kBrick, z0 = b.bz * kBrick;
+    b.whole = x0 >= p.box.origin[0] && x0 + kBrick <= p.box.end[0] && y0 >= p.box.origin[1] && y0 + kBrick <= p.box.end[1] &&
+              z0 >= p.box.origin[2] && z0 + kBrick <= p.box.end[2];
     return b;
-}
-
-// bit i: voxel i of this lane's row lies inside the box (cut bricks)
-__device__ __forceinline__ uint32_t row_inside(const StatsParams& p, const BrickAt& b, int lane)
-{
-    const int y = b.y0 + (lane & 7), z = b.z0 + (lane >> 3);
-    if (y < p.origin[1] || y >= p.end[1] || z < p.origin[2] || z >= p.end[2]) return 0u;
-    const int lo = max(p.origin[0] - b.x0, 0), hi = min(p.end[0] - b.x0, kBrick); // [lo, hi) of the row, hi > lo: the box touches the brick
-    return (0xffu >> (kBrick - hi)) & (0xffu << lo) & 0xffu;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // One count into a lane's LDS histogram, aggregated inside the wave first. Real scans are spikes — most of a CT is one air value —
@@ -137,7 +119,7 @@ __global__ __launch_bounds__(kStatsThreads) void k_volume_histogram(const StatsP
     __syncthreads();
     uint32_t* const hist = s_hist + ((4u * wave + (uint32_t) (lane & 3)) & (p.copies - 1u)) * n_bins;
 
-    const uint32_t total = (uint32_t) p.nb[0] * (uint32_t) p.nb[1] * (uint32_t) p.nb[2];
+    const uint32_t total = (uint32_t) range_bricks(p.range);
     const uint32_t stride = gridDim.x * kStatsWaves;
     uint32_t below = 0u, above = 0u, nans = 0u, visited = 0u;
     const float n_bins_f = (float) n_bins;
@@ -147,7 +129,7 @@ __global__ __launch_bounds__(kStatsThreads) void k_volume_histogram(const StatsP
         for (int i = 0; i < 8; ++i) {
             bool on = (inside >> i) & 1u;
             if constexpr (MASKED) {
-                const uint32_t l = ((i < 4 ? lab.x : lab.y) >> (8 * (i & 3))) & 255u;
+                const uint32_t l = byte_of(lab, i);
                 on = on && ((s_mask[l >> 5] >> (l & 31)) & 1u);
             }
             uint32_t bin = 0u;
@@ -191,7 +173,7 @@ __global__ __launch_bounds__(kStatsThreads) void k_volume_histogram(const StatsP
         }
         const BrickAt b = brick_at(p, k);
         if (b.whole) count_row(row, lab, 0xffu);
-        else count_row(row, lab, row_inside(p, b, lane));
+        else count_row(row, lab, row_in_box(p.box, b.bx, b.by * kBrick + (lane & 7), b.bz * kBrick + (lane >> 3)));
         row = next_row;
         lab = next_lab;
         k = kn;
@@ -249,7 +231,7 @@ __global__ __launch_bounds__(kStatsThreads) void k_label_statistics(const StatsP
     s_count[tid] = 0u; s_nan[tid] = 0u; s_min_inv[tid] = 0u; s_max[tid] = 0u; s_sum[tid] = Sum(0);
     __syncthreads();
 
-    const uint32_t total = (uint32_t) p.nb[0] * (uint32_t) p.nb[1] * (uint32_t) p.nb[2];
+    const uint32_t total = (uint32_t) range_bricks(p.range);
     const uint32_t stride = gridDim.x * kStatsWaves;
     // the registers of label `cur` (uniform over the wave; -1: none yet)
     int cur = -1;
@@ -297,7 +279,7 @@ __global__ __launch_bounds__(kStatsThreads) void k_label_statistics(const StatsP
             if constexpr (LABELS) next_lab = *reinterpret_cast<const uint2*>(p.labels + bn.first + (size_t) lane * 8);
         }
         const BrickAt b = brick_at(p, k);
-        const uint32_t inside = b.whole ? 0xffu : row_inside(p, b, lane);
+        const uint32_t inside = b.whole ? 0xffu : row_in_box(p.box, b.bx, b.by * kBrick + (lane & 7), b.bz * kBrick + (lane >> 3));
         int one_label = 0; // the brick's label when it holds one label only, else -1
         if constexpr (LABELS) {
             const uint32_t first = (uint32_t) __builtin_amdgcn_readfirstlane((int) (lab.x & 255u));
@@ -321,7 +303,7 @@ __global__ __launch_bounds__(kStatsThreads) void k_label_statistics(const StatsP
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 if (!((inside >> i) & 1u)) continue;
-                const uint32_t l = ((i < 4 ? lab.x : lab.y) >> (8 * (i & 3))) & 255u;
+                const uint32_t l = byte_of(lab, i);
                 const uint32_t c = row.code(i);
                 atomicAdd(&s_count[l], 1u);
                 if constexpr (FMT == FMT_F32) {
