@@ -7,8 +7,8 @@
 // pass only through INTEGERS: per block column / row / slice group the range of data texels its samples' base taps fall into
 // (texel_split of the block's first and last position + UVWOffset, tbrm_light_kernels.hip k_occ_flags). A light that turns by a
 // few degrees keeps those integers — UVWOffset stays within the same texel — so the lists are kept under that signature and a
-// pass that finds its signature launches nothing. The signature is evaluated here with the kernel's own fp32 sequence
-// (IEEE single operations, -ffp-contract=off on both sides).
+// pass that finds its signature launches nothing. The signature is evaluated here by the function k_occ_flags itself calls
+// (tbrm_occ_footprint.h pass_tap_span: IEEE single operations, -ffp-contract=off on both sides).
 #include "tbrm_resources.h"
 
 #include <algorithm>
@@ -19,52 +19,18 @@ namespace tbrm_host {
 
 using namespace tbrm;
 
-static constexpr int kBlock = 16, kDepth = 8; // kOccTile, kOccDepth (tbrm_light_kernels.hip)
 static constexpr size_t kMaxLists = 384;      // per handle (a reserved handle of eight lights starts with 240 spare ones); beyond: the least recently used ones nobody refers to go
 
-// texel_split (tbrm_device_math.h): the index of the lower tap
-static int base_tap(float u, float n)
-{
-    float x = u * n - 0.5f;
-    x = std::fmin(std::fmax(x, -0x1p30f), 0x1p30f);
-    return (int) std::floor(x);
-}
-
-// Everything k_occ_flags<MODE, AXIS> reads of a one-chunk pass besides ChunkParams::empty_bits, as integers: the geometry and,
+// Everything k_occ_flags<NS, AXIS> reads of a one-chunk pass besides ChunkParams::empty_bits, as integers: the geometry and,
 // per block column, block row and slice group, the lowest base tap and the highest upper tap over the streams the mode computes.
 static void block_lists_signature(const ChunkParams& p, int occ_mode, std::vector<int32_t>& sig)
 {
-    const int ns = (occ_mode == PASS_ADD || occ_mode == PASS_CHANGE_ONE) ? 1 : 2;
-    const int dim_u = p.axis == 0 ? 1 : 0, dim_v = p.axis == 2 ? 1 : 2, dim_s = p.axis;
-    const int dn[3] = {p.data.nx, p.data.ny, p.data.nz};
+    const OccPassShape s = occ_pass_shape(p, occ_mode_streams(occ_mode), 0);
     sig.clear();
-    for (int v : {ns, p.axis, p.W, p.H, p.dir, p.pass_start, p.pass_slices, p.chunk_slices, p.occ_groups, p.occ_blocks_x, p.occ_blocks_y, p.roi_by0,
-                  p.roi_by1, dn[0], dn[1], dn[2], p.data.bnx, p.data.bnxy, p.lv_dims[0], p.lv_dims[1], p.lv_dims[2]})
+    for (int v : {s.ns, p.axis, p.W, p.H, p.dir, p.pass_start, p.pass_slices, p.chunk_slices, p.occ_groups, p.occ_blocks_x, p.occ_blocks_y, p.roi_by0,
+                  p.roi_by1, p.data.nx, p.data.ny, p.data.nz, p.data.bnx, p.data.bnxy, p.lv_dims[0], p.lv_dims[1], p.lv_dims[2]})
         sig.push_back(v);
-    auto range = [&](int dim, int first, int last) {
-        int lo = INT32_MAX, hi = INT32_MIN;
-        for (int si = 0; si < ns; ++si) {
-            const ChunkStream& s = si == 0 ? p.a : p.r;
-            for (int pos : {first, last}) {
-                const float cc = (((float) (uint32_t) pos + 0.5f) / (float) (uint32_t) p.lv_dims[dim]) + s.uvw_off[dim];
-                const int i0 = base_tap(cc, (float) dn[dim]);
-                lo = std::min(lo, i0);
-                hi = std::max(hi, i0 + 1);
-            }
-        }
-        sig.push_back(lo);
-        sig.push_back(hi);
-    };
-    for (int bx = 0; bx < p.occ_blocks_x; ++bx) range(dim_u, bx * kBlock, std::min(bx * kBlock + kBlock, p.W) - 1);
-    for (int by = 0; by < p.occ_blocks_y; ++by) range(dim_v, by * kBlock, std::min(by * kBlock + kBlock, p.H) - 1);
-    const int n = std::min(p.chunk_slices, p.pass_slices);
-    for (int zg = 0; zg < p.occ_groups; ++zg) {
-        const int k0 = zg * kDepth;
-        if (k0 >= n) { sig.push_back(0); sig.push_back(-1); continue; } // (a group past the pass's last slice: never computed)
-        const int nk = std::min(kDepth, n - k0);
-        const int j0 = p.pass_start + k0 * p.dir, j1 = j0 + (nk - 1) * p.dir;
-        range(dim_s, j0, j1);
-    }
+    pass_tap_spans(s, [&](int lo, int hi) { sig.push_back(lo); sig.push_back(hi); });
 }
 
 static void free_lists(BlockLists* l)

@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tbrm_occ_footprint.h"
+
 namespace tbrm {
 
 __device__ __forceinline__ float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
@@ -165,16 +167,8 @@ __device__ __forceinline__ float quantize_u8(float x)
 }
 __device__ __forceinline__ uint32_t encode_u8(float x) { return (uint32_t) quantize_u8(x); }
 
-// Texel split of a normalised coordinate: floor/frac of u*N - 0.5 (clamped to +-2^30 so the conversion is defined).
-__device__ __forceinline__ void texel_split(float u, float n, int& i0, float& f)
-{
-    float x = u * n - 0.5f;
-    x = fminf(fmaxf(x, -0x1p30f), 0x1p30f);
-    const float fl = floorf(x);
-    i0 = (int) fl;
-    f = x - fl;
-}
-
+// texel_split (floor / frac of u * N - 0.5, clamped to +-2^30): tbrm_occ_footprint.h, one body for the kernels and the host's planners
+//
 // texel_split for a coordinate the caller knows to be finite and within +-2^30 texels (a sample position within a step of the unit
 // cube, a saturated coordinate): the clamp is dead there — the same bits without it
 __device__ __forceinline__ void texel_split_bounded(float u, float n, int& i0, float& f)

@@ -11,10 +11,7 @@
 
 namespace tbrm {
 
-// offset of voxel (x,y,z) in voxels: separable in x, y, z
-__device__ __forceinline__ uint32_t brick_off_x(int x) { return ((uint32_t) (x >> 3) << 9) | (uint32_t) (x & 7); }
-__device__ __forceinline__ uint32_t brick_off_y(int y, int bnx) { return ((uint32_t) ((y >> 3) * bnx) << 9) | ((uint32_t) (y & 7) << 3); }
-__device__ __forceinline__ uint32_t brick_off_z(int z, int bnxy) { return ((uint32_t) ((z >> 3) * bnxy) << 9) | ((uint32_t) (z & 7) << 6); }
+// offset of voxel (x,y,z) in voxels: separable in x, y, z (brick_off_x / _y / _z: tbrm_occ_footprint.h)
 __device__ __forceinline__ uint32_t brick_off(int x, int y, int z, int bnx, int bnxy)
 {
     return brick_off_x(x) + brick_off_y(y, bnx) + brick_off_z(z, bnxy);

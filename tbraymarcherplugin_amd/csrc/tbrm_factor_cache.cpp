@@ -181,7 +181,7 @@ int ensure_factor_scratch(tbrm_resources* r, int b, size_t blocks, int streams)
     }
     const size_t cap = std::max(blocks, f.store_blocks);
     for (int si = 0; si < streams; ++si)
-        if (!f.store[si]) HIP_TRY(hipMalloc((void**) &f.store[si], cap * 2048 * sizeof(float)));
+        if (!f.store[si]) HIP_TRY(hipMalloc((void**) &f.store[si], cap * kOccBlockFloats * sizeof(float)));
     f.store_blocks = cap;
     return TBRM_OK;
 }
@@ -259,7 +259,7 @@ static size_t kept_budget(const tbrm_resources* r)
 // allocates device memory, asks the device how much it has, or waits for a stream.
 FactorEntry* kept_new(tbrm_resources* r, const FactorKey& key, size_t want, BlockLists* lists)
 {
-    const size_t bytes = want * 2048 * sizeof(float);
+    const size_t bytes = want * kOccBlockFloats * sizeof(float);
     FactorEntry* e = nullptr;
     auto fits = [&](const FactorEntry* c) { return !c->pinned && c->cap_blocks >= want && c->cap_blocks <= want + want / 2 + 64; };
     auto useless = [&](const FactorEntry* c) { return (c->resolved && !c->valid) || c->spent || !c->enqueued; };
@@ -402,7 +402,7 @@ int reserve_resources(tbrm_resources* r, int n_lights, unsigned flags)
     // the factor cache's arena: per light two passes, twice (a light that moves fills new entries while the old ones are still read),
     // sized like an entry whose live-block count is not known yet (kept_new's caller: every block of a small pass, half of a large one)
     if (tune(TUNE_LIGHT_CACHE_MB) != 0) {
-        const size_t entry = (blocks * 2048 * sizeof(float) <= ((size_t) 256 << 20) ? blocks : blocks / 2) * 2048 * sizeof(float);
+        const size_t entry = (blocks * kOccBlockFloats * sizeof(float) <= ((size_t) 256 << 20) ? blocks : blocks / 2) * kOccBlockFloats * sizeof(float);
         size_t want = std::min(kept_budget(r), DeviceArena::rounded(entry) * (size_t) (4 * n_lights));
         size_t free_b = 0, total_b = 0;
         // never the last of the device's memory — whoever else allocates on it (a renderer, torch, other handles, the runtime's own

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "tbrm_brick_boards.h"
+#include "tbrm_occ_footprint.h"
 
 namespace tbrm {
 
@@ -85,8 +86,8 @@ struct ChunkStream {
     float* occ_next;        // occlusion launch: where the span's factors 1 - CurrentSample go, [span slices][H][W]
     // Block-compact hand-over of the occlusion factors (k_light_occlusion writes, k_light_sweep reads; ChunkParams::compact):
     // the live 16 x 16 x 8 block of rank k in the pass's ascending work list holds its factors as [slice 8][row 16][column 16]
-    // floats at fs_keep + 2048 k while k < fs_cap (a cache entry: tbrm_resources.h FactorEntry) and at
-    // fs_spill + 2048 (k - fs_cap) beyond (the handle's scratch store; fs_cap = 0: nothing is kept).
+    // floats where factor_block (tbrm_occ_footprint.h) says: at fs_keep + kOccBlockFloats k while k < fs_cap (a cache entry:
+    // tbrm_resources.h FactorEntry) and at fs_spill + kOccBlockFloats (k - fs_cap) beyond (the handle's scratch store; fs_cap = 0: nothing is kept).
     float* fs_keep;
     float* fs_spill;
     uint32_t fs_cap;
@@ -141,6 +142,22 @@ struct ChunkParams {
     const float* ones;            // sweep: 1024 floats of 1.0 (the factor of flagged-empty blocks and of pixels beyond the buffer)
     ChunkStream a, r;
 };
+
+// streams an occlusion launch of `mode` computes (PASS_CHANGE_ONE: one stream with the Change shader's rules)
+constexpr int occ_mode_streams(int mode) { return (mode == PASS_ADD || mode == PASS_CHANGE_ONE) ? 1 : 2; }
+// what the footprint rules (tbrm_occ_footprint.h) read of chunk c of a pass: k_occ_flags and the host's block-list signature (c = 0)
+__host__ __device__ __forceinline__ OccPassShape occ_pass_shape(const ChunkParams& p, int ns, int c)
+{
+    OccPassShape s;
+    s.axis = p.axis; s.W = p.W; s.H = p.H; s.dir = p.dir;
+    s.start = p.pass_start + c * p.chunk_slices * p.dir;
+    s.slices = p.chunk_slices < p.pass_slices - c * p.chunk_slices ? p.chunk_slices : p.pass_slices - c * p.chunk_slices;
+    s.blocks_x = p.occ_blocks_x; s.blocks_y = p.occ_blocks_y; s.groups = p.occ_groups;
+    s.data_dims[0] = p.data.nx; s.data_dims[1] = p.data.ny; s.data_dims[2] = p.data.nz;
+    s.ns = ns;
+    for (int a = 0; a < 3; ++a) { s.lv_dims[a] = p.lv_dims[a]; s.uvw_off[0][a] = p.a.uvw_off[a]; s.uvw_off[1][a] = p.r.uvw_off[a]; }
+    return s;
+}
 
 // The two axis passes of ONE light sample the data volume at the same positions: UVWOffset = normalize(lightPos) / min(TD)
 // whichever axis the pass runs along (LightingShaders.cpp:114-124) — only StepSize differs. A "dual" occlusion launch
@@ -369,7 +386,6 @@ struct RelayoutParams {
     int to_bricks; // 1: linear -> bricked (padding voxels are zeroed); 0: bricked -> linear
 };
 
-constexpr int kOccSlices = 8;      // slices per occlusion workgroup (kOccDepth in tbrm_light_kernels.hip)
 constexpr int kChunkTile = 32;      // core tile edge of the chunked propagation kernel (pixels)
 constexpr int kChunkThreads = 1024;
 constexpr int kChunkMaxHull = 64;   // T + steps * growth must stay within this

@@ -97,7 +97,7 @@ __global__ __launch_bounds__(kChunkThreads) void k_light_chain(const ChunkParams
                     if (si == 1 && flags == p.a.occ_flags) { st_one[NRP - 1][rd][0] = st_one[0][rd][0]; st_one[NRP - 1][rd][1] = st_one[0][rd][1]; continue; } // computed jointly
 #pragma unroll
                 for (int z = 0; z < 2; ++z) {
-                    bool one = x_last >= 0 && x_first < p.W && z * kOccSlices < p.occ_phase + g.n;
+                    bool one = x_last >= 0 && x_first < p.W && z * kOccDepth < p.occ_phase + g.n;
                     if (one) {
                         const uint8_t* frow = flags + (z * p.occ_blocks_y + by) * p.occ_blocks_x;
                         one = frow[bx0] != 0 && frow[bx1] != 0;
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(kChunkThreads) void k_light_chain(const ChunkParams
     // slice either way, which the vmcnt bookkeeping of the slice loop relies on).
     auto stage_occ = [&](int sf, int q) {
         if (sf >= g.n) return;
-        const int group = (p.occ_phase + sf) / kOccSlices;
+        const int group = (p.occ_phase + sf) / kOccDepth;
 #pragma unroll
         for (int rd = 0; rd < ROUNDS; ++rd) {
             if (!st_ok[rd]) continue;
@@ -372,7 +372,7 @@ __global__ __launch_bounds__(kChunkThreads) void k_light_chain(const ChunkParams
 #pragma unroll
                     for (int si = 0; si < NRP; ++si) {
                         const ChunkStream& st = si == 0 ? p.a : p.r;
-                        const bool one = st_adv[si][SF / kOccSlices] == 0u;
+                        const bool one = st_adv[si][SF / kOccDepth] == 0u;
                         const uint32_t off = one ? (uint32_t) lane * 4u : st_off[si] + (uint32_t) SF * (uint32_t) plane_elems;
                         dma_16(st.occ_base + off, ring(Q, si) + st_dst[0]);
                     }

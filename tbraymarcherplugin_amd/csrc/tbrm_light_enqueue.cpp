@@ -210,7 +210,7 @@ int enqueue_dual_occlusion(tbrm_resources* r, const PassPlan& pa, const PassPlan
     pc.pass_slices = pc.chunk_slices = pc.n_steps;
     pc.occ_blocks_x = ceil_div(pc.W, 16);
     pc.occ_blocks_y = ceil_div(pc.H, 16);
-    pc.occ_groups = ceil_div(pc.n_steps, kOccSlices);
+    pc.occ_groups = ceil_div(pc.n_steps, kOccDepth);
     pc.roi_by0 = 0;
     pc.roi_by1 = pc.occ_blocks_y;
     pc.compact = 1;
@@ -616,13 +616,13 @@ static int enqueue_plan_chunk_impl(tbrm_resources* r, const PassPlan& plan, int 
     p.a.plane_in = plan_plane(r, c, 0); p.a.plane_out = plan_plane(r, c + 1, 0);
     p.r.plane_in = plan_plane(r, c, 1); p.r.plane_out = plan_plane(r, c + 1, 1);
     ChunkStream* const streams[2] = {&p.a, &p.r};
-    const uint8_t* const chunk_flags = q.sparse ? fs->flags + (size_t) sp * plan.flags_per_span + (size_t) (k0 / kOccSlices) * plan.flags_per_group : nullptr;
+    const uint8_t* const chunk_flags = q.sparse ? fs->flags + (size_t) sp * plan.flags_per_span + (size_t) (k0 / kOccDepth) * plan.flags_per_group : nullptr;
     for (int si = 0; si < ns; ++si) {
         streams[si]->occ_base = r->occ_tmp[ob][si].base;
         streams[si]->occ_off = (uint32_t) (kPlaneGuard + (size_t) k0 * slice_elems);
         streams[si]->occ_flags = chunk_flags;
     }
-    p.occ_phase = k0 % kOccSlices;
+    p.occ_phase = k0 % kOccDepth;
     p.occ_list = nullptr;
     p.occ_count = nullptr;
     p.occ_flags = nullptr;

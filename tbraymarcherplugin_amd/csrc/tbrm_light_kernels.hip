@@ -60,9 +60,7 @@ __device__ __forceinline__ float propagate_stream(const PropParams& p, const Pro
     const float pv = (((float) (uint32_t) py + 0.5f) / (float) p.td[1]) + s.off_v;
     const float prev = sample_buffer_bilinear<LFMT>(s.read, p.td[0], p.td[1], pu, pv, s.border_light);
 
-    const float u = (((float) (uint32_t) pos[0] + 0.5f) / (float) (uint32_t) p.lv_dims[0]) + s.uvw_off[0];
-    const float v = (((float) (uint32_t) pos[1] + 0.5f) / (float) (uint32_t) p.lv_dims[1]) + s.uvw_off[1];
-    const float w = (((float) (uint32_t) pos[2] + 0.5f) / (float) (uint32_t) p.lv_dims[2]) + s.uvw_off[2];
+    const float u = sample_coord(pos[0], p.lv_dims[0], s.uvw_off[0]), v = sample_coord(pos[1], p.lv_dims[1], s.uvw_off[1]), w = sample_coord(pos[2], p.lv_dims[2], s.uvw_off[2]);
 
     const float aw = p.clip_mode ? clip_alpha_weight(u, v, w, p.cc, p.cd, p.lv_dims) : 1.0f;
     float cur = 0.0f;
@@ -151,10 +149,8 @@ size_t chunk_lds_bytes(const ChunkParams& p, int mode, int lv_fmt)
 // path handles ~one 64-lane gather per 20 cycles) become LDS reads. Addressing is separable in the bricked layout:
 // the two in-plane axes contribute per-thread constants, the slice axis a per-step value from a small LDS table
 // (which also carries the reference's per-thread (Loop+0.5)/res division out of the loop).
-constexpr int kOccTile = 16;  // pixels per side
-constexpr int kOccMaxBricks = 192; // staged bricks per workgroup (96 KiB of UNORM8 bricks)
-constexpr int kOccDepth = 8;  // slices per workgroup (16 was measured: fewer halo bricks per sample, but no faster)
-static_assert(kOccDepth == kOccSlices, "host and kernel disagree on the occlusion workgroup depth");
+// The unit's size, the sample coordinate, tap spans, brick ranges, the staging decision and the staged block's layout are
+// tbrm_occ_footprint.h's; the pieces of the sample loop that the kernel's forms share follow here.
 
 struct AxisTaps {        // one axis of a trilinear footprint with border addressing
     int i0;              // base tap index (unclamped)
@@ -171,16 +167,6 @@ __device__ __forceinline__ AxisTaps axis_taps(float coord, int n)
     return t;
 }
 
-// offset (in voxels) of coordinate c along `axis` inside the staged brick block: local brick index * 512 + in-brick part
-template <int AXIS>
-__device__ __forceinline__ uint32_t staged_off(int c, const int* b0, const int* nb)
-{
-    const int lb = (c >> 3) - b0[AXIS];
-    const uint32_t stride = AXIS == 0 ? 1u : (AXIS == 1 ? (uint32_t) nb[0] : (uint32_t) (nb[0] * nb[1]));
-    const uint32_t inb = (uint32_t) (c & 7) << (3 * AXIS);
-    return (uint32_t) lb * stride * 512u + inb;
-}
-
 template <int FMT>
 __device__ __forceinline__ float lds_voxel(const void* p, uint32_t i)
 {
@@ -189,19 +175,110 @@ __device__ __forceinline__ float lds_voxel(const void* p, uint32_t i)
     else return ((const float*) p)[i];
 }
 
+constexpr int fmt_bytes(int fmt) { return fmt == FMT_U8 ? 1 : (fmt == FMT_U16 ? 2 : 4); }
+
 // LDS bytes for the staged bricks: worst case over workgroups, from the ratio of data to light-volume resolution
 size_t occlusion_lds_bytes(const ChunkParams& p)
 {
-    const int dim_u = p.axis == 0 ? 1 : 0, dim_v = p.axis == 2 ? 1 : 2, dim_s = p.axis;
     const int dd[3] = {p.data.nx, p.data.ny, p.data.nz};
-    auto bricks = [&](int pixels, int dim) {
-        const double ratio = (double) dd[dim] / (double) p.lv_dims[dim];
-        const int texels = (int) ((pixels - 1) * ratio) + 2; // first base tap .. last +1 tap (a workgroup that needs one
-        return (texels - 1 + 7) / 8 + 1;                     // more brick than this reads its taps from global memory)
-    };
-    const size_t n = (size_t) bricks(kOccTile, dim_u) * bricks(kOccTile, dim_v) * bricks(kOccDepth, dim_s);
-    const size_t esz = p.data.fmt == FMT_U8 ? 1 : (p.data.fmt == FMT_U16 ? 2 : 4);
-    return n * 512 * esz;
+    return occ_lds_estimate(dd, p.lv_dims, p.axis, fmt_bytes(p.data.fmt));
+}
+
+// ---- the pieces of the sample loop that k_light_occlusion and k_light_occlusion_runs share ---------------------------------------
+// the transfer function's alpha as pairs (alpha[clamp(i)], alpha[clamp(i + 1)]) at i + 1 (sample_tf_alpha), one texel per thread
+__device__ __forceinline__ void fill_alpha_pairs(float2 (&s_alpha)[257], const float4* tf)
+{
+    const float a_t = tf[threadIdx.x].w, a_n = tf[min((int) threadIdx.x + 1, 255)].w;
+    s_alpha[threadIdx.x + 1] = make_float2(a_t, a_n);
+    if (threadIdx.x == 0) s_alpha[0] = make_float2(a_t, a_t);
+}
+
+// What a slice contributes to each of its samples (wave-uniform): the slice-axis coordinate, its texel split and
+// flags: bit0 tap0 in range, bit1 tap1 in range, bit2 w == saturate(w)
+struct OccSliceEntry {
+    float w, f;
+    int i0, flags;
+};
+__device__ __forceinline__ OccSliceEntry occ_slice_entry(int j, int lv_dim, float uvw_off, int data_dim)
+{
+    OccSliceEntry e;
+    e.w = sample_coord(j, lv_dim, uvw_off);
+    const AxisTaps t = axis_taps(e.w, data_dim);
+    e.f = t.f;
+    e.i0 = t.i0;
+    e.flags = (t.ok0 ? 1 : 0) | (t.ok1 ? 2 : 0) | ((e.w == saturate_(e.w)) ? 4 : 0);
+    return e;
+}
+
+// one tap: from the staged block in LDS or the bricked volume; outside the volume (never, in an INTERIOR unit) the border colour
+template <int DFMT, bool STAGED, bool INTERIOR>
+__device__ __forceinline__ float occ_tap(const char* smem, const void* data, uint32_t off, bool ok, float border)
+{
+    if constexpr (INTERIOR) return STAGED ? lds_voxel<DFMT>(smem, off) : load_voxel<DFMT>(data, off);
+    else return ok ? (STAGED ? lds_voxel<DFMT>(smem, off) : load_voxel<DFMT>(data, off)) : border;
+}
+
+// The sample loop is specialised on workgroup-uniform facts so that the common case carries no dead branches:
+//   STAGED   taps come from LDS (else from global memory: a workgroup whose bricks did not fit)
+//   INTERIOR every tap of every sample lies inside the volume (no border-colour selects)
+//   CLIP     the clip plane can change a sample's weight (else AlphaWeight is exactly 1)
+//   NONNEG   the opacity correction's step sizes are >= 0 (they are unless the host was handed garbage)
+// f(STAGED, INTERIOR, CLIP, NONNEG) is called with the form's constants. NONNEG is decided once per unit over all its streams' step
+// sizes (the NONNEG = false forms compute the same bits for steps >= 0, so a stream that alone would qualify loses nothing but time).
+template <class NN, class F>
+__device__ __forceinline__ void occ_forms_of(bool staged, bool interior, bool clip, NN nonneg_c, F& f)
+{
+    using T_ = std::true_type; using F_ = std::false_type;
+    if (staged && interior && !clip) f(T_{}, T_{}, F_{}, nonneg_c); // the common case
+    else if (staged && !clip) f(T_{}, F_{}, F_{}, nonneg_c);         // shell of the volume
+    else if (staged) f(T_{}, F_{}, T_{}, nonneg_c);                  // clip plane active
+    else f(F_{}, F_{}, T_{}, nonneg_c);                              // bricks did not fit in LDS
+}
+template <class F>
+__device__ __forceinline__ void occ_forms(bool staged, bool interior, bool clip, bool nonneg, F& f)
+{
+    if (nonneg) occ_forms_of(staged, interior, clip, std::true_type{}, f);
+    else occ_forms_of(staged, interior, clip, std::false_type{}, f);
+}
+
+// The held-plane window. A texel plane of the footprint is the taps at one slice-axis coordinate, reduced as far as the filter
+// order (x, then y, then z) allows before the slice-axis weight is applied (P: 1, 2 or 4 values). Consecutive slices of a pass
+// usually sample consecutive texel planes, so the +1 plane of one step is the base plane of the next: `lo` (texel index `held`)
+// and `hi` (the plane after it) are kept in registers and only one new plane is fetched per step instead of two. i is wave-uniform:
+// scalar branches. fetch(upper) fetches the plane at i (false) or i + 1 (true).
+template <class P, class Fetch>
+__device__ __forceinline__ void held_planes_step(P& lo, P& hi, int& held, int i, Fetch&& fetch)
+{
+    if (i == held + 1) { lo = hi; hi = fetch(true); }
+    else if (i == held - 1) { hi = lo; lo = fetch(false); }
+    else if (i != held) { lo = fetch(false); hi = fetch(true); }
+    held = i;
+}
+constexpr int kNoPlaneHeld = INT32_MIN / 2;
+
+// One sample: clip weight (c0 .. c2: its coordinate in the volume's axis order), the Add shader's guard, the windowed and
+// opacity-corrected alpha of value() for one step size (occ0) or two (DUAL: occ0, occ1), times the weight.
+template <int DFMT, bool CLIP, bool NONNEG, bool DUAL, class V>
+__device__ __forceinline__ void occ_sample(const ChunkParams& p, float c0, float c1, float c2, bool inside, V&& value, float step0, float step1, const float2* s_alpha, float& occ0, float& occ1)
+{
+    float aw = 1.0f;
+    if constexpr (CLIP) aw = clip_alpha_weight(c0, c1, c2, p.cc, p.cd, p.lv_dims);
+    occ0 = 0.0f;
+    occ1 = 0.0f;
+    if (aw > 0.0f && inside) {
+        if constexpr (DUAL) {
+            windowed_alpha2<DFMT != FMT_F32, NONNEG>(value(), step0, step1, s_alpha, p.win, occ0, occ1);
+            occ0 = occ0 * aw;
+            occ1 = occ1 * aw;
+        } else occ0 = windowed_alpha<DFMT != FMT_F32, NONNEG>(value(), step0, s_alpha, p.win) * aw;
+    }
+}
+
+// slice q's factors of a dual launch into the two passes' blocks (null: block flagged empty)
+__device__ __forceinline__ void dual_store(float* const* out2, const int* step, int q, float occ0, float occ1)
+{
+    if (out2[0]) out2[0][q * step[0]] = 1 - occ0;
+    if (out2[1]) out2[1][q * step[1]] = 1 - occ1;
 }
 
 // ---- k_occ_flags: once per pass, which occlusion workgroups are empty ---------------------------------------------
@@ -209,57 +286,35 @@ size_t occlusion_lds_bytes(const ChunkParams& p)
 // every sample's base tap has its k_brick_empty bit set: the bit vouches for every value the 8 taps of a sample based
 // in that brick can take (the brick plus its +1 apron), so every CurrentSample is exactly 0. Workgroups with taps
 // outside the volume are never flagged (a blend with the sampler's border colour can leave both value ranges).
-template <int MODE, int AXIS>
+template <int NS, int AXIS>
 __global__ __launch_bounds__(256) void k_occ_flags(const ChunkParams p, int n_chunks)
 {
-    constexpr int NS = MODE != PASS_ADD ? 2 : 1;
-    constexpr int dim_u = AXIS == 0 ? 1 : 0, dim_v = AXIS == 2 ? 1 : 2, dim_s = AXIS;
     const int per_chunk = p.occ_groups * p.occ_blocks_y * p.occ_blocks_x;
     const int id = blockIdx.x * 256 + threadIdx.x;
     if (id >= n_chunks * per_chunk) return;
     const int c = id / per_chunk, rem = id % per_chunk;
     const int bx = rem % p.occ_blocks_x, by = (rem / p.occ_blocks_x) % p.occ_blocks_y, zg = rem / (p.occ_blocks_x * p.occ_blocks_y);
-    const int n = min(p.chunk_slices, p.pass_slices - c * p.chunk_slices);
-    const int k0 = zg * kOccDepth;
     uint8_t flag = 0;
     if (by < p.roi_by0 || by >= p.roi_by1) flag = 1; // outside the slab's reach: never computed, never read
-    else if (k0 < n) {
-        const int nk = min(kOccDepth, n - k0);
-        const int j0 = p.pass_start + (c * p.chunk_slices + k0) * p.dir, j1 = j0 + (nk - 1) * p.dir;
-        const int px0 = bx * kOccTile, py0 = by * kOccTile;
-        const int pxl = min(px0 + kOccTile, p.W) - 1, pyl = min(py0 + kOccTile, p.H) - 1;
-        const int dn[3] = {p.data.nx, p.data.ny, p.data.nz};
+    else {
+        OccPassShape s = occ_pass_shape(p, NS, c);
+        s.axis = AXIS;
         const int bn[3] = {p.data.bnx, p.data.bnxy / p.data.bnx, (p.data.nz + 7) >> 3};
-        int lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
+        constexpr int dims[3] = {AXIS == 0 ? 1 : 0, AXIS == 2 ? 1 : 2, AXIS}; // plane axes, slice axis -> volume axes
+        const int index[3] = {bx, by, zg};
+        bool ok = true; // every tap inside the volume (and the group not past the chunk's last slice)
+        int b0[3], nb[3];
 #pragma unroll
-        for (int si = 0; si < NS; ++si) {
-            const ChunkStream& s = si == 0 ? p.a : p.r;
-            const int ends[3][2] = {{px0, pxl}, {py0, pyl}, {j0, j1}};
-            constexpr int dims[3] = {dim_u, dim_v, dim_s};
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    const float cc = (((float) (uint32_t) ends[a][e] + 0.5f) / (float) (uint32_t) p.lv_dims[dims[a]]) + s.uvw_off[dims[a]];
-                    int i0;
-                    float f;
-                    texel_split(cc, (float) dn[dims[a]], i0, f);
-                    lo[dims[a]] = min(lo[dims[a]], i0);
-                    hi[dims[a]] = max(hi[dims[a]], i0 + 1);
-                }
-        }
-        bool ok = true;
-        int b_lo[3], b_hi[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            ok = ok && lo[a] >= 0 && hi[a] < dn[a]; // every tap inside the volume
-            b_lo[a] = max(lo[a] >> 3, 0);
-            b_hi[a] = min(hi[a] >> 3, bn[a] - 1);
+        for (int part = 0; part < 3; ++part) {
+            int lo, hi;
+            bool border = true;
+            if (pass_tap_span(s, part, index[part], lo, hi)) brick_span(lo, hi, s.data_dims[dims[part]], bn[dims[part]], b0[dims[part]], nb[dims[part]], border);
+            ok = ok && !border;
         }
         if (ok) {
-            for (int z = b_lo[2]; z <= b_hi[2] && ok; ++z)
-                for (int y = b_lo[1]; y <= b_hi[1] && ok; ++y)
-                    for (int x = b_lo[0]; x <= b_hi[0]; ++x) {
+            for (int z = b0[2]; z < b0[2] + nb[2] && ok; ++z)
+                for (int y = b0[1]; y < b0[1] + nb[1] && ok; ++y)
+                    for (int x = b0[0]; x < b0[0] + nb[0]; ++x) {
                         const int b = z * p.data.bnxy + y * p.data.bnx + x;
                         if (!((p.empty_bits[b >> 5] >> (b & 31)) & 1u)) { ok = false; break; }
                     }
@@ -349,14 +404,14 @@ __global__ __launch_bounds__(256) void k_occ_compact(const ChunkParams p, int se
     }
 }
 
-template <int MODE>
+template <int NS> // (flags only depend on the stream count)
 static hipError_t launch_flags2(const ChunkParams& p, int n_chunks, hipStream_t s)
 {
     const int total = n_chunks * p.occ_groups * p.occ_blocks_y * p.occ_blocks_x;
     const dim3 grid((total + 255) / 256), block(256);
-    if (p.axis == 0) hipLaunchKernelGGL((k_occ_flags<MODE, 0>), grid, block, 0, s, p, n_chunks);
-    else if (p.axis == 1) hipLaunchKernelGGL((k_occ_flags<MODE, 1>), grid, block, 0, s, p, n_chunks);
-    else hipLaunchKernelGGL((k_occ_flags<MODE, 2>), grid, block, 0, s, p, n_chunks);
+    if (p.axis == 0) hipLaunchKernelGGL((k_occ_flags<NS, 0>), grid, block, 0, s, p, n_chunks);
+    else if (p.axis == 1) hipLaunchKernelGGL((k_occ_flags<NS, 1>), grid, block, 0, s, p, n_chunks);
+    else hipLaunchKernelGGL((k_occ_flags<NS, 2>), grid, block, 0, s, p, n_chunks);
     if (p.occ_list_out) {
         const int per_chunk = p.occ_groups * p.occ_blocks_y * p.occ_blocks_x, segs = (per_chunk + kCompactSeg - 1) / kCompactSeg;
         hipLaunchKernelGGL(k_occ_compact, dim3(n_chunks * segs), dim3(256), 0, s, p, segs);
@@ -365,8 +420,7 @@ static hipError_t launch_flags2(const ChunkParams& p, int n_chunks, hipStream_t 
 }
 hipError_t launch_occ_flags(const ChunkParams& p, int mode, int n_chunks, hipStream_t s)
 {
-    const bool one = mode == PASS_ADD || mode == PASS_CHANGE_ONE;
-    return one ? launch_flags2<PASS_ADD>(p, n_chunks, s) : launch_flags2<PASS_CHANGE>(p, n_chunks, s); // flags only depend on the stream count
+    return occ_mode_streams(mode) == 1 ? launch_flags2<1>(p, n_chunks, s) : launch_flags2<2>(p, n_chunks, s);
 }
 
 // DUAL (tbrm_internal.h DualOcc): the launch walks the light volume as a virtual pass along AXIS (z: see DualOcc) and every
@@ -378,12 +432,12 @@ template <int DFMT, int MODE, int AXIS, bool DUAL = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TBRM_OCC_WAVES_PER_EU, 8))) void k_light_occlusion(const ChunkParams p, int lds_budget_bytes, const DualOcc d)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int NS = (MODE == PASS_ADD || MODE == PASS_CHANGE_ONE) ? 1 : 2; // PASS_CHANGE_ONE: one stream with the Change shader's rules
+    constexpr int NS = occ_mode_streams(MODE);
     constexpr bool GUARD = MODE == PASS_ADD || MODE == PASS_ADD2; // all(uvw == saturate(uvw)): the Add shader only (AddDirLightShader.usf:98)
-    constexpr int ESZ = DFMT == FMT_U8 ? 1 : (DFMT == FMT_U16 ? 2 : 4);
-    __shared__ float2 s_alpha[257]; // pairs (alpha[clamp(i)], alpha[clamp(i + 1)]) at i + 1: sample_tf_alpha
-    __shared__ float s_w[2][kOccDepth], s_f[2][kOccDepth];
-    __shared__ int s_i[2][kOccDepth], s_flags[2][kOccDepth]; // flags: bit0 tap0 in range, bit1 tap1 in range, bit2 w == saturate(w)
+    constexpr int ESZ = fmt_bytes(DFMT);
+    __shared__ float2 s_alpha[257];
+    __shared__ float s_w[2][kOccDepth], s_f[2][kOccDepth]; // the slice-table entries (OccSliceEntry), [stream][slice]
+    __shared__ int s_i[2][kOccDepth], s_flags[2][kOccDepth];
     __shared__ int s_b0[3], s_nb[3], s_staged, s_interior;
     __shared__ uint32_t s_o0[2][kOccDepth], s_o1[2][kOccDepth];
     __shared__ int s_ends[12], s_end_dim[12];
@@ -416,58 +470,50 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TBRM_OCC_WA
     const int px0 = gx * kOccTile, py0 = gy * kOccTile, k0 = gz * kOccDepth;
     const int nk = min(kOccDepth, p.n_steps - k0);
 
-    {
-        const float a_t = p.tf[threadIdx.x].w, a_n = p.tf[min((int) threadIdx.x + 1, 255)].w;
-        s_alpha[threadIdx.x + 1] = make_float2(a_t, a_n);
-        if (threadIdx.x == 0) s_alpha[0] = make_float2(a_t, a_t);
-    }
+    fill_alpha_pairs(s_alpha, p.tf);
     if (threadIdx.x < NS * kOccDepth) { // slice-axis taps of each step of this workgroup (wave-uniform values)
         const int si = threadIdx.x / kOccDepth, q = threadIdx.x % kOccDepth;
         const ChunkStream& s = si == 0 ? p.a : p.r;
-        const int j = p.j0 + min(k0 + q, p.n_steps - 1) * p.dir;
-        const float w = (((float) (uint32_t) j + 0.5f) / (float) (uint32_t) p.lv_dims[dim_s]) + s.uvw_off[dim_s];
-        const AxisTaps t = axis_taps(w, data_dims[dim_s]);
-        s_w[si][q] = w; s_f[si][q] = t.f; s_i[si][q] = t.i0;
-        s_flags[si][q] = (t.ok0 ? 1 : 0) | (t.ok1 ? 2 : 0) | ((w == saturate_(w)) ? 4 : 0);
+        const OccSliceEntry e = occ_slice_entry(p.j0 + min(k0 + q, p.n_steps - 1) * p.dir, p.lv_dims[dim_s], s.uvw_off[dim_s], data_dims[dim_s]);
+        s_w[si][q] = e.w; s_f[si][q] = e.f; s_i[si][q] = e.i0; s_flags[si][q] = e.flags;
     }
-    if (threadIdx.x >= 64 && threadIdx.x < 64 + NS * 6) { // tap range of the first / last pixel and slice, one lane each
+    if (threadIdx.x >= 64 && threadIdx.x < 64 + NS * 6) { // base tap of the first / last pixel and slice, one lane each
         const int t = threadIdx.x - 64, si = t / 6, a = (t % 6) >> 1, e = t & 1;
         const ChunkStream& s = si == 0 ? p.a : p.r;
-        const int pxl = min(px0 + kOccTile, p.W) - 1, pyl = min(py0 + kOccTile, p.H) - 1;
-        const int end = a == 0 ? (e ? pxl : px0) : (a == 1 ? (e ? pyl : py0) : p.j0 + (e ? k0 + nk - 1 : k0) * p.dir);
+        int first, last;
+        if (a == 0) block_ends(gx, p.W, first, last);
+        else if (a == 1) block_ends(gy, p.H, first, last);
+        else group_ends(k0, p.n_steps, p.j0, p.dir, first, last);
         const int dim = a == 0 ? dim_u : (a == 1 ? dim_v : dim_s);
         const int lvd = dim == 0 ? p.lv_dims[0] : (dim == 1 ? p.lv_dims[1] : p.lv_dims[2]);
         const float off = dim == 0 ? s.uvw_off[0] : (dim == 1 ? s.uvw_off[1] : s.uvw_off[2]);
         const int dd = dim == 0 ? p.data.nx : (dim == 1 ? p.data.ny : p.data.nz);
-        const float c = (((float) (uint32_t) end + 0.5f) / (float) (uint32_t) lvd) + off;
-        int i0;
-        float f;
-        texel_split(c, (float) dd, i0, f);
-        s_ends[t] = i0;
+        s_ends[t] = base_tap(sample_coord(e ? last : first, lvd, off), (float) dd);
         s_end_dim[t] = dim;
     }
     __syncthreads();
     if (threadIdx.x == 0) { // brick range the workgroup's samples can touch (union over the streams)
         int lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
         for (int t = 0; t < NS * 6; ++t) {
-            const int d = s_end_dim[t], i0 = s_ends[t];
-            if (d == 0) { lo[0] = min(lo[0], i0); hi[0] = max(hi[0], i0 + 1); }
-            else if (d == 1) { lo[1] = min(lo[1], i0); hi[1] = max(hi[1], i0 + 1); }
-            else { lo[2] = min(lo[2], i0); hi[2] = max(hi[2], i0 + 1); }
+            const int dm = s_end_dim[t], i0 = s_ends[t];
+            if (dm == 0) tap_span_add(i0, lo[0], hi[0]);
+            else if (dm == 1) tap_span_add(i0, lo[1], hi[1]);
+            else tap_span_add(i0, lo[2], hi[2]);
         }
         const int bn[3] = {p.data.bnx, p.data.bnxy / p.data.bnx, (p.data.nz + 7) >> 3};
-        const int dn[3] = {p.data.nx, p.data.ny, p.data.nz};
         int count = 1;
         bool touches_border = false;
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
-            const int b_lo = max(lo[a] >> 3, 0), b_hi = min(hi[a] >> 3, bn[a] - 1);
-            s_b0[a] = b_lo;
-            s_nb[a] = max(b_hi - b_lo + 1, 0);
-            count *= s_nb[a];
-            touches_border = touches_border || lo[a] < 0 || hi[a] >= dn[a];
+            int b0a, nba;
+            bool border;
+            brick_span(lo[a], hi[a], data_dims[a], bn[a], b0a, nba, border);
+            s_b0[a] = b0a;
+            s_nb[a] = nba;
+            count *= nba;
+            touches_border = touches_border || border;
         }
-        s_staged = (count > 0 && count <= kOccMaxBricks && count * 512 * ESZ <= lds_budget_bytes) ? 1 : 0; // else: read taps from global memory
+        s_staged = bricks_staged(count, ESZ, lds_budget_bytes) ? 1 : 0;
         s_interior = touches_border ? 0 : 1;
     }
     __syncthreads();
@@ -475,35 +521,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TBRM_OCC_WA
     const bool staged = s_staged != 0;
     const int b0[3] = {s_b0[0], s_b0[1], s_b0[2]}, nb[3] = {s_nb[0], s_nb[1], s_nb[2]};
     if (staged) { // copy the bricks: 512*ESZ bytes each, 16 bytes per lane
-        constexpr int PIECES = 512 * ESZ / 16; // a power of two
+        constexpr int PIECES = kBrickVoxels * ESZ / 16; // a power of two
         const int bricks = nb[0] * nb[1] * nb[2];
         // global index of every staged brick, once (the integer divisions stay out of the copy loop)
         if ((int) threadIdx.x < bricks) {
-            const int lb = threadIdx.x;
-            const int lx = lb % nb[0], ly = (lb / nb[0]) % nb[1], lz = lb / (nb[0] * nb[1]);
-            s_brick[lb] = (uint32_t) ((b0[2] + lz) * p.data.bnxy + (b0[1] + ly) * p.data.bnx + (b0[0] + lx));
+            const int lb = threadIdx.x, nxy = nb[0] * nb[1];
+            s_brick[lb] = staged_brick_xy(lb % nxy, b0[0], b0[1], nb[0], p.data.bnx) + staged_brick_z(lb / nxy, b0[2], p.data.bnxy);
         }
         __syncthreads();
         const int total = bricks * PIECES;
         const int wave_base = (threadIdx.x >> 6) * 64, lane = threadIdx.x & 63;
         for (int cb = wave_base; cb < total; cb += 256) {
             const int c = cb + lane;
-            if (c < total) {
-                const uint32_t gb = s_brick[c / PIECES];
-                dma_16((const char*) p.data.data + ((size_t) gb * 512 * ESZ + (size_t) (c % PIECES) * 16), smem + (size_t) cb * 16);
-            }
+            if (c < total) dma_16((const char*) p.data.data + staged_piece_src(s_brick[c / PIECES], c, PIECES, ESZ), smem + (size_t) cb * 16);
         }
     }
 
-    // offset of voxel coordinate c along axis A: in the staged block, or in the bricked global volume
+    // offset of voxel coordinate c along an axis: in the staged block, or in the bricked global volume
     auto voff = [&](int c, auto axis_c) -> uint32_t {
         constexpr int axis = decltype(axis_c)::value;
-        const int n = data_dims[axis];
-        c = min(max(c, 0), n - 1); // clamped: out-of-range taps are replaced by the border colour after the load
-        if (staged) {
-            const int cb = min(max(c >> 3, b0[axis]), b0[axis] + nb[axis] - 1); // stay inside the staged block
-            return staged_off<axis>((cb << 3) | (c & 7), b0, nb);
-        }
+        c = tap_coord(c, data_dims[axis]);
+        if (staged) return staged_off<axis>(c, b0[axis], nb[axis], axis == 0 ? 1u : (axis == 1 ? (uint32_t) nb[0] : (uint32_t) (nb[0] * nb[1])));
         return axis == 0 ? brick_off_x(c) : (axis == 1 ? brick_off_y(c, p.data.bnx) : brick_off_z(c, p.data.bnxy));
     };
     using AU = std::integral_constant<int, dim_u>; using AV = std::integral_constant<int, dim_v>; using AS = std::integral_constant<int, dim_s>;
@@ -522,23 +560,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TBRM_OCC_WA
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
-    // the sample loop, specialised on workgroup-uniform facts so the common case carries no dead branches:
-    //   STAGED   taps come from LDS (else from global memory: a workgroup whose bricks did not fit)
-    //   INTERIOR every tap of every sample lies inside the volume (no border-colour selects)
-    //   CLIP     the clip plane can change a sample's weight (else AlphaWeight is exactly 1)
-    auto run = [&](auto staged_c, auto interior_c, auto clip_c) {
-        constexpr bool STAGED = decltype(staged_c)::value, INTERIOR = decltype(interior_c)::value, CLIP = decltype(clip_c)::value;
+    auto run = [&](auto staged_c, auto interior_c, auto clip_c, auto nonneg_c) {
+        constexpr bool STAGED = decltype(staged_c)::value, INTERIOR = decltype(interior_c)::value, CLIP = decltype(clip_c)::value, NONNEG = decltype(nonneg_c)::value;
         const float border = p.data_border;
-        auto tap = [&](uint32_t off, bool ok) -> float {
-            if constexpr (INTERIOR) return STAGED ? lds_voxel<DFMT>(smem, off) : load_voxel<DFMT>(p.data.data, off);
-            else return ok ? (STAGED ? lds_voxel<DFMT>(smem, off) : load_voxel<DFMT>(p.data.data, off)) : border;
-        };
+        auto tap = [&](uint32_t off, bool ok) -> float { return occ_tap<DFMT, STAGED, INTERIOR>(smem, p.data.data, off, ok, border); };
 #pragma unroll
         for (int si = 0; si < NS; ++si) {
             const ChunkStream& s = si == 0 ? p.a : p.r;
-            // GetUVW(pos, res) + UVWOffset (AddDirLightShader.usf:85): the two in-plane components
-            const float u = (((float) (uint32_t) px + 0.5f) / (float) (uint32_t) p.lv_dims[dim_u]) + s.uvw_off[dim_u];
-            const float v = (((float) (uint32_t) py + 0.5f) / (float) (uint32_t) p.lv_dims[dim_v]) + s.uvw_off[dim_v];
+            const float u = sample_coord(px, p.lv_dims[dim_u], s.uvw_off[dim_u]), v = sample_coord(py, p.lv_dims[dim_v], s.uvw_off[dim_v]);
             const AxisTaps tu = axis_taps(u, data_dims[dim_u]), tv = axis_taps(v, data_dims[dim_v]);
             const bool guard_uv = (u == saturate_(u)) && (v == saturate_(v));
             const uint32_t u0 = voff(tu.i0, AU{}), u1 = voff(tu.i0 + 1, AU{}), v0 = voff(tv.i0, AV{}), v1 = voff(tv.i0 + 1, AV{});
@@ -560,27 +589,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TBRM_OCC_WA
                     const int pu = P.axis == 0 ? pos[1] : pos[0], pv = P.axis == 2 ? pos[1] : pos[2]; // the pass's plane coordinates
                     const int ks = (pa - P.start) * P.dir;                                              // its slice
                     const int32_t rank = P.fs_slot[((ks >> 3) * P.blocks_y + (pv >> 4)) * P.blocks_x + (pu >> 4)];
-                    if (rank >= 0) {
-                        float* const blk_base = (uint32_t) rank < P.fs_cap[si] ? P.fs_keep[si] + (size_t) (uint32_t) rank * 2048 : P.fs_spill[si] + (size_t) ((uint32_t) rank - P.fs_cap[si]) * 2048;
-                        out2[k] = blk_base + (ks & 7) * 256 + (pv & 15) * 16 + (pu & 15);
+                    if (rank >= 0) { // (factor_block, spelled out: tbrm_occ_footprint.h says why)
+                        float* const blk_base = (uint32_t) rank < P.fs_cap[si] ? P.fs_keep[si] + (size_t) (uint32_t) rank * kOccBlockFloats : P.fs_spill[si] + (size_t) ((uint32_t) rank - P.fs_cap[si]) * kOccBlockFloats;
+                        out2[k] = blk_base + (ks & 7) * kOccSliceFloats + (pv & 15) * kOccTile + (pu & 15);
                     }
-                    // one step along the launch's loop axis, in pass k's block: its own slice axis (a block slice is 256 floats), its
-                    // columns, or its rows
-                    out2_step[k] = (dim_s == P.axis ? 256 * P.dir : (dim_s == (P.axis == 0 ? 1 : 0) ? 1 : kOccTile)) * p.dir;
+                    // one step along the launch's loop axis, in pass k's block: its own slice axis, its columns, or its rows
+                    out2_step[k] = (dim_s == P.axis ? kOccSliceFloats * P.dir : (dim_s == (P.axis == 0 ? 1 : 0) ? 1 : kOccTile)) * p.dir;
                 }
             } else {
                 out = s.occ_next + k0 * plane_elems + py * p.W + px;
                 out_step = plane_elems;
-                if (p.compact) {
-                    float* const blk_base = (uint32_t) entry < s.fs_cap ? s.fs_keep + (size_t) entry * 2048 : s.fs_spill + (size_t) ((uint32_t) entry - s.fs_cap) * 2048;
+                if (p.compact) { // (factor_block, spelled out)
+                    float* const blk_base = (uint32_t) entry < s.fs_cap ? s.fs_keep + (size_t) entry * kOccBlockFloats : s.fs_spill + (size_t) ((uint32_t) entry - s.fs_cap) * kOccBlockFloats;
                     out = blk_base + (py - py0) * kOccTile + (px - px0);
-                    out_step = kOccTile * kOccTile;
+                    out_step = kOccSliceFloats;
                 }
             }
-            // One texel plane of the footprint (4 taps at one slice-axis coordinate), reduced as far as the filter order
-            // (x, then y, then z) allows before the slice-axis weight is applied. Consecutive slices of a pass usually
-            // sample consecutive texel planes, so the +1 plane of one step is the base plane of the next: it is kept in
-            // registers and only one new plane (4 LDS taps + decode) is fetched per step instead of two.
+            // a texel plane of the footprint (held_planes_step): 1, 2 or 4 values, by the place of the slice axis in the filter order
             constexpr int PV = AXIS == 2 ? 1 : (AXIS == 1 ? 2 : 4);
             struct PlaneVal { float v[PV]; };
             auto fetch_plane = [&](int q, bool upper) -> PlaneVal {
@@ -602,65 +627,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TBRM_OCC_WA
                                   lerp_(lerp_(lo.v[2], hi.v[2], fs), lerp_(lo.v[3], hi.v[3], fs), tu.f), tv.f);
             };
             PlaneVal lo{}, hi{};
-            int held = INT32_MIN / 2; // slice-axis texel index of `lo`; `hi` is the plane after it
-
-            // (the opacity correction's step sizes are >= 0 unless the host was handed garbage: decided here, outside the loop)
-            auto slices = [&](auto nonneg_c) {
-            constexpr bool NONNEG = decltype(nonneg_c)::value;
+            int held = kNoPlaneHeld;
             // the step sizes in vector registers (as scalars they are spilled around this loop and fetched back every trip)
             float step_v0 = DUAL ? d.pass[0].step100[si] : s.step100, step_v1 = DUAL ? d.pass[1].step100[si] : 0.0f;
             asm volatile("" : "+v"(step_v0), "+v"(step_v1));
             for (int q = 0; q < nk; ++q) {
                 const float fs = s_f[si][q];
                 const int fl = s_flags[si][q];
-                const int i = __builtin_amdgcn_readfirstlane(s_i[si][q]); // wave-uniform: scalar branches below
-                if (i == held + 1) { lo = hi; hi = fetch_plane(q, true); }
-                else if (i == held - 1) { hi = lo; lo = fetch_plane(q, false); }
-                else if (i != held) { lo = fetch_plane(q, false); hi = fetch_plane(q, true); }
-                held = i;
-                float aw = 1.0f;
-                if constexpr (CLIP) {
-                    const float w = s_w[si][q];
-                    float c0, c1, c2;
-                    if (AXIS == 0) { c0 = w; c1 = u; c2 = v; } else if (AXIS == 1) { c0 = u; c1 = w; c2 = v; } else { c0 = u; c1 = v; c2 = w; }
-                    aw = clip_alpha_weight(c0, c1, c2, p.cc, p.cd, p.lv_dims);
-                }
-                bool inside = true;
-                if constexpr (GUARD) inside = guard_uv && (fl & 4);
-                if constexpr (DUAL) {
-                    float occ0 = 0.0f, occ1 = 0.0f;
-                    if (aw > 0.0f && inside) {
-                        windowed_alpha2<DFMT != FMT_F32, NONNEG>(combine(lo, hi, fs), step_v0, step_v1, s_alpha, p.win, occ0, occ1);
-                        occ0 = occ0 * aw;
-                        occ1 = occ1 * aw;
-                    }
-                    if (out2[0]) out2[0][q * out2_step[0]] = 1 - occ0;
-                    if (out2[1]) out2[1][q * out2_step[1]] = 1 - occ1;
-                    continue;
-                }
-                float occ = 0.0f;
-                if (aw > 0.0f && inside) occ = windowed_alpha<DFMT != FMT_F32, NONNEG>(combine(lo, hi, fs), step_v0, s_alpha, p.win) * aw;
-                out[q * out_step] = 1 - occ; // handed over as the factor of AddDirLightShader.usf:117
+                held_planes_step(lo, hi, held, __builtin_amdgcn_readfirstlane(s_i[si][q]), [&](bool upper) { return fetch_plane(q, upper); });
+                const float w = CLIP ? s_w[si][q] : 0.0f;
+                float occ0, occ1;
+                occ_sample<DFMT, CLIP, NONNEG, DUAL>(p, AXIS == 0 ? w : u, AXIS == 0 ? u : (AXIS == 1 ? w : v), AXIS == 2 ? w : v, !GUARD || (guard_uv && (fl & 4)),
+                                                     [&] { return combine(lo, hi, fs); }, step_v0, step_v1, s_alpha, occ0, occ1);
+                if constexpr (DUAL) dual_store(out2, out2_step, q, occ0, occ1);
+                else out[q * out_step] = 1 - occ0; // handed over as the factor of AddDirLightShader.usf:117
             }
-            };
-            const bool steps_nonneg = DUAL ? (d.pass[0].step100[si] >= 0.0f && d.pass[1].step100[si] >= 0.0f) : s.step100 >= 0.0f;
-            if (steps_nonneg) slices(std::true_type{});
-            else slices(std::false_type{});
         }
     };
-    using T_ = std::true_type; using F_ = std::false_type;
-    const bool interior = s_interior != 0;
+    bool steps_nonneg = true;
+#pragma unroll
+    for (int si = 0; si < NS; ++si) steps_nonneg = steps_nonneg && (DUAL ? (d.pass[0].step100[si] >= 0.0f && d.pass[1].step100[si] >= 0.0f) : (si == 0 ? p.a : p.r).step100 >= 0.0f);
     if (!pixel_ok) continue;
-    if (staged && interior && !p.clip_mode) run(T_{}, T_{}, F_{});       // the common case
-    else if (staged && !p.clip_mode) run(T_{}, F_{}, F_{});               // shell of the volume
-    else if (staged) run(T_{}, F_{}, T_{});                               // clip plane active
-    else run(F_{}, F_{}, T_{});                                           // bricks did not fit in LDS
+    occ_forms(staged, s_interior != 0, p.clip_mode != 0, steps_nonneg, run);
   }
 }
 
 // ---- k_light_occlusion_runs: a dual launch whose workgroups take RUNS of z-adjacent live units ----------------------------------
-// Units, staging, block lists, ranks, factor layout and every voxel's arithmetic are k_light_occlusion<..., 2, DUAL>'s. A
-// workgroup takes one word of the run list (tbrm_internal.h OccRuns): up to occ_run live units of one column, bottom to top.
+// The same units, staging, block lists, ranks, factor layout and per-voxel arithmetic as the dual per-unit form: both kernels take
+// the footprint rules from tbrm_occ_footprint.h and the sample loop's pieces from above. A workgroup takes one word of the run list (tbrm_internal.h OccRuns): up to occ_run live units of one column, bottom to top.
 // What is a function of the column is set up once per run — the alpha pair table, every thread's u / v taps, weights, validity
 // bits and in-plane tap offsets, the x / y brick range with the x / y part of the staged bricks' indices, the invariant part of
 // the factor-store addresses — and what changes from a unit to the one above it per unit: the eight slice-table entries (two
@@ -679,10 +673,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TBRM_OCC_WA
                                                                                                                                    const int* __restrict__ run_count)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int NS = (MODE == PASS_ADD || MODE == PASS_CHANGE_ONE) ? 1 : 2;
+    constexpr int NS = occ_mode_streams(MODE);
     constexpr bool GUARD = MODE == PASS_ADD || MODE == PASS_ADD2;
-    constexpr int ESZ = DFMT == FMT_U8 ? 1 : (DFMT == FMT_U16 ? 2 : 4);
-    constexpr int PIECES = 512 * ESZ / 16; // 16-byte pieces of a brick
+    constexpr int ESZ = fmt_bytes(DFMT);
+    constexpr int PIECES = kBrickVoxels * ESZ / 16; // 16-byte pieces of a brick
     __shared__ float2 s_alpha[257];
     __shared__ float s_w[2][NS][kOccDepth], s_f[2][NS][kOccDepth]; // [unit parity][stream][slice]
     __shared__ int s_i[2][NS][kOccDepth], s_flags[2][NS][kOccDepth];
@@ -702,69 +696,48 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TBRM_OCC_WA
     const bool pixel_ok = px < p.W && py < p.H;
 
     // ---- once per run ----
-    {
-        const float a_t = p.tf[threadIdx.x].w, a_n = p.tf[min((int) threadIdx.x + 1, 255)].w;
-        s_alpha[threadIdx.x + 1] = make_float2(a_t, a_n);
-        if (threadIdx.x == 0) s_alpha[0] = make_float2(a_t, a_t);
-    }
+    fill_alpha_pairs(s_alpha, p.tf);
     if (threadIdx.x >= 64 && threadIdx.x < 64 + NS * 4) { // base tap of the first / last pixel along x and y, one lane each
         const int t = threadIdx.x - 64, si = t >> 2, a = (t >> 1) & 1, e = t & 1;
         const ChunkStream& s = si == 0 ? p.a : p.r;
-        const int pxl = min(px0 + kOccTile, p.W) - 1, pyl = min(py0 + kOccTile, p.H) - 1;
-        const int end = a == 0 ? (e ? pxl : px0) : (e ? pyl : py0);
-        const float c = (((float) (uint32_t) end + 0.5f) / (float) (uint32_t) (a == 0 ? p.lv_dims[0] : p.lv_dims[1])) + (a == 0 ? s.uvw_off[0] : s.uvw_off[1]);
-        int i0;
-        float f;
-        texel_split(c, (float) (a == 0 ? p.data.nx : p.data.ny), i0, f);
-        s_xyend[t] = i0;
+        int first, last;
+        if (a == 0) block_ends(gx, p.W, first, last);
+        else block_ends(gy, p.H, first, last);
+        s_xyend[t] = base_tap(sample_coord(e ? last : first, a == 0 ? p.lv_dims[0] : p.lv_dims[1], a == 0 ? s.uvw_off[0] : s.uvw_off[1]), (float) (a == 0 ? p.data.nx : p.data.ny));
     }
     __syncthreads();
     // the x / y part of the brick range the column's samples can touch (union over the streams), the same for every thread
     int b0x, b0y, nbx, nby;
-    bool border_xy = false;
+    bool border_xy;
     {
-        int b0[2], nb[2];
         int lo[2] = {INT32_MAX, INT32_MAX}, hi[2] = {INT32_MIN, INT32_MIN};
 #pragma unroll
-        for (int t = 0; t < NS * 4; ++t) {
-            const int a = (t >> 1) & 1, i0 = __builtin_amdgcn_readfirstlane(s_xyend[t]);
-            lo[a] = min(lo[a], i0);
-            hi[a] = max(hi[a], i0 + 1);
-        }
-        const int bn[2] = {p.data.bnx, p.data.bnxy / p.data.bnx}, dn[2] = {p.data.nx, p.data.ny};
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            const int b_lo = max(lo[a] >> 3, 0), b_hi = min(hi[a] >> 3, bn[a] - 1);
-            b0[a] = b_lo;
-            nb[a] = max(b_hi - b_lo + 1, 0);
-            border_xy = border_xy || lo[a] < 0 || hi[a] >= dn[a];
-        }
-        b0x = b0[0]; b0y = b0[1]; nbx = nb[0]; nby = nb[1];
+        for (int t = 0; t < NS * 4; ++t) tap_span_add(__builtin_amdgcn_readfirstlane(s_xyend[t]), lo[(t >> 1) & 1], hi[(t >> 1) & 1]);
+        bool border_x, border_y;
+        brick_span(lo[0], hi[0], p.data.nx, p.data.bnx, b0x, nbx, border_x);
+        brick_span(lo[1], hi[1], p.data.ny, p.data.bnxy / p.data.bnx, b0y, nby, border_y);
+        border_xy = border_x || border_y;
     }
     const int nxy = nbx * nby;
     if ((int) threadIdx.x < min(nxy, kOccMaxBricks)) // x / y part of every staged brick's index (read behind the first unit's barrier)
-        s_brick_xy[threadIdx.x] = (uint32_t) ((b0y + (int) threadIdx.x / nbx) * p.data.bnx + (b0x + (int) threadIdx.x % nbx));
+        s_brick_xy[threadIdx.x] = staged_brick_xy((int) threadIdx.x, b0x, b0y, nbx, p.data.bnx);
 
     // a thread's taps in the plane: offsets inside the staged block (STAGED_FORM) or in the bricked volume
     auto thread_taps = [&](int si, bool staged_form) -> OccThreadTaps {
         const ChunkStream& s = si == 0 ? p.a : p.r;
         OccThreadTaps t;
-        // GetUVW(pos, res) + UVWOffset (AddDirLightShader.usf:85): the two in-plane components
-        t.u = (((float) (uint32_t) px + 0.5f) / (float) (uint32_t) p.lv_dims[0]) + s.uvw_off[0];
-        t.v = (((float) (uint32_t) py + 0.5f) / (float) (uint32_t) p.lv_dims[1]) + s.uvw_off[1];
+        t.u = sample_coord(px, p.lv_dims[0], s.uvw_off[0]);
+        t.v = sample_coord(py, p.lv_dims[1], s.uvw_off[1]);
         const AxisTaps tu = axis_taps(t.u, p.data.nx), tv = axis_taps(t.v, p.data.ny);
         t.fu = tu.f;
         t.fv = tv.f;
-        // (k_light_occlusion's voff: clamped into the volume and the staged block; staged_off's brick index * 512 + in-brick part)
         auto off_x = [&](int c) -> uint32_t {
-            c = min(max(c, 0), p.data.nx - 1);
-            if (!staged_form) return brick_off_x(c);
-            return (uint32_t) (min(max(c >> 3, b0x), b0x + nbx - 1) - b0x) * 512u + (uint32_t) (c & 7);
+            c = tap_coord(c, p.data.nx);
+            return staged_form ? staged_off<0>(c, b0x, nbx, 1u) : brick_off_x(c);
         };
         auto off_y = [&](int c) -> uint32_t {
-            c = min(max(c, 0), p.data.ny - 1);
-            if (!staged_form) return brick_off_y(c, p.data.bnx);
-            return (uint32_t) (min(max(c >> 3, b0y), b0y + nby - 1) - b0y) * (uint32_t) nbx * 512u + ((uint32_t) (c & 7) << 3);
+            c = tap_coord(c, p.data.ny);
+            return staged_form ? staged_off<1>(c, b0y, nby, (uint32_t) nbx) : brick_off_y(c, p.data.bnx);
         };
         const uint32_t u0 = off_x(tu.i0), u1 = off_x(tu.i0 + 1), v0 = off_y(tv.i0), v1 = off_y(tv.i0 + 1);
         t.o00 = u0 + v0; t.o10 = u1 + v0; t.o01 = u0 + v1; t.o11 = u1 + v1;
@@ -777,28 +750,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TBRM_OCC_WA
         uint32_t o00, o10, o01, o11;
         float fu, fv;
         int ok;
-        float lo, hi; // texel planes of the footprint (4 taps at one z, filtered along x and y) around the last slice taken
-        int held;     // z texel index of `lo`; `hi` is the plane after it
+        float lo, hi; // the held planes (held_planes_step): 4 taps at one z, filtered along x and y
+        int held;
     };
     auto stream_regs = [&](int si) __attribute__((always_inline)) -> StreamRegs {
         const OccThreadTaps t = thread_taps(si, true);
-        return StreamRegs{t.o00, t.o10, t.o01, t.o11, t.fu, t.fv, t.ok, 0.0f, 0.0f, INT32_MIN / 2};
+        return StreamRegs{t.o00, t.o10, t.o01, t.o11, t.fu, t.fv, t.ok, 0.0f, 0.0f, kNoPlaneHeld};
     };
     StreamRegs regs_a = stream_regs(0), regs_r = NS == 2 ? stream_regs(1) : StreamRegs{};
     // where a thread's factors go in the two passes' stores, as far as the column decides it: the pass's block is
-    // fs_slot[inv_idx + what the unit adds], the voxel's place in it inv_off + what the unit adds (k_light_occlusion: out2)
+    // fs_slot[inv_idx + what the unit adds], the voxel's place in it inv_off + what the unit adds (the per-unit form's out2)
     int inv_idx[2], inv_off[2];
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         const DualPass& P = d.pass[k];
         if (P.axis == 2) {
             inv_idx[k] = (py >> 4) * P.blocks_x + (px >> 4);
-            inv_off[k] = (py & 15) * 16 + (px & 15);
+            inv_off[k] = (py & 15) * kOccTile + (px & 15);
         } else {
             const int pa = P.axis == 0 ? px : py, pu = P.axis == 0 ? py : px; // (the pass's rows are z)
             const int ks = (pa - P.start) * P.dir;
             inv_idx[k] = (ks >> 3) * P.blocks_y * P.blocks_x + (pu >> 4);
-            inv_off[k] = (ks & 7) * 256 + (pu & 15);
+            inv_off[k] = (ks & 7) * kOccSliceFloats + (pu & 15);
         }
     }
     bool steps_nonneg = true;
@@ -813,21 +786,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TBRM_OCC_WA
         if (threadIdx.x < NS * kOccDepth) { // z taps of each slice of the unit (wave-uniform values)
             const int si = threadIdx.x / kOccDepth, q = threadIdx.x % kOccDepth;
             const ChunkStream& s = si == 0 ? p.a : p.r;
-            const int j = min(k0 + q, p.n_steps - 1);
-            const float w = (((float) (uint32_t) j + 0.5f) / (float) (uint32_t) p.lv_dims[2]) + s.uvw_off[2];
-            const AxisTaps t = axis_taps(w, p.data.nz);
-            s_w[par][si][q] = w; s_f[par][si][q] = t.f; s_i[par][si][q] = t.i0;
-            s_flags[par][si][q] = (t.ok0 ? 1 : 0) | (t.ok1 ? 2 : 0) | ((w == saturate_(w)) ? 4 : 0);
+            const OccSliceEntry e = occ_slice_entry(min(k0 + q, p.n_steps - 1), p.lv_dims[2], s.uvw_off[2], p.data.nz);
+            s_w[par][si][q] = e.w; s_f[par][si][q] = e.f; s_i[par][si][q] = e.i0; s_flags[par][si][q] = e.flags;
         }
         if (threadIdx.x >= 64 && threadIdx.x < 64 + NS * 2) { // base tap of the unit's first / last slice
             const int t = threadIdx.x - 64, si = t >> 1, e = t & 1;
             const ChunkStream& s = si == 0 ? p.a : p.r;
-            const int end = e ? k0 + nk - 1 : k0;
-            const float c = (((float) (uint32_t) end + 0.5f) / (float) (uint32_t) p.lv_dims[2]) + s.uvw_off[2];
-            int i0;
-            float f;
-            texel_split(c, (float) p.data.nz, i0, f);
-            s_zend[par][t] = i0;
+            int first, last;
+            group_ends(k0, p.n_steps, 0, 1, first, last); // (a dual launch loops up z from 0: launch_occ3)
+            s_zend[par][t] = base_tap(sample_coord(e ? last : first, p.lv_dims[2], s.uvw_off[2]), (float) p.data.nz);
         }
         __syncthreads(); // (also: every thread is done with the bricks of the unit before)
         bool staged, interior;
@@ -835,38 +802,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TBRM_OCC_WA
         {
             int zlo = INT32_MAX, zhi = INT32_MIN;
 #pragma unroll
-            for (int t = 0; t < NS * 2; ++t) {
-                const int i0 = __builtin_amdgcn_readfirstlane(s_zend[par][t]);
-                zlo = min(zlo, i0);
-                zhi = max(zhi, i0 + 1);
-            }
-            const int b_lo = max(zlo >> 3, 0), b_hi = min(zhi >> 3, ((p.data.nz + 7) >> 3) - 1);
-            b0z = b_lo;
-            nbz = max(b_hi - b_lo + 1, 0);
-            const int count = nxy * nbz;
-            staged = count > 0 && count <= kOccMaxBricks && count * 512 * ESZ <= lds_budget_bytes; // else: taps from global memory
-            interior = !(border_xy || zlo < 0 || zhi >= p.data.nz);
+            for (int t = 0; t < NS * 2; ++t) tap_span_add(__builtin_amdgcn_readfirstlane(s_zend[par][t]), zlo, zhi);
+            bool border_z;
+            brick_span(zlo, zhi, p.data.nz, (p.data.nz + 7) >> 3, b0z, nbz, border_z);
+            staged = bricks_staged(nxy * nbz, ESZ, lds_budget_bytes);
+            interior = !(border_xy || border_z);
         }
         if (staged) { // copy the bricks, a z layer at a time: 512*ESZ bytes each, 16 bytes per lane
             const int layer = nxy * PIECES;
             const int wave_base = wave * 64;
             for (int lz = 0; lz < nbz; ++lz) {
-                const uint32_t gz_part = (uint32_t) ((b0z + lz) * p.data.bnxy);
+                const uint32_t gz_part = staged_brick_z(lz, b0z, p.data.bnxy);
                 for (int cb = wave_base; cb < layer; cb += 256) {
                     const int c = cb + lane;
-                    if (c < layer) { // (8-bit bricks are 32 pieces: an odd number of them ends in the middle of a wave)
-                        const uint32_t gb = s_brick_xy[c / PIECES] + gz_part;
-                        dma_16((const char*) p.data.data + ((size_t) gb * 512 * ESZ + (size_t) (c % PIECES) * 16), smem + (size_t) (lz * layer + cb) * 16);
-                    }
+                    if (c < layer) // (8-bit bricks are 32 pieces: an odd number of them ends in the middle of a wave)
+                        dma_16((const char*) p.data.data + staged_piece_src(s_brick_xy[c / PIECES] + gz_part, c, PIECES, ESZ), smem + (size_t) (lz * layer + cb) * 16);
                 }
             }
         }
         if (threadIdx.x < NS * kOccDepth) { // z tap offsets of each slice, in the layout just chosen
             const int si = threadIdx.x / kOccDepth, q = threadIdx.x % kOccDepth;
             auto zoff = [&](int c) -> uint32_t {
-                c = min(max(c, 0), p.data.nz - 1);
-                if (!staged) return brick_off_z(c, p.data.bnxy);
-                return (uint32_t) (min(max(c >> 3, b0z), b0z + nbz - 1) - b0z) * (uint32_t) nxy * 512u + ((uint32_t) (c & 7) << 6);
+                c = tap_coord(c, p.data.nz);
+                return staged ? staged_off<2>(c, b0z, nbz, (uint32_t) nxy) : brick_off_z(c, p.data.bnxy);
             };
             s_o0[par][si][q] = zoff(s_i[par][si][q]);
             s_o1[par][si][q] = zoff(s_i[par][si][q] + 1);
@@ -881,11 +839,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TBRM_OCC_WA
             if (P.axis == 2) {
                 const int ks = (k0 - P.start) * P.dir;
                 unit_idx = (ks >> 3) * P.blocks_y * P.blocks_x;
-                unit_off[k] = (ks & 7) * 256;
-                out2_step[k] = 256 * P.dir;
+                unit_off[k] = (ks & 7) * kOccSliceFloats;
+                out2_step[k] = kOccSliceFloats * P.dir;
             } else {
                 unit_idx = (k0 >> 4) * P.blocks_x;
-                unit_off[k] = (k0 & 15) * 16;
+                unit_off[k] = (k0 & 15) * kOccTile;
                 out2_step[k] = kOccTile;
             }
             rank[k] = pixel_ok ? P.fs_slot[inv_idx[k] + unit_idx] : -1;
@@ -894,14 +852,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TBRM_OCC_WA
         __syncthreads();
         if (!pixel_ok) continue;
 
-        // the sample loop, specialised as k_light_occlusion's: STAGED / INTERIOR / CLIP
+        // the sample loop in one of occ_forms' forms
         auto run = [&](auto staged_c, auto interior_c, auto clip_c, auto nonneg_c) __attribute__((always_inline)) { // (inlined early: lo / hi / held stay in registers)
             constexpr bool STAGED = decltype(staged_c)::value, INTERIOR = decltype(interior_c)::value, CLIP = decltype(clip_c)::value, NONNEG = decltype(nonneg_c)::value;
             const float border = p.data_border;
-            auto tap = [&](uint32_t off, bool ok) -> float {
-                if constexpr (INTERIOR) return STAGED ? lds_voxel<DFMT>(smem, off) : load_voxel<DFMT>(p.data.data, off);
-                else return ok ? (STAGED ? lds_voxel<DFMT>(smem, off) : load_voxel<DFMT>(p.data.data, off)) : border;
-            };
+            auto tap = [&](uint32_t off, bool ok) -> float { return occ_tap<DFMT, STAGED, INTERIOR>(smem, p.data.data, off, ok, border); };
             auto stream = [&](auto si_c, StreamRegs& sr) __attribute__((always_inline)) {
                 constexpr int si = decltype(si_c)::value;
                 uint32_t o00 = sr.o00, o10 = sr.o10, o01 = sr.o01, o11 = sr.o11;
@@ -916,10 +871,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TBRM_OCC_WA
                 float* out2[2]; // where this thread's voxels go in the two passes' stores (null: block flagged empty)
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
-                    const DualPass& P = d.pass[k];
                     out2[k] = nullptr;
-                    if (rank[k] >= 0) {
-                        float* const blk_base = (uint32_t) rank[k] < P.fs_cap[si] ? P.fs_keep[si] + (size_t) (uint32_t) rank[k] * 2048 : P.fs_spill[si] + (size_t) ((uint32_t) rank[k] - P.fs_cap[si]) * 2048;
+                    const DualPass& P = d.pass[k];
+                    if (rank[k] >= 0) { // (factor_block, spelled out: tbrm_occ_footprint.h says why)
+                        float* const blk_base = (uint32_t) rank[k] < P.fs_cap[si] ? P.fs_keep[si] + (size_t) (uint32_t) rank[k] * kOccBlockFloats : P.fs_spill[si] + (size_t) ((uint32_t) rank[k] - P.fs_cap[si]) * kOccBlockFloats;
                         out2[k] = blk_base + (inv_off[k] + unit_off[k]);
                     }
                 }
@@ -937,33 +892,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TBRM_OCC_WA
                     const float fs = s_f[par][si][q];
                     const int fl = s_flags[par][si][q];
                     const int i = __builtin_amdgcn_readfirstlane(s_i[par][si][q]); // wave-uniform: scalar branches below
-                    if (i == sr.held + 1) { sr.lo = sr.hi; sr.hi = fetch_plane(q, true); }
-                    else if (i == sr.held - 1) { sr.hi = sr.lo; sr.lo = fetch_plane(q, false); }
-                    else if (i != sr.held) { sr.lo = fetch_plane(q, false); sr.hi = fetch_plane(q, true); }
-                    sr.held = i;
-                    float aw = 1.0f;
-                    if constexpr (CLIP) aw = clip_alpha_weight(u, v, s_w[par][si][q], p.cc, p.cd, p.lv_dims);
-                    bool inside = true;
-                    if constexpr (GUARD) inside = (ok & 16) && (fl & 4);
-                    float occ0 = 0.0f, occ1 = 0.0f;
-                    if (aw > 0.0f && inside) {
-                        windowed_alpha2<DFMT != FMT_F32, NONNEG>(lerp_(sr.lo, sr.hi, fs), step_v0, step_v1, s_alpha, p.win, occ0, occ1);
-                        occ0 = occ0 * aw;
-                        occ1 = occ1 * aw;
-                    }
-                    if (out2[0]) out2[0][q * out2_step[0]] = 1 - occ0;
-                    if (out2[1]) out2[1][q * out2_step[1]] = 1 - occ1;
+                    held_planes_step(sr.lo, sr.hi, sr.held, i, [&](bool upper) { return fetch_plane(q, upper); });
+                    float occ0, occ1;
+                    occ_sample<DFMT, CLIP, NONNEG, true>(p, u, v, CLIP ? s_w[par][si][q] : 0.0f, !GUARD || ((ok & 16) && (fl & 4)), [&] { return lerp_(sr.lo, sr.hi, fs); }, step_v0, step_v1, s_alpha,
+                                                         occ0, occ1);
+                    dual_store(out2, out2_step, q, occ0, occ1);
                 }
             };
             stream(std::integral_constant<int, 0>{}, regs_a);
             if constexpr (NS == 2) stream(std::integral_constant<int, 1>{}, regs_r);
         };
+        // (occ_forms' ladder, written out: through the function the two-stream forms spill up to 14 more vector registers —
+        // profiles/r14_occlusion_rules.txt)
         using T_ = std::true_type; using F_ = std::false_type;
         auto forms = [&](auto nonneg_c) __attribute__((always_inline)) {
-            if (staged && interior && !p.clip_mode) run(T_{}, T_{}, F_{}, nonneg_c); // the common case
-            else if (staged && !p.clip_mode) run(T_{}, F_{}, F_{}, nonneg_c);         // shell of the volume
-            else if (staged) run(T_{}, F_{}, T_{}, nonneg_c);                         // clip plane active
-            else run(F_{}, F_{}, T_{}, nonneg_c);                                     // bricks did not fit in LDS
+            if (staged && interior && !p.clip_mode) run(T_{}, T_{}, F_{}, nonneg_c);
+            else if (staged && !p.clip_mode) run(T_{}, F_{}, F_{}, nonneg_c);
+            else if (staged) run(T_{}, F_{}, T_{}, nonneg_c);
+            else run(F_{}, F_{}, T_{}, nonneg_c);
         };
         if (steps_nonneg) forms(T_{});
         else forms(F_{});

@@ -20,13 +20,11 @@ unsigned event_flags()
 bool force_slice_kernel() { return tune(TUNE_FORCE_SLICE_KERNEL) == 1; }
 int chunk_steps_override() { return tune(TUNE_CHUNK_STEPS); }
 
-// The texel coordinate of pixel c's previous-slice fetch along one buffer axis, with the kernel's own fp32 sequence (texel_split of
-// ((c + 0.5) / size + offset) over `texels` texels; the light planes: texels == size)
+// The texel coordinate of pixel c's previous-slice fetch along one buffer axis: the kernels' own functions (tbrm_occ_footprint.h:
+// texel_split's coordinate of ((c + 0.5) / size + offset) over `texels` texels; the light planes: texels == size)
 static float tap_texel(int c, int size, float off, int texels)
 {
-    const float u = (((float) (uint32_t) c + 0.5f) / (float) size) + off;
-    const float x = u * (float) texels - 0.5f;
-    return std::fmin(std::fmax(x, -0x1p30f), 0x1p30f);
+    return texel_coord(sample_coord(c, size, off), (float) texels);
 }
 
 // (tap index - pixel index) of the previous-slice bilinear fetch over every pixel of one buffer axis: hi includes the +1 tap,
@@ -591,7 +589,7 @@ static int plan_pass_sweep(tbrm_resources* r, const PropParams& base, const tbrm
             // sized for what passes under this volume / transfer function / window have needed so far; before the first count
             // has arrived: every block of a small pass (an entry that overflows is dropped and its pass sampled again), half
             // the blocks of a large one (CT-like volumes are mostly air: 512^3 of the benchmark keeps 40 %)
-            const size_t unknown = blocks * 2048 * sizeof(float) <= ((size_t) 256 << 20) ? blocks : blocks / 2;
+            const size_t unknown = blocks * kOccBlockFloats * sizeof(float) <= ((size_t) 256 << 20) ? blocks : blocks / 2;
             const size_t want = live_known ? std::max<size_t>(live, 1)
                                            : (r->f_est_blocks ? std::min(blocks, r->f_est_blocks + r->f_est_blocks / 32 + 64) : std::max<size_t>(unknown, 1));
             if (refill && refill->cap_blocks >= want && !refill->pinned) {
@@ -692,9 +690,7 @@ int plan_pass(tbrm_resources* r, const PropParams& base, const tbrm_light_pass& 
         for (const tbrm_light_pass* q : {&pa, pr}) {
             if (!q) continue;
             for (int z : {za, zb - 1}) {
-                const int i0 = (int) std::floor(tap_texel(z, r->lv_dims[2], q->uvw_offset[2], r->desc.dim_z));
-                lo = std::min(lo, i0);
-                hi = std::max(hi, i0 + 1);
+                tap_span_add(base_tap(sample_coord(z, r->lv_dims[2], q->uvw_offset[2]), (float) r->desc.dim_z), lo, hi);
             }
         }
         lo = clamp_int(lo, 0, r->desc.dim_z - 1);
@@ -724,7 +720,7 @@ int plan_pass(tbrm_resources* r, const PropParams& base, const tbrm_light_pass& 
     // pass's first occlusion launch (enqueue_plan_chunk)
     plan.sparse = tune(TUNE_SPARSE_OCC) != 0;
     plan.work_list = plan.sparse && tune(TUNE_OCC_LIST) != 0;
-    p.occ_groups = ceil_div(S, kOccSlices);
+    p.occ_groups = ceil_div(S, kOccDepth);
     plan.flags_per_group = (size_t) p.occ_blocks_y * p.occ_blocks_x;
     plan.flags_per_span = (size_t) p.occ_groups * plan.flags_per_group;
     if (plan.sparse) {

@@ -163,7 +163,7 @@ struct BlockLists {
 };
 
 struct FactorEntry {
-    float* base = nullptr;          // cap_blocks x 2048 floats
+    float* base = nullptr;          // cap_blocks factor blocks (kOccBlockFloats each)
     size_t cap_blocks = 0;
     BlockLists* lists = nullptr;    // the ranks its blocks are stored under (borrowed: BlockLists::users)
     hipEvent_t ev_filled = nullptr; // the occlusion that fills the entry is done (occlusion stream)
@@ -178,7 +178,7 @@ struct FactorEntry {
     bool pinned = false;            // in use by the operator being planned
     bool spent = false;             // its light has left the scene: first in line for reuse
     uint64_t last_use = 0;
-    size_t bytes() const { return cap_blocks * 2048 * sizeof(float); }
+    size_t bytes() const { return cap_blocks * tbrm::kOccBlockFloats * sizeof(float); }
 };
 
 // Scratch of the block-compact hand-over: per buffer (axis passes take four in rotation) the factor stores of the two streams
@@ -515,7 +515,7 @@ RelayoutParams relayout_params(const void* src, void* dst, const int dims[3], co
 
 // ---- the light-pass layer (tbrm_light_plan.cpp, tbrm_factor_cache.cpp, tbrm_light_enqueue.cpp, tbrm_light_operators.cpp) ------------------------------------------------------------------------
 // Range of (tap index - pixel index) of the previous-slice bilinear fetch over one buffer axis, evaluated with the
-// kernel's own fp32 sequence (texel_split of ((c+0.5)/size + offset)); hi includes the +1 tap.
+// kernel's own functions (tbrm_occ_footprint.h: texel_split of sample_coord); hi includes the +1 tap.
 struct TapRange { int lo = 0, hi = 0; bool ok = false; };
 
 struct ChunkFit { int M = 0; TapRange tx, ty; int rect_planes = 0; }; // (rect_planes: ChunkParams::rect_planes of the pass)

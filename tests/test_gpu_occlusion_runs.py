@@ -253,11 +253,54 @@ def test_units_in_runs_is_what_numpy_cuts_from_the_data(gpu, tunables, dims, r):
                 assert want > 0
 
 
+UNSTAGED_DIMS = (96, 80, 144)  # float32 data under a half-resolution light volume of 48 x 40 x 72: 3 x 3 x 9 units
+UNSTAGED_BUDGET = 96 * 1024 // 2048  # bricks of 512 floats that the staging budget of 96 KiB holds
+
+
+def unstaged_scene(world):
+    """The first of LIGHTS whose two passes over the half-resolution light volume are both swept (one dual launch) and under which
+    some unit of the middle column cannot be staged: its tap span crosses five bricks in x or y, which with three brick layers in z
+    is 5 * 4 * 3 bricks of 2 KiB, more than the budget, while a unit of 4 * 4 * 3 bricks just fits. Returns (direction, brick
+    counts of every unit [gz][gy][gx], widest x / y span of the middle column in bricks); None: no such light."""
+    lv = tuple((d + 1) // 2 for d in UNSTAGED_DIMS)
+    bn = [(d + 7) // 8 for d in UNSTAGED_DIMS]
+    for d in LIGHTS:
+        light = abi.DirLightParams(d, 0.4)
+        plan = abi.host_plan_light(light, world, lv)
+        if len(plan) != 2 or any(p[0] != 0 for p in plan):
+            continue
+        off = abi.host_light_passes(light, world, lv)[0][0].uvw_offset  # (the same for both passes of a light)
+
+        def span(a, first, last):  # bricks the taps of positions first .. last touch along axis a, clamped to the grid
+            taps = [_base_tap(e, lv[a], off[a], UNSTAGED_DIMS[a]) for e in (first, last)]
+            return max(min((max(taps) + 1) >> 3, bn[a] - 1) - max(min(taps) >> 3, 0) + 1, 0)
+
+        nx = [span(0, 16 * g, min(16 * g + 16, lv[0]) - 1) for g in range((lv[0] + 15) // 16)]
+        ny = [span(1, 16 * g, min(16 * g + 16, lv[1]) - 1) for g in range((lv[1] + 15) // 16)]
+        nz = [span(2, 8 * g, min(8 * g + 8, lv[2]) - 1) for g in range((lv[2] + 7) // 8)]
+        counts = np.array([[[x * y * z for x in nx] for y in ny] for z in nz])
+        if max(nx[1], ny[1]) >= 5 and counts[:, 1, 1].max() > UNSTAGED_BUDGET:
+            return d, counts, max(nx[1], ny[1])
+    return None
+
+
+def test_the_unstaged_scene_holds_units_of_both_kinds():
+    """(no device) the precondition of the "unstaged" case below"""
+    found = unstaged_scene(S.default_world())
+    assert found is not None, "no light of LIGHTS has two swept passes and a middle column that spans five bricks"
+    _, counts, widest = found
+    assert widest >= 5 and counts[:, 1, 1].max() >= 5 * 4 * 3 > UNSTAGED_BUDGET, (widest, counts[:, 1, 1])
+    assert ((counts > 0) & (counts <= UNSTAGED_BUDGET)).any() and 4 * 4 * 3 <= UNSTAGED_BUDGET, counts
+
+
 @gpu_test
-@pytest.mark.parametrize("case", ["clip_plane", "cache_off", "not_reserved", "float_light_volume"])
+@pytest.mark.parametrize("case", ["clip_plane", "cache_off", "not_reserved", "float_light_volume", "unstaged"])
 def test_run_form_under_other_conditions(gpu, oracle_mod, tunables, case):
     """An active clip plane (the sample loop's other form), no factor cache (fused Changes: two streams per launch), a handle that
-    was never reserved (its lists are allocated on the way), a float light volume (raw floats compared)."""
+    was never reserved (its lists are allocated on the way), a float light volume (raw floats compared), units whose bricks do not fit
+    the staging budget beside units whose bricks do (taps from global memory: unstaged_scene)."""
+    if case == "unstaged":
+        return run_form_with_unstaged_units(oracle_mod, tunables)
     dims, dtype = DIMS[0], np.uint16
     vol = make_volume(dims, dtype)
     world = S.default_world()
@@ -294,6 +337,48 @@ def test_run_form_under_other_conditions(gpu, oracle_mod, tunables, case):
             assert (c["occlusion_units_in_runs"] > 0) == (r > 1) and c["occlusion_dual"] > 0, (case, r, c)
     for r in RUNS:
         assert got[r].tobytes() == got[1].tobytes(), f"{case}, occ_run {r}: {np.count_nonzero(got[r] != got[1])} light voxels differ from occ_run 1"
+
+
+def run_form_with_unstaged_units(oracle_mod, tunables):
+    """An Add and a Change over dense float32 data of 96 x 80 x 144 under a half-resolution light volume: the same bytes for occ_run 1
+    and 4, and the oracle's."""
+    world = S.default_world()
+    found = unstaged_scene(world)
+    assert found is not None, "no light of LIGHTS has two swept passes and a middle column that spans five bricks"
+    d, counts, widest = found
+    assert widest >= 5 and counts[:, 1, 1].max() >= 5 * 4 * 3 > UNSTAGED_BUDGET, (widest, counts[:, 1, 1])
+    assert ((counts > 0) & (counts <= UNSTAGED_BUDGET)).any(), counts
+    vol = S.make_volume_numpy(UNSTAGED_DIMS, np.float32, 0x5EED0B14)
+    light = abi.DirLightParams(d, 0.4)
+    turned = abi.DirLightParams(S.rotate_z(d, 5.0), 0.4)
+    orc = oracle_mod.OracleScene(vol, False, True)
+    orc.set_tf_lut(abi.color_curve_to_lut(S.TF_A_KEYS))
+    orc.set_windowing(abi.WindowingParams(*WINDOW))
+    want = {}
+    orc.add_dir_light(light, True, world)
+    want["add"] = orc.light.copy()
+    orc.change_dir_light(light, turned, world)
+    want["change"] = orc.light.copy()
+    got = {}
+    for r in (1, 4):
+        tunables("occ_run", r)
+        with abi.Resources(UNSTAGED_DIMS, abi.DTYPE_FMT[np.dtype(np.float32)], False, True) as res:
+            res.upload_volume(vol)
+            res.set_tf_lut(abi.color_curve_to_lut(S.TF_A_KEYS))
+            res.set_windowing(abi.WindowingParams(*WINDOW))
+            res.reserve(2)
+            res.clear_light_volume(0.0)
+            res.add_dir_light(light, True, world)
+            res.flush()
+            got[r, "add"] = res.download_light_volume()
+            res.change_dir_light(light, turned, world)
+            res.flush()
+            got[r, "change"] = res.download_light_volume()
+            c = res.path_counters()
+            assert c["occlusion_dual"] > 0 and (c["occlusion_units_in_runs"] > 0) == (r > 1), (r, c)
+    for name in ("add", "change"):
+        assert got[4, name].tobytes() == got[1, name].tobytes(), f"{name}: {np.count_nonzero(got[4, name] != got[1, name])} light voxels differ between occ_run 4 and 1"
+        assert np.array_equal(got[4, name], want[name]), f"{name}: {np.count_nonzero(got[4, name] != want[name])} light voxels differ from the oracle"
 
 
 @gpu_test
