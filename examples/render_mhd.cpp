@@ -5,7 +5,7 @@
 //
 //   g++ -std=c++17 -O2 -I include examples/render_mhd.cpp -o render_mhd -L tbraymarcherplugin_amd/lib -ltbrm -lz
 //       (plus -Wl,-rpath,$PWD/tbraymarcherplugin_amd/lib -Wl,-rpath,/opt/rocm/lib to run it in place)
-//   ./render_mhd volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]] [--islands OP,N[,LABEL]]
+//   ./render_mhd volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]] [--margin OP,RADIUS[,LABEL]] [--islands OP,N[,LABEL]]
 //       --light-color: the key light's colour (components in [0, 1]) on an RGB light volume (include/tbrm_color_lights.h); the fill stays white
 //       --auto-window: the window comes from the data (ARaymarchVolume::AutoWindow, include/tbrm_volume_stats.h): the span between
 //                      the LOW and HIGH percentiles of the value histogram, 0.01,0.99 when not given
@@ -17,7 +17,11 @@
 //       --morph: after --grow, binary morphology of label LABEL (the grown label when not given) (ARaymarchVolume::MorphLabel,
 //                      include/tbrm_morphology.h): OP is dilate, erode, open or close, R the radius in unit steps of the 6-neighbour
 //                      cross; voxels that leave the label get label 0; printed as one "morph" line
-//       --islands: after --grow and --morph, the islands of label LABEL (the grown label when not given) (ARaymarchVolume::KeepLargestIslands
+//       --margin: after --grow and --morph, a Euclidean margin of label LABEL (the grown label when not given) (ARaymarchVolume::MarginLabel,
+//                      include/tbrm_margin.h): OP is expand, shrink, open or close, RADIUS a distance in the units of the file's
+//                      ElementSpacing — a ball on the anisotropic grid; voxels that leave the label get label 0; printed as one
+//                      "margin" line
+//       --islands: after --grow, --morph and --margin, the islands of label LABEL (the grown label when not given) (ARaymarchVolume::KeepLargestIslands
 //                      and its kin, include/tbrm_islands.h), 6-connected: OP is keep (the N largest stay, the others get label 0), remove
 //                      (islands of fewer than N voxels get label 0), split (the N largest get LABEL, LABEL + 1, ..) or fill (what the
 //                      label encloses, up to N voxels a hole, 0: of any size, joins it); printed as one "islands" line
@@ -77,6 +81,18 @@ int main(int argc, char** argv)
             argc -= 2;
             break;
         }
+    char margin_op[8] = "";
+    double margin_radius = 0.0;
+    int margin_label = -1;
+    bool margin = false;
+    for (int i = 1; i + 1 < argc; ++i)
+        if (!std::strcmp(argv[i], "--margin")) {
+            if (std::sscanf(argv[i + 1], "%7[a-z],%lf,%d", margin_op, &margin_radius, &margin_label) < 2) { argc = 0; break; }
+            margin = true;
+            for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
+            argc -= 2;
+            break;
+        }
     char islands_op[8] = "";
     long long islands_n = 0;
     int islands_label = -1;
@@ -98,7 +114,7 @@ int main(int argc, char** argv)
             break;
         }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]] [--islands OP,N[,LABEL]]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]] [--margin OP,RADIUS[,LABEL]] [--islands OP,N[,LABEL]]\n", argv[0]);
         return 2;
     }
     const int width = argc > 3 ? std::atoi(argv[3]) : 512, height = argc > 4 ? std::atoi(argv[4]) : 512;
@@ -181,7 +197,23 @@ int main(int argc, char** argv)
                     morph_label, (unsigned long long) m.SourceVoxels, (unsigned long long) m.ResultVoxels, (unsigned long long) m.Added,
                     (unsigned long long) m.Removed, m.BoxMin[0], m.BoxMin[1], m.BoxMin[2], m.BoxMax[0], m.BoxMax[1], m.BoxMax[2], m.Launches);
     }
-    if (islands) { // after the grow and the morphology, before the frame
+    if (margin) { // after the grow and the morphology, before the frame
+        static const char* const names[4] = {"expand", "shrink", "open", "close"};
+        int op = -1;
+        for (int k = 0; k < 4; ++k)
+            if (!std::strcmp(margin_op, names[k])) op = k;
+        if (margin_label < 0) margin_label = grow_label;
+        FMarginResult m;
+        if (op < 0 || !volume.MarginLabel(op, margin_radius, margin_label, m)) {
+            std::fprintf(stderr, "margin failed: %s\n", op < 0 ? "OP must be expand, shrink, open or close" : tbrm_last_error());
+            return 1;
+        }
+        std::printf("margin %s %.9g label %d weights %u %u %u limit %u reach %d %d %d source %llu result %llu added %llu removed %llu box %d %d %d .. %d %d %d launches %d\n",
+                    margin_op, margin_radius, margin_label, m.Weights[0], m.Weights[1], m.Weights[2], m.Limit, m.Reach[0], m.Reach[1], m.Reach[2],
+                    (unsigned long long) m.SourceVoxels, (unsigned long long) m.ResultVoxels, (unsigned long long) m.Added, (unsigned long long) m.Removed,
+                    m.BoxMin[0], m.BoxMin[1], m.BoxMin[2], m.BoxMax[0], m.BoxMax[1], m.BoxMax[2], m.Launches);
+    }
+    if (islands) { // after the grow, the morphology and the margin, before the frame
         if (islands_label < 0) islands_label = grow_label;
         FIslandsResult r;
         bool known = true, ok = false;

@@ -23,6 +23,7 @@
 #include "tbrm_segment.h"
 #include "tbrm_morphology.h"
 #include "tbrm_islands.h"
+#include "tbrm_margin.h"
 
 #include <algorithm>
 #include <cmath>
@@ -289,6 +290,17 @@ struct FMorphResult {
     int Launches = 0;
 };
 
+// What a Euclidean margin call found (include/tbrm_margin.h): ARaymarchVolume::MarginLabel and its four named forms
+struct FMarginResult {
+    uint64_t SourceVoxels = 0, ResultVoxels = 0; // the label's voxels before and the operator's result, inside the box
+    uint64_t Added = 0, Removed = 0;             // voxels that joined / left the label
+    uint64_t Relabelled = 0;                     // label bytes that changed
+    int BoxMin[3] = {0, 0, 0}, BoxMax[3] = {-1, -1, -1}; // of what joined or left, inclusive; nothing: the volume's size and -1
+    int Reach[3] = {0, 0, 0};                    // voxels per axis the radius reaches
+    uint32_t Weights[3] = {0, 0, 0}, Limit = 0;  // the squared distance the radius and the spacing became (tbrm_host_margin_weights)
+    int Launches = 0;
+};
+
 // What an island call found (include/tbrm_islands.h): ARaymarchVolume::KeepLargestIslands / RemoveSmallIslands / SplitIslands /
 // FillLabelHoles
 struct FIslandsResult {
@@ -321,6 +333,9 @@ public:
     // (not in the reference) an RGB light volume lit by the lights' LightColor; read when the resources are initialised
     // (SetVolumeAsset). false: a mono handle, and LightColor is ignored. The batched reset has no colour form: light by light.
     bool bColoredLights = false;
+    // (not in the reference) the voxel spacing MarginLabel measures its radius in: LoadMHDFileIntoVolume sets it to the file's
+    // ElementSpacing, SetVolumeAsset (a new asset, of unknown spacing) resets it; all zero: unit spacing
+    double VoxelSpacing[3] = {0, 0, 0};
 
     struct FStats { int Resets = 0, LightAdds = 0, LightChanges = 0, Frames = 0; } Stats; // what Tick decided (test hook)
 
@@ -330,6 +345,7 @@ public:
     bool SetVolumeAsset(const void* Voxels, int SizeX, int SizeY, int SizeZ, int Format)
     {
         InitializeRaymarchResources(SizeX, SizeY, SizeZ, Format);
+        for (double& s : VoxelSpacing) s = 0.0;
         if (!RaymarchResources.Handle) return false;
         const size_t bytes = (size_t) SizeX * SizeY * SizeZ * (Format == TBRM_FMT_G8 ? 1 : (Format == TBRM_FMT_G16 ? 2 : 4));
         if (tbrm_upload_volume(RaymarchResources.Handle, Voxels, bytes) != TBRM_OK) return false;
@@ -501,6 +517,40 @@ public:
     bool ErodeLabel(int Radius, int Label, FMorphResult& Out, int Connectivity = 6) { return MorphLabel(TBRM_MORPH_ERODE, Radius, Label, Out, Connectivity); }
     bool OpenLabel(int Radius, int Label, FMorphResult& Out, int Connectivity = 6) { return MorphLabel(TBRM_MORPH_OPEN, Radius, Label, Out, Connectivity); }
     bool CloseLabel(int Radius, int Label, FMorphResult& Out, int Connectivity = 6) { return MorphLabel(TBRM_MORPH_CLOSE, Radius, Label, Out, Connectivity); }
+
+    // A Euclidean margin of one label (include/tbrm_margin.h; no counterpart in the reference): Op (TBRM_MARGIN_EXPAND .. CLOSE) by
+    // RadiusWorld, a distance in the unit of VoxelSpacing (voxels when there is none), as a ball on the anisotropic grid, on the
+    // device. Voxels that join get Label (over any label), voxels that leave get EraseLabel; bMeasureOnly counts them and writes
+    // nothing. Like the other label edits it requests no recompute. Needs a label volume.
+    bool MarginLabel(int Op, double RadiusWorld, int Label, FMarginResult& Out, int EraseLabel = 0, bool bMeasureOnly = false)
+    {
+        Out = FMarginResult{};
+        if (!RaymarchResources.Handle || Label < 0 || Label > 255) return false;
+        const bool unit = VoxelSpacing[0] == 0.0 && VoxelSpacing[1] == 0.0 && VoxelSpacing[2] == 0.0;
+        const double spacing[3] = {unit ? 1.0 : VoxelSpacing[0], unit ? 1.0 : VoxelSpacing[1], unit ? 1.0 : VoxelSpacing[2]};
+        tbrm_margin_desc d{};
+        if (tbrm_host_margin_weights(spacing, RadiusWorld, d.weights, &d.limit) != TBRM_OK) return false;
+        d.op = Op;
+        d.new_label = bMeasureOnly ? -1 : Label;
+        d.erase_label = EraseLabel;
+        d.source[Label >> 5] = 1u << (Label & 31);
+        for (uint32_t& w : d.writable) w = 0xffffffffu;
+        tbrm_margin_result r{};
+        if (tbrm_margin_labels(RaymarchResources.Handle, &d, &r) != TBRM_OK) return false;
+        Out.SourceVoxels = r.source_voxels;
+        Out.ResultVoxels = r.result_voxels;
+        Out.Added = r.added;
+        Out.Removed = r.removed;
+        Out.Relabelled = r.relabelled;
+        for (int c = 0; c < 3; ++c) { Out.BoxMin[c] = r.bbox_min[c]; Out.BoxMax[c] = r.bbox_max[c]; Out.Reach[c] = r.reach[c]; Out.Weights[c] = d.weights[c]; }
+        Out.Limit = d.limit;
+        Out.Launches = r.launches;
+        return true;
+    }
+    bool ExpandLabelBy(double RadiusWorld, int Label, FMarginResult& Out) { return MarginLabel(TBRM_MARGIN_EXPAND, RadiusWorld, Label, Out); }
+    bool ShrinkLabelBy(double RadiusWorld, int Label, FMarginResult& Out, int EraseLabel = 0) { return MarginLabel(TBRM_MARGIN_SHRINK, RadiusWorld, Label, Out, EraseLabel); }
+    bool OpenLabelBy(double RadiusWorld, int Label, FMarginResult& Out, int EraseLabel = 0) { return MarginLabel(TBRM_MARGIN_OPEN, RadiusWorld, Label, Out, EraseLabel); }
+    bool CloseLabelBy(double RadiusWorld, int Label, FMarginResult& Out, int EraseLabel = 0) { return MarginLabel(TBRM_MARGIN_CLOSE, RadiusWorld, Label, Out, EraseLabel); }
 
     // The islands of one label (include/tbrm_islands.h; no counterpart in the reference): its connected components, ordered by size,
     // on the device. The four tools are parameter sets of one rule. Like the other label edits they request no recompute. They need a

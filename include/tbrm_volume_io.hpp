@@ -274,7 +274,9 @@ inline bool LoadMHDFileIntoVolume(ARaymarchVolume& Volume, const std::string& Fi
     if (OutInfo) *OutInfo = info;
     const int fmt = info.TbrmFormat();
     if (fmt < 0) return false;
-    return Volume.SetVolumeAsset(voxels.data(), info.Dimensions[0], info.Dimensions[1], info.Dimensions[2], fmt);
+    if (!Volume.SetVolumeAsset(voxels.data(), info.Dimensions[0], info.Dimensions[1], info.Dimensions[2], fmt)) return false;
+    for (int c = 0; c < 3; ++c) Volume.VoxelSpacing[c] = info.Spacing[c]; // what ARaymarchVolume::MarginLabel measures its radius in
+    return true;
 }
 inline bool LoadMHDFileIntoVolumeNormalized(ARaymarchVolume& Volume, const std::string& FileName, FVolumeInfo* OutInfo = nullptr)
 {

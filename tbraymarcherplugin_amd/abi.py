@@ -255,6 +255,34 @@ class ISLANDS_RESULT(C.Structure):  # tbrm_islands_result
                 ("bbox_min", C.c_int32 * 3), ("bbox_max", C.c_int32 * 3), ("table_entries", C.c_int32), ("reserved", C.c_int32)]
 
 
+# every symbol include/tbrm_margin.h declares (Euclidean margins of labels; tests/test_margin_abi.py checks the header against this list)
+MARGIN_SYMBOLS = ["tbrm_margin_abi_version", "tbrm_margin_labels", "tbrm_label_distance", "tbrm_host_margin_weights", "tbrm_margin_counters"]
+
+MARGIN_ABI_VERSION = 1  # TBRM_MARGIN_ABI_VERSION of include/tbrm_margin.h
+MARGIN_MAX_REACH = 64
+MARGIN_FAR = 0xFFFFFFFF
+MARGIN_EXPAND, MARGIN_SHRINK, MARGIN_OPEN, MARGIN_CLOSE = range(4)
+MARGIN_OPS = {"expand": MARGIN_EXPAND, "shrink": MARGIN_SHRINK, "open": MARGIN_OPEN, "close": MARGIN_CLOSE}
+
+
+class MARGIN_DESC(C.Structure):  # tbrm_margin_desc
+    _fields_ = [("origin", C.c_int32 * 3), ("extent", C.c_int32 * 3), ("op", C.c_int32), ("new_label", C.c_int32), ("erase_label", C.c_int32),
+                ("reserved", C.c_int32), ("weights", C.c_uint32 * 3), ("limit", C.c_uint32), ("source", C.c_uint32 * 8), ("writable", C.c_uint32 * 8)]
+
+
+class MARGIN_RESULT(C.Structure):  # tbrm_margin_result
+    _fields_ = [("source_voxels", C.c_uint64), ("result_voxels", C.c_uint64), ("added", C.c_uint64), ("removed", C.c_uint64), ("relabelled", C.c_uint64),
+                ("bbox_min", C.c_int32 * 3), ("bbox_max", C.c_int32 * 3), ("reach", C.c_int32 * 3), ("launches", C.c_int32)]
+
+
+def margin_weights(spacing, radius):
+    """tbrm_host_margin_weights: the voxel spacing (x, y, z) and a radius in the same unit -> ((w_x, w_y, w_z), limit)"""
+    s = (C.c_double * 3)(*[float(v) for v in spacing])
+    w, limit = (C.c_uint32 * 3)(), C.c_uint32()
+    check(load().tbrm_host_margin_weights(s, float(radius), w, C.byref(limit)))
+    return tuple(int(v) for v in w), int(limit.value)
+
+
 class ISLAND(C.Structure):  # tbrm_island
     _fields_ = [("voxels", C.c_uint64), ("first", C.c_int32 * 3), ("label", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -419,6 +447,14 @@ def load():
                           "(`python tbraymarcherplugin_amd/build.py --force`)")
     lib.tbrm_label_islands.argtypes = [vp, P(ISLANDS_DESC), P(ISLAND), C.c_int32, P(ISLANDS_RESULT)]
     lib.tbrm_islands_counters.argtypes = [vp, P(C.c_uint64 * 6)]
+    have = lib.tbrm_margin_abi_version() if hasattr(lib, "tbrm_margin_abi_version") else -1
+    if have != MARGIN_ABI_VERSION:
+        raise ImportError(f"{LIB_PATH} has margin ABI version {have}, this binding is written against {MARGIN_ABI_VERSION}: rebuild it "
+                          "(`python tbraymarcherplugin_amd/build.py --force`)")
+    lib.tbrm_margin_labels.argtypes = [vp, P(MARGIN_DESC), P(MARGIN_RESULT)]
+    lib.tbrm_label_distance.argtypes = [vp, P(MARGIN_DESC), C.c_int32, vp, C.c_size_t]
+    lib.tbrm_host_margin_weights.argtypes = [P(C.c_double * 3), C.c_double, P(C.c_uint32 * 3), P(C.c_uint32)]
+    lib.tbrm_margin_counters.argtypes = [vp, P(C.c_uint64 * 4)]
     _lib = lib
     return lib
 
@@ -857,6 +893,52 @@ class Resources:
         out = (C.c_uint64 * 4)()
         check(self.lib.tbrm_morph_counters(self.handle, C.byref(out)))
         return {k: int(out[i]) for i, k in enumerate(self.MORPH_COUNTERS)}
+
+    # Euclidean margins of labels (include/tbrm_margin.h): boxes, weights and reaches as (x, y, z)
+    def margin_desc(self, op, weights, limit, source, new_label, origin=None, extent=None, writable=None, erase_label=0):
+        """op: MARGIN_EXPAND .. MARGIN_CLOSE or its name; weights, limit: the squared distance's (margin_weights turns a spacing and a
+        radius into them); source, writable, new_label: as in morph_desc"""
+        d = MARGIN_DESC()
+        if extent is not None:
+            d.origin[:] = [int(v) for v in (origin if origin is not None else (0, 0, 0))]
+            d.extent[:] = [int(v) for v in extent]
+        d.op, d.new_label, d.erase_label = int(MARGIN_OPS.get(op, op)), int(new_label), int(erase_label)
+        d.weights[:] = [int(v) for v in weights]
+        d.limit = int(limit)
+        for l in source:
+            d.source[int(l) >> 5] |= 1 << (int(l) & 31)
+        if writable is None:
+            d.writable[:] = [0xFFFFFFFF] * 8
+        else:
+            for l in writable:
+                d.writable[int(l) >> 5] |= 1 << (int(l) & 31)
+        return d
+
+    def margin_labels(self, op, weights, limit, source, new_label, origin=None, extent=None, writable=None, erase_label=0):
+        """tbrm_margin_labels: {"source_voxels", "result_voxels", "added", "removed", "relabelled", "bbox_min", "bbox_max", "reach", "launches"}"""
+        d = self.margin_desc(op, weights, limit, source, new_label, origin, extent, writable, erase_label)
+        out = MARGIN_RESULT()
+        check(self.lib.tbrm_margin_labels(self.handle, C.byref(d), C.byref(out)))
+        return {"source_voxels": int(out.source_voxels), "result_voxels": int(out.result_voxels), "added": int(out.added), "removed": int(out.removed),
+                "relabelled": int(out.relabelled), "bbox_min": tuple(out.bbox_min[:]), "bbox_max": tuple(out.bbox_max[:]), "reach": tuple(out.reach[:]),
+                "launches": int(out.launches)}
+
+    def label_distance(self, source, weights, limit, origin=None, extent=None, inside=False):
+        """tbrm_label_distance: the weighted squared distance to the source set (inside: to its complement inside the volume) of the
+        box's voxels, uint32 [ez, ey, ex]; MARGIN_FAR above `limit`"""
+        d = self.margin_desc(MARGIN_EXPAND, weights, limit, source, -1, origin, extent)
+        whole = extent is None or tuple(int(v) for v in extent) == (0, 0, 0)
+        ex, ey, ez = (self.desc.dim_x, self.desc.dim_y, self.desc.dim_z) if whole else (int(v) for v in extent)
+        out = np.empty((max(ez, 0), max(ey, 0), max(ex, 0)), dtype=np.uint32)
+        check(self.lib.tbrm_label_distance(self.handle, C.byref(d), int(bool(inside)), out.ctypes.data, out.nbytes))
+        return out
+
+    MARGIN_COUNTERS = ("margin_calls", "launches", "bricks_computed", "bricks_written")
+
+    def margin_counters(self):
+        out = (C.c_uint64 * 4)()
+        check(self.lib.tbrm_margin_counters(self.handle, C.byref(out)))
+        return {k: int(out[i]) for i, k in enumerate(self.MARGIN_COUNTERS)}
 
     # the islands of a label (include/tbrm_islands.h): boxes and first voxels as (x, y, z)
     def islands_desc(self, source, connectivity=6, max_islands=0, min_voxels=0, keep_label=-1, label_step=0, drop_label=-1, spare_border=False,

@@ -442,6 +442,8 @@ enum Tunable : int {
                              // 1: a read-back per pass — the test hook). The result does not depend on it
     TUNE_MORPH_STEPS,        // tbrm_morph_labels: unit steps one launch of k_morph_steps iterates in a brick's 24^3 window (1 .. 8; 1: a launch
                              // per step — the test hook and the A/B switch). The result does not depend on it
+    TUNE_MARGIN_SKIP,        // tbrm_margin_labels, tbrm_label_distance: 1: bricks whose result the board classes give are not computed; 0: every
+                             // brick of the range is (the test hook and the A/B switch). The result does not depend on it
     TUNE_COUNT
 };
 int tune(Tunable t);

@@ -424,6 +424,11 @@ struct tbrm_resources {
     char* d_islands[3] = {nullptr, nullptr, nullptr};
     size_t islands_bytes[3]{};
     uint64_t islands_counters[6]{};    // tbrm_islands_counters ([4] is computed from islands_bytes)
+    // Euclidean margins (tbrm_api_margin.cpp; include/tbrm_margin.h): the scratch beyond d_grow — the bricks' states, the field after two
+    // axes, the staging of a distance map — sized to the largest brick range a call has needed so far
+    char* d_margin = nullptr;
+    size_t margin_bytes = 0;
+    uint64_t margin_counters[4]{};     // tbrm_margin_counters
 };
 
 
