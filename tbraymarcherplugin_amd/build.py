@@ -25,7 +25,7 @@ UNITS = [
     for m in (1, 0, 2, 5)
 ]
 SOURCES = sorted({u[0] for u in UNITS})
-HEADERS = ["tbrm_ray_replay.inc", "tbrm_ray_locate.inc", "tbrm_ray_leap.inc", "tbrm_internal.h", "tbrm_resources.h", "tbrm_device_math.h", "tbrm_device_sampling.h", "tbrm_host_math.h", "tbrm_light_chain.h", "tbrm_light_sweep.h", "tbrm_light_passes.h", "tbrm_stats_divisor.h", "tbrm_morph_plan.h", "tbrm_islands_rule.h", "tbrm_islands_kernels.h", "tbrm_margin_plan.h", "tbrm_margin_kernels.h", "tbrm_brick_boards.h", "tbrm_occ_footprint.h", "tbrm_box.h",
+HEADERS = ["tbrm_ray_replay.inc", "tbrm_ray_locate.inc", "tbrm_ray_leap.inc", "tbrm_internal.h", "tbrm_resources.h", "tbrm_device_math.h", "tbrm_device_sampling.h", "tbrm_host_math.h", "tbrm_light_chain.h", "tbrm_light_sweep.h", "tbrm_sweep_tile.h", "tbrm_light_passes.h", "tbrm_stats_divisor.h", "tbrm_morph_plan.h", "tbrm_islands_rule.h", "tbrm_islands_kernels.h", "tbrm_margin_plan.h", "tbrm_margin_kernels.h", "tbrm_brick_boards.h", "tbrm_occ_footprint.h", "tbrm_box.h",
            "../../include/tbrm.h", "../../include/tbrm_labels.h", "../../include/tbrm_color_lights.h", "../../include/tbrm_volume_region.h", "../../include/tbrm_volume_stats.h", "../../include/tbrm_view_cache.h", "../../include/tbrm_hit.h", "../../include/tbrm_segment.h", "../../include/tbrm_morphology.h", "../../include/tbrm_islands.h", "../../include/tbrm_margin.h"]
 
 # -ffp-contract=off + explicit fma is the arithmetic contract with the oracle (DESIGN.md "Arithmetic spec").

@@ -1,19 +1,12 @@
 // tbrm_light_sweep.h — what k_light_sweep (tbrm_light_sweep.hip, compiled as one translation unit per mode)
-// and the host-side planner (tbrm_light_plan.cpp) have to agree on: tile shape, LDS budget, hand-off record layout. Internal.
+// and the host-side planner (tbrm_light_plan.cpp) have to agree on: tile shape, LDS budget, hand-off record layout (the index rules: tbrm_sweep_tile.h). Internal.
 #pragma once
 #include "tbrm_internal.h"
+#include "tbrm_sweep_tile.h"
 
 namespace tbrm {
 
-constexpr int kSweepTile = 32;                         // a tile's edge: 32 x 32 pixels
-// LDS plane: 48 columns x 48 cells (tile + halo <= 14 + guard ring), COLUMN-major — a pixel's two taps of one column
-// (rows iy, iy + 1) are neighbours in memory and arrive as one register pair, ready for a packed lerp along x over (top, bottom)
-// — with an odd column stride of 49 floats: the 32 columns of a wave's lanes fall into 32 different banks
-constexpr int kSweepCols = 48;
-constexpr int kSweepColStride = kSweepTile + 17;
-constexpr int kSweepPlane = kSweepCols * kSweepColStride;
-constexpr int kSweepLvBrick = 528;                     // bytes per staged light-volume brick: 512 + 16, so that the four bricks
-                                                       // under a tile row start 4 banks apart
+// (the tile, the LDS plane and the staged brick: tbrm_sweep_tile.h)
 constexpr int kSweepRing = 8;                          // register ring of requested hand-off words (slices)
 constexpr int kSweepComputeWaves = kSweepTile / 4;     // a wave: 32 columns x 4 rows (two rows per lane)
 // + the hand-off waves + one factor loader per stream (an LDS-DMA costs its wave 60 - 180 cycles of issue: the eight of a
@@ -46,11 +39,6 @@ inline size_t sweep_lds_bytes(int mode, int slices, int lv_fmt)
 }
 
 inline int sweep_max_slices() { return 8 * kSweepFlagGroups; }
-
-// hand-off words a tile reads per slice and stream, in chunks of 64 (one per lane of the hand-off wave)
-inline int sweep_halo_chunks(int hx, int hy) { return (kSweepTile * (hx + hy) + hx * hy + 63) / 64; }
-// words of a tile's hand-off record per slice (and per stream of a float light volume): its hx columns and hy rows away from the light
-inline int sweep_record_words(int hx, int hy) { return kSweepTile * (hx + hy); }
 
 // one translation unit per mode: tbrm_light_sweep.hip compiled with -DTBRM_SWEEP_UNIT_MODE
 template <int MODE>

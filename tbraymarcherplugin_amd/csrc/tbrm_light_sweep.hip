@@ -191,7 +191,7 @@ __device__ __forceinline__ void sweep_tile(const ChunkParams& p, const SweepPara
         if ((q.debug & 2) != 0 && q.stamps != nullptr && threadIdx.x == 0) q.stamps[4 * tile_lin + 0] = wall_clock64();
     }
     // LDS plane coordinates of tile pixel (0, 0): behind the guard ring and whatever halo lies on the low side
-    const int ox = 1 + max(q.sx < 0 ? hx : 0, (RREC && q.r_sx < 0) ? q.r_hx : 0), oy = 1 + max(q.sy < 0 ? hy : 0, (RREC && q.r_sy < 0) ? q.r_hy : 0);
+    const int ox = sweep_plane_origin(q.sx, hx, RREC ? q.r_sx : 0, RREC ? q.r_hx : 0), oy = sweep_plane_origin(q.sy, hy, RREC ? q.r_sy : 0, RREC ? q.r_hy : 0);
     const bool down = p.dir < 0;
     const int layer0 = p.j0 >> 3;
 
@@ -232,6 +232,8 @@ __device__ __forceinline__ void sweep_tile(const ChunkParams& p, const SweepPara
     }
 
     // ---- light-volume bricks: a layer = the 4 x 4 bricks under the tile, in pieces of 16 bytes, one per compute thread ----
+    // (sweep_piece, tbrm_sweep_tile.h, is this arithmetic as a function, checked on the host; called here it moves the chained kernels'
+    // spilled scalar registers, so it stays written out)
     constexpr int dim_u = AXIS == 0 ? 1 : 0, dim_v = AXIS == 2 ? 1 : 2, dim_s = AXIS; // plane axes -> volume axes
     const int lbn[3] = {p.lv_bnx, p.lv_bnxy / p.lv_bnx, (p.lv_dims[2] + 7) >> 3};
     const int piece = (int) threadIdx.x & (NTC - 1);
@@ -283,32 +285,22 @@ __device__ __forceinline__ void sweep_tile(const ChunkParams& p, const SweepPara
     uint32_t dep_epoch = link.in_epoch & 0xffffu;
     uint32_t* prog_word = link.prog_out + tile_lin;
     if constexpr (CHAIN) {
-        const int a = link.in_axis;
-        const int ua = a == 0 ? 1 : 0, va = a == 2 ? 1 : 2;
-        int lo[3]; // first brick of the tile per volume axis (along this pass's axis: filled in per layer)
+        int lo[3]; // first brick of the tile per volume axis (along this pass's axis: a layer at a time)
         lo[dim_u] = base_x >> 3;
         lo[dim_v] = base_y >> 3;
         lo[dim_s] = 0;
-        const int lo_a = a == 0 ? lo[0] : (a == 1 ? lo[1] : lo[2]), lo_u = ua == 0 ? lo[0] : lo[1], lo_v = va == 1 ? lo[1] : lo[2];
-        int c0;
-        if (dim_s == a) { // same axis: the same tile of the pass before, layer by layer
-            c0 = (lo_v >> 2) * link.in_tiles_x + (lo_u >> 2);
-            dep_n0 = link.in_down ? link.in_layer0 + 1 : 1 - link.in_layer0;
-            dep_n1 = link.in_down ? -1 : 1;
-        } else {
-            // the tile's four bricks along a, [lo_a, lo_a + 4): the last of them in the pass before's order
-            dep_n0 = (link.in_down ? link.in_layer0 - lo_a : lo_a + 3 - link.in_layer0) + 1;
-            if (dim_s == ua) { c0 = (lo_v >> 2) * link.in_tiles_x; dep_c1 = 1; }
-            else { c0 = lo_u >> 2; dep_c1 = link.in_tiles_x; }
-        }
+        const SweepDep d = sweep_chain_dep(dim_s, link.in_axis, link.in_tiles_x, link.in_down, link.in_layer0, lo);
+        const int c0 = d.c0;
+        dep_c1 = d.c1; dep_n0 = d.n0; dep_n1 = d.n1;
         dep_base = link.prog_in + c0; // (the launch's first pass: in_G = 0 — it needs nothing of the words it is pointed at, its own)
         asm volatile("" : "+v"(dep_c1), "+v"(dep_n0), "+v"(dep_n1), "+v"(dep_G), "+v"(dep_epoch));
         asm volatile("" : "+v"(dep_base), "+v"(prog_word));
     }
     auto depends_on = [&](int g, uint32_t& needed) -> const uint32_t* {
         const int L = layer_of(min(g, G - 1));
-        needed = (uint32_t) min(max(dep_n0 + dep_n1 * L, 0), dep_G); // (bricks past the volume's end belong to no layer of the pass before)
-        return dep_base + dep_c1 * (L >> 2);
+        const SweepDep d = {0, dep_c1, dep_n0, dep_n1}; // (c0 is in dep_base already: the word is dep_base[c1 * (L >> 2)])
+        needed = sweep_dep_needed(d, L, dep_G);
+        return dep_base + sweep_dep_word(d, L);
     };
     auto wait_for_layer = [&](int g) { // blocking form: the tile's first two layers
         uint32_t needed = 0;
@@ -345,72 +337,42 @@ __device__ __forceinline__ void sweep_tile(const ChunkParams& p, const SweepPara
         // =================================================== the hand-off wave(s) ================================================
         // A tile publishes E_x = its hx columns and E_y = its hy rows on the side AWAY from the light, words [row][column of
         // E_x] then [row of E_y][column]; its halo is the same cells of the three upstream neighbours.
-        const int e0x = q.sx > 0 ? 0 : T - hx, e0y = q.sy > 0 ? 0 : T - hy;
+        // (sweep_published_cell / sweep_halo_word, tbrm_sweep_tile.h)
         int pub_cell[HC];      // LDS cell of the word this lane publishes (chunk h: word 64 h + lane), < 0: none
         bool hal_on[HC];       // this lane fetches halo word 64 h + lane
         int hal_dst[HC];
         uint32_t hal_src[HC];  // neighbour tile * RW + word
+        // halo word w of a stream of geometry g: whether the lane fetches it, the LDS cell it lands in, its place in a slice's
+        // records ([tile][stride words]); off: nothing is fetched
+        auto halo_entry = [&](int w, const SweepSides& g, int stride, bool off, bool& on, int& dst, uint32_t& src) {
+            const SweepHaloWord hw = sweep_halo_word(w, g, T, tile_x, tile_y);
+            const int ntx = hw.ntx, nty = hw.nty;
+            // (a neighbour's pixels beyond the buffer are not handed over: their cells hold the border colour from the start)
+            on = hw.on && (unsigned) ntx < (unsigned) p.tiles_x && (unsigned) nty < (unsigned) p.tiles_y &&
+                 (unsigned) (base_x + hw.cx) < (unsigned) p.W && (unsigned) (base_y + hw.cy) < (unsigned) p.H;
+            if (off) on = false;
+            dst = sweep_plane_cell(ox, oy, hw.cx, hw.cy);
+            src = on ? (uint32_t) ((nty * p.tiles_x + ntx) * stride + hw.word) : 0u;
+        };
+        const SweepSides sides = {q.sx, q.sy, hx, hy};
 #pragma unroll
         for (int h = 0; h < HC; ++h) {
             const int w = h * 64 + lane;
-            {
-                int cx = 0, cy = 0;
-                const bool on = w < RW;
-                if (w < T * hx) { cy = w / max(hx, 1); cx = e0x + (w - cy * hx); }
-                else { const int m = w - T * hx; cy = e0y + m / T; cx = m % T; }
-                pub_cell[h] = on ? (ox + cx) * CS + oy + cy : -1;
-            }
-            const int nx = T * hx, ny = T * hy, nc = hx * hy;
-            int ntx = tile_x, nty = tile_y, word = 0, cxh = 0, cyh = 0; // neighbour tile, its word, the halo cell in tile coordinates
-            bool on = false;
-            if (w < nx) { const int row = w / max(hx, 1), kx = w - row * hx; ntx += q.sx; word = row * hx + kx; cxh = (q.sx > 0 ? T : -hx) + kx; cyh = row; on = true; }
-            else if (w < nx + ny) { const int m = w - nx, ky = m / T, col = m - ky * T; nty += q.sy; word = nx + ky * T + col; cxh = col; cyh = (q.sy > 0 ? T : -hy) + ky; on = true; }
-            else if (w < nx + ny + nc) {
-                const int m = w - nx - ny, ky = m / max(hx, 1), kx = m - ky * hx;
-                ntx += q.sx; nty += q.sy;
-                word = (e0y + ky) * hx + kx;
-                cxh = (q.sx > 0 ? T : -hx) + kx; cyh = (q.sy > 0 ? T : -hy) + ky;
-                on = true;
-            }
-            // (a neighbour's pixels beyond the buffer are not handed over: their cells hold the border colour from the start)
-            on = on && (unsigned) ntx < (unsigned) p.tiles_x && (unsigned) nty < (unsigned) p.tiles_y &&
-                 (unsigned) (base_x + cxh) < (unsigned) p.W && (unsigned) (base_y + cyh) < (unsigned) p.H;
-            if (q.debug & 1) on = false;
-            hal_on[h] = on;
-            hal_dst[h] = (ox + cxh) * CS + oy + cyh;
-            hal_src[h] = on ? (uint32_t) ((nty * p.tiles_x + ntx) * RWS + word) : 0u;
+            int cx, cy;
+            pub_cell[h] = sweep_published_cell(w, sides, T, cx, cy) ? sweep_plane_cell(ox, oy, cx, cy) : -1;
+            halo_entry(w, sides, RWS, (q.debug & 1) != 0, hal_on[h], hal_dst[h], hal_src[h]);
         }
         // RREC: stream r's halo cells, the same construction with stream r's geometry; their words were written by the launch
         // before this one (tag r_epoch), tile by tile in the same [slice][tile][word] layout
         bool rh_on[HC];
         int rh_dst[HC];
         uint32_t rh_src[HC];
-        const int r_RW = T * q.r_hx + T * q.r_hy;
+        const int r_RW = sweep_record_words(q.r_hx, q.r_hy);
         const uint32_t r_rec_slice = (uint32_t) (n_tiles * r_RW);
         if constexpr (RREC) {
-            const int rhx = q.r_hx, rhy = q.r_hy;
-            const int re0y = q.r_sy > 0 ? 0 : T - rhy;
+            const SweepSides r_sides = {q.r_sx, q.r_sy, q.r_hx, q.r_hy};
 #pragma unroll
-            for (int h = 0; h < HC; ++h) {
-                const int w = h * 64 + lane;
-                const int nx = T * rhx, ny = T * rhy, nc = rhx * rhy;
-                int ntx = tile_x, nty = tile_y, word = 0, cxh = 0, cyh = 0;
-                bool on = false;
-                if (w < nx) { const int row = w / max(rhx, 1), kx = w - row * rhx; ntx += q.r_sx; word = row * rhx + kx; cxh = (q.r_sx > 0 ? T : -rhx) + kx; cyh = row; on = true; }
-                else if (w < nx + ny) { const int m = w - nx, ky = m / T, col = m - ky * T; nty += q.r_sy; word = nx + ky * T + col; cxh = col; cyh = (q.r_sy > 0 ? T : -rhy) + ky; on = true; }
-                else if (w < nx + ny + nc) {
-                    const int m = w - nx - ny, ky = m / max(rhx, 1), kx = m - ky * rhx;
-                    ntx += q.r_sx; nty += q.r_sy;
-                    word = (re0y + ky) * rhx + kx;
-                    cxh = (q.r_sx > 0 ? T : -rhx) + kx; cyh = (q.r_sy > 0 ? T : -rhy) + ky;
-                    on = true;
-                }
-                on = on && (unsigned) ntx < (unsigned) p.tiles_x && (unsigned) nty < (unsigned) p.tiles_y &&
-                     (unsigned) (base_x + cxh) < (unsigned) p.W && (unsigned) (base_y + cyh) < (unsigned) p.H;
-                rh_on[h] = on;
-                rh_dst[h] = (ox + cxh) * CS + oy + cyh;
-                rh_src[h] = on ? (uint32_t) ((nty * p.tiles_x + ntx) * r_RW + word) : 0u;
-            }
+            for (int h = 0; h < HC; ++h) halo_entry(h * 64 + lane, r_sides, r_RW, false, rh_on[h], rh_dst[h], rh_src[h]);
         }
         auto handoff = [&](auto pub_c, auto con_c) {
         constexpr bool PUB = decltype(pub_c)::value, CON = decltype(con_c)::value;
@@ -606,16 +568,13 @@ __device__ __forceinline__ void sweep_tile(const ChunkParams& p, const SweepPara
         for (int k = 0; k < R; ++k) {
             const int r = r0 + k, py = base_y + r;
             in_pl[k] = in_x && py < p.H;
-            own[k] = (ox + c) * CS + oy + r;
+            own[k] = sweep_plane_cell(ox, oy, c, r);
             own_idx[k] = in_pl[k] ? (uint32_t) (py * p.W + px) : 0u;
-            const uint32_t lb = (uint32_t) ((r >> 3) * 4 + (c >> 3)) * (uint32_t) LVB;
-            if (AXIS == 0) lv_at[k] = lb + (uint32_t) (r & 7) * 64u + (uint32_t) (c & 7) * 8u;
-            else if (AXIS == 1) lv_at[k] = lb + (uint32_t) (r & 7) * 64u + (uint32_t) (c & 7);
-            else lv_at[k] = lb + (uint32_t) (r & 7) * 8u + (uint32_t) (c & 7);
+            lv_at[k] = sweep_lv_at<AXIS>(c, r);
         }
         static_assert(R == 2, "a lane's two rows share a brick (r0 is even)");
-        lv_at[1] = lv_at[0] + (AXIS == 2 ? 8u : 64u); // (said so that the second voxel's address is the first one's plus an immediate)
-        constexpr uint32_t kLvStep = AXIS == 0 ? 1u : (AXIS == 1 ? 8u : 64u);
+        lv_at[1] = lv_at[0] + sweep_lv_row_step(AXIS); // (said so that the second voxel's address is the first one's plus an immediate)
+        constexpr uint32_t kLvStep = sweep_lv_step(AXIS);
         uint32_t lv_voxel[R] = {0, 0}; // F32: the pixel's voxel in the bricked light volume, slice 0 of the volume (elements)
         if constexpr (F32) {
 #pragma unroll
@@ -943,37 +902,39 @@ static hipError_t launch_sweep5(const ChunkParams& p, const SweepParams& q, hipS
     hipLaunchKernelGGL((k_light_sweep<MODE, AXIS, PF, HC, RREC, LFMT>), dim3(p.tiles_x * p.tiles_y), dim3(sweep_threads(MODE)), sweep_lds_bytes(MODE, p.n_steps, LFMT), s, p, q);
     return hipGetLastError();
 }
-// Requests run two slices ahead of their use (three for the six-chunk records, whose ring of three slices is what fits the
-// registers): distances 3, 4 and 6 lost to 2 in every measurement of rounds 3 and 4 and are not instantiated.
+// (PF, HC) for hc chunks of hand-off words per slice: (2, 2) up to two chunks, (2, 3) up to three, (3, 6) up to six. Requests run two
+// slices ahead of their use (three for the six-chunk records, whose ring of three slices is what fits the registers: six words per lane
+// and stream): distances 3, 4 and 6 lost to 2 in every measurement of rounds 3 and 4 and are not instantiated. RUNGS: the choices a
+// caller has kernels for — bit 0: (2, 2), bit 1: (2, 3), bit 2: (3, 6); a geometry whose own choice is not among them takes the next
+// larger one, one beyond the largest none (sweep_fit rules these out). go(PF, HC) launches.
+template <int RUNGS, class F>
+static hipError_t sweep_pf_hc(int hc, F&& go)
+{
+    if constexpr ((RUNGS & 1) != 0) { if (hc <= 2) return go(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{}); }
+    if constexpr ((RUNGS & 2) != 0) { if (hc <= 3) return go(std::integral_constant<int, 2>{}, std::integral_constant<int, 3>{}); }
+    if constexpr ((RUNGS & 4) != 0) { if (hc <= 6) return go(std::integral_constant<int, 3>{}, std::integral_constant<int, 6>{}); }
+    return hipErrorInvalidConfiguration;
+}
 template <int MODE, int AXIS>
 static hipError_t launch_sweep4(const ChunkParams& p, const SweepParams& q, hipStream_t s)
 {
-    const int hc = sweep_halo_chunks(q.hx, q.hy);
+    const int hc = sweep_halo_chunks(q.hx, q.hy), hc2 = std::max(hc, sweep_halo_chunks(q.r_hx, q.r_hy)); // (hc2: a stream from records, sweep_fit)
+    auto go = [&](auto rrec, auto lfmt) {
+        return [&](auto pf, auto hcs) { return launch_sweep5<MODE, AXIS, decltype(pf)::value, decltype(hcs)::value, decltype(rrec)::value, decltype(lfmt)::value>(p, q, s); };
+    };
+    using U8 = std::integral_constant<int, FMT_U8>;
+    using F32 = std::integral_constant<int, FMT_F32>;
     if (q.lv_f32) { // float light volumes: Add, fused Change, planes; up to three words per lane and stream (sweep_fit)
         if constexpr (MODE == PASS_ADD || MODE == PASS_CHANGE || MODE == PASS_PLANES) {
-            if (q.r_from_records) {
-                if constexpr (MODE == PASS_CHANGE) {
-                    if (std::max(hc, sweep_halo_chunks(q.r_hx, q.r_hy)) <= 3) return launch_sweep5<MODE, AXIS, 2, 3, true, FMT_F32>(p, q, s);
-                }
-                return hipErrorInvalidConfiguration;
-            }
-            if (hc <= 2) return launch_sweep5<MODE, AXIS, 2, 2, false, FMT_F32>(p, q, s);
-            if (hc <= 3) return launch_sweep5<MODE, AXIS, 2, 3, false, FMT_F32>(p, q, s);
+            if (!q.r_from_records) return sweep_pf_hc<1 | 2>(hc, go(std::false_type{}, F32{}));
+            if constexpr (MODE == PASS_CHANGE) return sweep_pf_hc<2>(hc2, go(std::true_type{}, F32{}));
         }
         return hipErrorInvalidConfiguration;
     }
     if constexpr (MODE == PASS_CHANGE) {
-        if (q.r_from_records) { // (sweep_fit: both streams' words fit three per lane)
-            const int hc2 = std::max(hc, sweep_halo_chunks(q.r_hx, q.r_hy));
-            if (hc2 <= 3) return launch_sweep5<MODE, AXIS, 2, 3, true>(p, q, s);
-            if (hc2 <= 6) return launch_sweep5<MODE, AXIS, 3, 6, true>(p, q, s);
-            return hipErrorInvalidConfiguration;
-        }
+        if (q.r_from_records) return sweep_pf_hc<2 | 4>(hc2, go(std::true_type{}, U8{}));
     }
-    if (hc <= 2) return launch_sweep5<MODE, AXIS, 2, 2>(p, q, s);
-    if (hc <= 3) return launch_sweep5<MODE, AXIS, 2, 3>(p, q, s);
-    if (hc <= 6) return launch_sweep5<MODE, AXIS, 3, 6>(p, q, s); // (six words per lane and stream: a ring of three slices is what fits the registers)
-    return hipErrorInvalidConfiguration; // (sweep_fit rules these out)
+    return sweep_pf_hc<1 | 2 | 4>(hc, go(std::false_type{}, U8{}));
 }
 template <int MODE>
 hipError_t launch_sweep_unit(const ChunkParams& p, const SweepParams& q, hipStream_t s)
@@ -1004,9 +965,8 @@ hipError_t launch_sweep_chain_unit(const SweepChainArgs& c, hipStream_t s)
             hipLaunchKernelGGL(kernel, dim3(grid), dim3(sweep_threads(MODE)), lds, s, c);
             return hipGetLastError();
         };
-        if (hc <= 2) return go(k_light_sweep_chain<MODE, 2, 2>);
-        if (hc <= 3) return go(k_light_sweep_chain<MODE, 2, 3>);
-        return hipErrorInvalidConfiguration; // (the host chains passes of up to three chunks)
+        // (the host chains passes of up to three chunks)
+        return sweep_pf_hc<1 | 2>(hc, [&](auto pf, auto hcs) { return go(k_light_sweep_chain<MODE, decltype(pf)::value, decltype(hcs)::value>); });
     }
 }
 
