@@ -5,7 +5,7 @@
 //
 //   g++ -std=c++17 -O2 -I include examples/render_mhd.cpp -o render_mhd -L tbraymarcherplugin_amd/lib -ltbrm -lz
 //       (plus -Wl,-rpath,$PWD/tbraymarcherplugin_amd/lib -Wl,-rpath,/opt/rocm/lib to run it in place)
-//   ./render_mhd volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]] [--margin OP,RADIUS[,LABEL]] [--islands OP,N[,LABEL]]
+//   ./render_mhd volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]] [--margin OP,RADIUS[,LABEL]] [--smooth RADIUS[,ITERATIONS[,LABEL]]] [--islands OP,N[,LABEL]]
 //       --light-color: the key light's colour (components in [0, 1]) on an RGB light volume (include/tbrm_color_lights.h); the fill stays white
 //       --auto-window: the window comes from the data (ARaymarchVolume::AutoWindow, include/tbrm_volume_stats.h): the span between
 //                      the LOW and HIGH percentiles of the value histogram, 0.01,0.99 when not given
@@ -21,7 +21,11 @@
 //                      include/tbrm_margin.h): OP is expand, shrink, open or close, RADIUS a distance in the units of the file's
 //                      ElementSpacing — a ball on the anisotropic grid; voxels that leave the label get label 0; printed as one
 //                      "margin" line
-//       --islands: after --grow, --morph and --margin, the islands of label LABEL (the grown label when not given) (ARaymarchVolume::KeepLargestIslands
+//       --smooth: after --grow, --morph and --margin, the median of label LABEL (the grown label when not given) (ARaymarchVolume::MedianLabel,
+//                      include/tbrm_smooth.h): a voxel keeps or gets the label where a strict majority of the box of RADIUS round it —
+//                      a distance in the units of the file's ElementSpacing, rounded to voxels per axis — has it; ITERATIONS passes
+//                      (1 when not given); voxels that leave the label get label 0; printed as one "smooth" line
+//       --islands: after --grow, --morph, --margin and --smooth, the islands of label LABEL (the grown label when not given) (ARaymarchVolume::KeepLargestIslands
 //                      and its kin, include/tbrm_islands.h), 6-connected: OP is keep (the N largest stay, the others get label 0), remove
 //                      (islands of fewer than N voxels get label 0), split (the N largest get LABEL, LABEL + 1, ..) or fill (what the
 //                      label encloses, up to N voxels a hole, 0: of any size, joins it); printed as one "islands" line
@@ -85,6 +89,17 @@ int main(int argc, char** argv)
     double margin_radius = 0.0;
     int margin_label = -1;
     bool margin = false;
+    double smooth_radius = 0.0;
+    int smooth_iterations = 1, smooth_label = -1;
+    bool smooth = false;
+    for (int i = 1; i + 1 < argc; ++i)
+        if (!std::strcmp(argv[i], "--smooth")) {
+            if (std::sscanf(argv[i + 1], "%lf,%d,%d", &smooth_radius, &smooth_iterations, &smooth_label) < 1) { argc = 0; break; }
+            smooth = true;
+            for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
+            argc -= 2;
+            break;
+        }
     for (int i = 1; i + 1 < argc; ++i)
         if (!std::strcmp(argv[i], "--margin")) {
             if (std::sscanf(argv[i + 1], "%7[a-z],%lf,%d", margin_op, &margin_radius, &margin_label) < 2) { argc = 0; break; }
@@ -114,7 +129,7 @@ int main(int argc, char** argv)
             break;
         }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]] [--margin OP,RADIUS[,LABEL]] [--islands OP,N[,LABEL]]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]] [--margin OP,RADIUS[,LABEL]] [--smooth RADIUS[,ITERATIONS[,LABEL]]] [--islands OP,N[,LABEL]]\n", argv[0]);
         return 2;
     }
     const int width = argc > 3 ? std::atoi(argv[3]) : 512, height = argc > 4 ? std::atoi(argv[4]) : 512;
@@ -213,7 +228,19 @@ int main(int argc, char** argv)
                     (unsigned long long) m.SourceVoxels, (unsigned long long) m.ResultVoxels, (unsigned long long) m.Added, (unsigned long long) m.Removed,
                     m.BoxMin[0], m.BoxMin[1], m.BoxMin[2], m.BoxMax[0], m.BoxMax[1], m.BoxMax[2], m.Launches);
     }
-    if (islands) { // after the grow, the morphology and the margin, before the frame
+    if (smooth) { // after the grow, the morphology and the margin, before the frame
+        if (smooth_label < 0) smooth_label = grow_label;
+        FSmoothResult m;
+        if (!volume.MedianLabel(smooth_label, smooth_radius, smooth_iterations, m)) {
+            std::fprintf(stderr, "smooth failed: %s\n", tbrm_last_error());
+            return 1;
+        }
+        std::printf("smooth %.9g iterations %d label %d radius %d %d %d reach %d %d %d source %llu result %llu added %llu removed %llu box %d %d %d .. %d %d %d launches %d\n",
+                    smooth_radius, smooth_iterations, smooth_label, m.Radius[0], m.Radius[1], m.Radius[2], m.Reach[0], m.Reach[1], m.Reach[2],
+                    (unsigned long long) m.SourceVoxels, (unsigned long long) m.ResultVoxels, (unsigned long long) m.Added, (unsigned long long) m.Removed,
+                    m.BoxMin[0], m.BoxMin[1], m.BoxMin[2], m.BoxMax[0], m.BoxMax[1], m.BoxMax[2], m.Launches);
+    }
+    if (islands) { // after the grow, the morphology, the margin and the smoothing, before the frame
         if (islands_label < 0) islands_label = grow_label;
         FIslandsResult r;
         bool known = true, ok = false;

@@ -24,6 +24,7 @@
 #include "tbrm_morphology.h"
 #include "tbrm_islands.h"
 #include "tbrm_margin.h"
+#include "tbrm_smooth.h"
 
 #include <algorithm>
 #include <cmath>
@@ -301,6 +302,17 @@ struct FMarginResult {
     int Launches = 0;
 };
 
+// What a smoothing call found (include/tbrm_smooth.h): ARaymarchVolume::SmoothLabel and MedianLabel
+struct FSmoothResult {
+    uint64_t SourceVoxels = 0, ResultVoxels = 0; // the label's voxels before and the filter's result, inside the box
+    uint64_t Added = 0, Removed = 0;             // voxels that joined / left the label
+    uint64_t Relabelled = 0;                     // label bytes that changed
+    int BoxMin[3] = {0, 0, 0}, BoxMax[3] = {-1, -1, -1}; // of what joined or left, inclusive; nothing: the volume's size and -1
+    int Radius[3] = {0, 0, 0};                   // voxels per axis the radius and the spacing became (tbrm_host_smooth_radii)
+    int Reach[3] = {0, 0, 0};                    // Iterations times that
+    int Launches = 0;
+};
+
 // What an island call found (include/tbrm_islands.h): ARaymarchVolume::KeepLargestIslands / RemoveSmallIslands / SplitIslands /
 // FillLabelHoles
 struct FIslandsResult {
@@ -333,7 +345,7 @@ public:
     // (not in the reference) an RGB light volume lit by the lights' LightColor; read when the resources are initialised
     // (SetVolumeAsset). false: a mono handle, and LightColor is ignored. The batched reset has no colour form: light by light.
     bool bColoredLights = false;
-    // (not in the reference) the voxel spacing MarginLabel measures its radius in: LoadMHDFileIntoVolume sets it to the file's
+    // (not in the reference) the voxel spacing MarginLabel and SmoothLabel measure their radius in: LoadMHDFileIntoVolume sets it to the file's
     // ElementSpacing, SetVolumeAsset (a new asset, of unknown spacing) resets it; all zero: unit spacing
     double VoxelSpacing[3] = {0, 0, 0};
 
@@ -551,6 +563,41 @@ public:
     bool ShrinkLabelBy(double RadiusWorld, int Label, FMarginResult& Out, int EraseLabel = 0) { return MarginLabel(TBRM_MARGIN_SHRINK, RadiusWorld, Label, Out, EraseLabel); }
     bool OpenLabelBy(double RadiusWorld, int Label, FMarginResult& Out, int EraseLabel = 0) { return MarginLabel(TBRM_MARGIN_OPEN, RadiusWorld, Label, Out, EraseLabel); }
     bool CloseLabelBy(double RadiusWorld, int Label, FMarginResult& Out, int EraseLabel = 0) { return MarginLabel(TBRM_MARGIN_CLOSE, RadiusWorld, Label, Out, EraseLabel); }
+
+    // Smoothing of one label (include/tbrm_smooth.h; no counterpart in the reference): a voxel belongs to the label afterwards where
+    // more than RankNum / RankDen of the box of RadiusInVolumeUnits round it — a distance in the unit of VoxelSpacing (voxels when
+    // there is none), rounded to voxels per axis, the box clipped to the volume — does now; Iterations passes, on the device. Voxels
+    // that join get Label (over any label), voxels that leave get EraseLabel; bMeasureOnly counts them and writes nothing. Like the
+    // other label edits it requests no recompute. Needs a label volume.
+    bool SmoothLabel(int Label, double RadiusInVolumeUnits, int Iterations, FSmoothResult& Out, int RankNum = 1, int RankDen = 2, int EraseLabel = 0,
+                     bool bMeasureOnly = false)
+    {
+        Out = FSmoothResult{};
+        if (!RaymarchResources.Handle || Label < 0 || Label > 255) return false;
+        const bool unit = VoxelSpacing[0] == 0.0 && VoxelSpacing[1] == 0.0 && VoxelSpacing[2] == 0.0;
+        const double spacing[3] = {unit ? 1.0 : VoxelSpacing[0], unit ? 1.0 : VoxelSpacing[1], unit ? 1.0 : VoxelSpacing[2]};
+        tbrm_smooth_desc d{};
+        if (tbrm_host_smooth_radii(spacing, RadiusInVolumeUnits, d.radius) != TBRM_OK) return false;
+        d.rank_num = RankNum;
+        d.rank_den = RankDen;
+        d.iterations = Iterations;
+        d.new_label = bMeasureOnly ? -1 : Label;
+        d.erase_label = EraseLabel;
+        d.source[Label >> 5] = 1u << (Label & 31);
+        for (uint32_t& w : d.writable) w = 0xffffffffu;
+        tbrm_smooth_result r{};
+        if (tbrm_smooth_labels(RaymarchResources.Handle, &d, &r) != TBRM_OK) return false;
+        Out.SourceVoxels = r.source_voxels;
+        Out.ResultVoxels = r.result_voxels;
+        Out.Added = r.added;
+        Out.Removed = r.removed;
+        Out.Relabelled = r.relabelled;
+        for (int c = 0; c < 3; ++c) { Out.BoxMin[c] = r.bbox_min[c]; Out.BoxMax[c] = r.bbox_max[c]; Out.Radius[c] = d.radius[c]; Out.Reach[c] = r.reach[c]; }
+        Out.Launches = r.launches;
+        return true;
+    }
+    // the median: a strict majority of the box
+    bool MedianLabel(int Label, double RadiusInVolumeUnits, int Iterations, FSmoothResult& Out) { return SmoothLabel(Label, RadiusInVolumeUnits, Iterations, Out, 1, 2); }
 
     // The islands of one label (include/tbrm_islands.h; no counterpart in the reference): its connected components, ordered by size,
     // on the device. The four tools are parameter sets of one rule. Like the other label edits they request no recompute. They need a

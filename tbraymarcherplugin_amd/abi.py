@@ -283,6 +283,35 @@ def margin_weights(spacing, radius):
     return tuple(int(v) for v in w), int(limit.value)
 
 
+# every symbol include/tbrm_smooth.h declares (smoothing of labels; tests/test_smooth_abi.py checks the header against this list)
+SMOOTH_SYMBOLS = ["tbrm_smooth_abi_version", "tbrm_smooth_labels", "tbrm_host_smooth_radii", "tbrm_smooth_counters"]
+
+SMOOTH_ABI_VERSION = 1  # TBRM_SMOOTH_ABI_VERSION of include/tbrm_smooth.h
+SMOOTH_MAX_RADIUS = 16
+SMOOTH_MAX_ITERATIONS = 64
+SMOOTH_MAX_REACH = 64
+SMOOTH_MAX_RANK_DEN = 256
+
+
+class SMOOTH_DESC(C.Structure):  # tbrm_smooth_desc
+    _fields_ = [("origin", C.c_int32 * 3), ("extent", C.c_int32 * 3), ("radius", C.c_int32 * 3), ("rank_num", C.c_int32), ("rank_den", C.c_int32),
+                ("iterations", C.c_int32), ("new_label", C.c_int32), ("erase_label", C.c_int32), ("reserved", C.c_int32),
+                ("source", C.c_uint32 * 8), ("writable", C.c_uint32 * 8)]
+
+
+class SMOOTH_RESULT(C.Structure):  # tbrm_smooth_result
+    _fields_ = [("source_voxels", C.c_uint64), ("result_voxels", C.c_uint64), ("added", C.c_uint64), ("removed", C.c_uint64), ("relabelled", C.c_uint64),
+                ("bbox_min", C.c_int32 * 3), ("bbox_max", C.c_int32 * 3), ("reach", C.c_int32 * 3), ("launches", C.c_int32)]
+
+
+def smooth_radii(spacing, radius):
+    """tbrm_host_smooth_radii: the voxel spacing (x, y, z) and a radius in the same unit -> (r_x, r_y, r_z)"""
+    s = (C.c_double * 3)(*[float(v) for v in spacing])
+    r = (C.c_int32 * 3)()
+    check(load().tbrm_host_smooth_radii(s, float(radius), r))
+    return tuple(int(v) for v in r)
+
+
 class ISLAND(C.Structure):  # tbrm_island
     _fields_ = [("voxels", C.c_uint64), ("first", C.c_int32 * 3), ("label", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -455,6 +484,13 @@ def load():
     lib.tbrm_label_distance.argtypes = [vp, P(MARGIN_DESC), C.c_int32, vp, C.c_size_t]
     lib.tbrm_host_margin_weights.argtypes = [P(C.c_double * 3), C.c_double, P(C.c_uint32 * 3), P(C.c_uint32)]
     lib.tbrm_margin_counters.argtypes = [vp, P(C.c_uint64 * 4)]
+    have = lib.tbrm_smooth_abi_version() if hasattr(lib, "tbrm_smooth_abi_version") else -1
+    if have != SMOOTH_ABI_VERSION:
+        raise ImportError(f"{LIB_PATH} has smooth ABI version {have}, this binding is written against {SMOOTH_ABI_VERSION}: rebuild it "
+                          "(`python tbraymarcherplugin_amd/build.py --force`)")
+    lib.tbrm_smooth_labels.argtypes = [vp, P(SMOOTH_DESC), P(SMOOTH_RESULT)]
+    lib.tbrm_host_smooth_radii.argtypes = [P(C.c_double * 3), C.c_double, P(C.c_int32 * 3)]
+    lib.tbrm_smooth_counters.argtypes = [vp, P(C.c_uint64 * 4)]
     _lib = lib
     return lib
 
@@ -939,6 +975,42 @@ class Resources:
         out = (C.c_uint64 * 4)()
         check(self.lib.tbrm_margin_counters(self.handle, C.byref(out)))
         return {k: int(out[i]) for i, k in enumerate(self.MARGIN_COUNTERS)}
+
+    # smoothing of labels (include/tbrm_smooth.h): boxes, radii and reaches as (x, y, z)
+    def smooth_desc(self, radius, source, new_label, rank=(1, 2), iterations=1, origin=None, extent=None, writable=None, erase_label=0):
+        """radius: (r_x, r_y, r_z) in voxels, or one number for all three (smooth_radii turns a spacing and a radius into them);
+        rank: (rank_num, rank_den), the median by default; source, writable, new_label: as in morph_desc"""
+        d = SMOOTH_DESC()
+        if extent is not None:
+            d.origin[:] = [int(v) for v in (origin if origin is not None else (0, 0, 0))]
+            d.extent[:] = [int(v) for v in extent]
+        d.radius[:] = [int(radius)] * 3 if np.isscalar(radius) else [int(v) for v in radius]
+        d.rank_num, d.rank_den, d.iterations = int(rank[0]), int(rank[1]), int(iterations)
+        d.new_label, d.erase_label = int(new_label), int(erase_label)
+        for l in source:
+            d.source[int(l) >> 5] |= 1 << (int(l) & 31)
+        if writable is None:
+            d.writable[:] = [0xFFFFFFFF] * 8
+        else:
+            for l in writable:
+                d.writable[int(l) >> 5] |= 1 << (int(l) & 31)
+        return d
+
+    def smooth_labels(self, radius, source, new_label, rank=(1, 2), iterations=1, origin=None, extent=None, writable=None, erase_label=0):
+        """tbrm_smooth_labels: {"source_voxels", "result_voxels", "added", "removed", "relabelled", "bbox_min", "bbox_max", "reach", "launches"}"""
+        d = self.smooth_desc(radius, source, new_label, rank, iterations, origin, extent, writable, erase_label)
+        out = SMOOTH_RESULT()
+        check(self.lib.tbrm_smooth_labels(self.handle, C.byref(d), C.byref(out)))
+        return {"source_voxels": int(out.source_voxels), "result_voxels": int(out.result_voxels), "added": int(out.added), "removed": int(out.removed),
+                "relabelled": int(out.relabelled), "bbox_min": tuple(out.bbox_min[:]), "bbox_max": tuple(out.bbox_max[:]), "reach": tuple(out.reach[:]),
+                "launches": int(out.launches)}
+
+    SMOOTH_COUNTERS = ("smooth_calls", "launches", "bricks_computed", "bricks_written")
+
+    def smooth_counters(self):
+        out = (C.c_uint64 * 4)()
+        check(self.lib.tbrm_smooth_counters(self.handle, C.byref(out)))
+        return {k: int(out[i]) for i, k in enumerate(self.SMOOTH_COUNTERS)}
 
     # the islands of a label (include/tbrm_islands.h): boxes and first voxels as (x, y, z)
     def islands_desc(self, source, connectivity=6, max_islands=0, min_voxels=0, keep_label=-1, label_step=0, drop_label=-1, spare_border=False,

@@ -88,6 +88,21 @@ TBRM_BOARDS_HD uint64_t slice_in_volume(const int dims[3], int bx, int by, int z
     return rows >= kBrick ? xs : (rows <= 0 ? 0ull : xs & ((1ull << (8 * rows)) - 1ull));
 }
 
+// ---- windows clipped to the volume ---------------------------------------------------------------------------------------------------
+// the voxels of [v - r, v + r] that lie inside an axis of `dim` voxels (r >= 0); 0 for a v outside it, whose window may hold none
+TBRM_BOARDS_HD int clipped_extent(int dim, int v, int r)
+{
+    if (v < 0 || v >= dim) return 0;
+    const int lo = v - r < 0 ? 0 : v - r;
+    const int hi = v > dim - 1 - r ? dim - 1 : v + r; // (no overflow: dim - 1 - r is formed, not v + r)
+    return hi - lo + 1;
+}
+
+// The x window of a row as bits: a row word holds the brick's own byte at the bits 16 .. 23 and its neighbours' bytes either side of
+// it (bit p: the voxel x = bx * 8 - 16 + p, p < 40); the window of radius r <= 16 of the brick's voxel i is 2 r + 1 bits from 16 + i - r on
+constexpr int kRowWordShift = 16;
+TBRM_BOARDS_HD uint64_t row_window(int i, int r) { return ((1ull << (2 * r + 1)) - 1ull) << (kRowWordShift + i - r); }
+
 // ---- the 8 bytes of a row (Row8: uint2, or anything with 32-bit x and y) -------------------------------------------------------------
 template <class Row8> TBRM_BOARDS_HD uint32_t byte_of(const Row8& v, int i) { return ((i < 4 ? v.x : v.y) >> (8 * (i & 3))) & 255u; }
 

@@ -444,6 +444,8 @@ enum Tunable : int {
                              // per step — the test hook and the A/B switch). The result does not depend on it
     TUNE_MARGIN_SKIP,        // tbrm_margin_labels, tbrm_label_distance: 1: bricks whose result the board classes give are not computed; 0: every
                              // brick of the range is (the test hook and the A/B switch). The result does not depend on it
+    TUNE_SMOOTH_SKIP,        // tbrm_smooth_labels: 1: bricks whose result the board classes give are not computed; 0: every brick of the range
+                             // is (the test hook and the A/B switch). The result does not depend on it
     TUNE_COUNT
 };
 int tune(Tunable t);

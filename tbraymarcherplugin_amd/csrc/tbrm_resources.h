@@ -429,6 +429,7 @@ struct tbrm_resources {
     char* d_margin = nullptr;
     size_t margin_bytes = 0;
     uint64_t margin_counters[4]{};     // tbrm_margin_counters
+    uint64_t smooth_counters[4]{};     // tbrm_smooth_counters (include/tbrm_smooth.h; the call works in d_grow and takes no scratch of its own)
 };
 
 
