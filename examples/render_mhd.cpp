@@ -5,7 +5,7 @@
 //
 //   g++ -std=c++17 -O2 -I include examples/render_mhd.cpp -o render_mhd -L tbraymarcherplugin_amd/lib -ltbrm -lz
 //       (plus -Wl,-rpath,$PWD/tbraymarcherplugin_amd/lib -Wl,-rpath,/opt/rocm/lib to run it in place)
-//   ./render_mhd volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]] [--margin OP,RADIUS[,LABEL]] [--smooth RADIUS[,ITERATIONS[,LABEL]]] [--islands OP,N[,LABEL]]
+//   ./render_mhd volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]] [--margin OP,RADIUS[,LABEL]] [--smooth RADIUS[,ITERATIONS[,LABEL]]] [--islands OP,N[,LABEL]] [--scissors OP,LABEL,x0,y0,x1,y1,x2,y2[,..]]
 //       --light-color: the key light's colour (components in [0, 1]) on an RGB light volume (include/tbrm_color_lights.h); the fill stays white
 //       --auto-window: the window comes from the data (ARaymarchVolume::AutoWindow, include/tbrm_volume_stats.h): the span between
 //                      the LOW and HIGH percentiles of the value histogram, 0.01,0.99 when not given
@@ -25,6 +25,10 @@
 //                      include/tbrm_smooth.h): a voxel keeps or gets the label where a strict majority of the box of RADIUS round it —
 //                      a distance in the units of the file's ElementSpacing, rounded to voxels per axis — has it; ITERATIONS passes
 //                      (1 when not given); voxels that leave the label get label 0; printed as one "smooth" line
+//       --scissors: after every other edit, the lasso through the points (x, y) — pixels of the rendered view, closed by itself, even-odd —
+//                      cuts or fills label LABEL in the voxels the view sees under it, through its whole depth (ARaymarchVolume::ScissorLabel,
+//                      include/tbrm_scissors.h): OP is erase_inside, erase_outside (keep only what is under the lasso), fill_inside or
+//                      fill_outside; voxels that leave the label get label 0; printed as one "scissors" line
 //       --islands: after --grow, --morph, --margin and --smooth, the islands of label LABEL (the grown label when not given) (ARaymarchVolume::KeepLargestIslands
 //                      and its kin, include/tbrm_islands.h), 6-connected: OP is keep (the N largest stay, the others get label 0), remove
 //                      (islands of fewer than N voxels get label 0), split (the N largest get LABEL, LABEL + 1, ..) or fill (what the
@@ -128,8 +132,28 @@ int main(int argc, char** argv)
             argc -= 2;
             break;
         }
+    std::vector<double> scissors_points;
+    char scissors_op[16] = "";
+    int scissors_label = -1;
+    bool scissors = false;
+    for (int i = 1; i + 1 < argc; ++i)
+        if (!std::strcmp(argv[i], "--scissors")) {
+            int used = 0;
+            if (std::sscanf(argv[i + 1], "%15[a-z_],%d%n", scissors_op, &scissors_label, &used) < 2) { argc = 0; break; }
+            for (const char* at = argv[i + 1] + used; *at == ',';) {
+                char* end = nullptr;
+                scissors_points.push_back(std::strtod(at + 1, &end));
+                if (end == at + 1) { scissors_points.clear(); break; }
+                at = end;
+            }
+            if (scissors_points.size() < 6 || (scissors_points.size() & 1)) { argc = 0; break; }
+            scissors = true;
+            for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
+            argc -= 2;
+            break;
+        }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]] [--margin OP,RADIUS[,LABEL]] [--smooth RADIUS[,ITERATIONS[,LABEL]]] [--islands OP,N[,LABEL]]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]] [--margin OP,RADIUS[,LABEL]] [--smooth RADIUS[,ITERATIONS[,LABEL]]] [--islands OP,N[,LABEL]] [--scissors OP,LABEL,x0,y0,x1,y1,x2,y2[,..]]\n", argv[0]);
         return 2;
     }
     const int width = argc > 3 ? std::atoi(argv[3]) : 512, height = argc > 4 ? std::atoi(argv[4]) : 512;
@@ -260,6 +284,21 @@ int main(int argc, char** argv)
                     (unsigned long long) r.Largest, (unsigned long long) r.Relabelled, r.BoxMin[0], r.BoxMin[1], r.BoxMin[2], r.BoxMax[0], r.BoxMax[1], r.BoxMax[2]);
     }
     std::vector<float> rgba((size_t) width * height * 4);
+    if (scissors) { // after every other edit, before the frame: the points are pixels of the frame below
+        static const char* const names[4] = {"erase_inside", "erase_outside", "fill_inside", "fill_outside"};
+        int op = -1;
+        for (int k = 0; k < 4; ++k)
+            if (!std::strcmp(scissors_op, names[k])) op = k;
+        FScissorsResult m;
+        if (op < 0 || !volume.ScissorLabel(cam, scissors_points, op, scissors_label, 0.0, HUGE_VAL, m)) {
+            std::fprintf(stderr, "scissors failed: %s\n", op < 0 ? "OP must be erase_inside, erase_outside, fill_inside or fill_outside" : tbrm_last_error());
+            return 1;
+        }
+        std::printf("scissors %s label %d points %zu pixels %llu source %llu result %llu added %llu removed %llu box %d %d %d .. %d %d %d bricks %d inside %d outside %d projected launches %d\n",
+                    scissors_op, scissors_label, scissors_points.size() / 2, (unsigned long long) m.MaskPixels, (unsigned long long) m.SourceVoxels,
+                    (unsigned long long) m.ResultVoxels, (unsigned long long) m.Added, (unsigned long long) m.Removed, m.BoxMin[0], m.BoxMin[1], m.BoxMin[2], m.BoxMax[0],
+                    m.BoxMax[1], m.BoxMax[2], m.BricksInside, m.BricksOutside, m.BricksProjected, m.Launches);
+    }
     if (!volume.RenderLit(cam, rgba.data())) {
         std::fprintf(stderr, "render failed: %s\n", tbrm_last_error());
         return 1;

@@ -25,6 +25,7 @@
 #include "tbrm_islands.h"
 #include "tbrm_margin.h"
 #include "tbrm_smooth.h"
+#include "tbrm_scissors.h"
 
 #include <algorithm>
 #include <cmath>
@@ -313,6 +314,18 @@ struct FSmoothResult {
     int Launches = 0;
 };
 
+// What a scissors call found (include/tbrm_scissors.h): ARaymarchVolume::ScissorLabel and its kin
+struct FScissorsResult {
+    uint64_t SourceVoxels = 0, ResultVoxels = 0; // the label's voxels before and afterwards
+    uint64_t Added = 0, Removed = 0;             // voxels that joined / left the label
+    uint64_t Relabelled = 0;                     // label bytes that changed
+    int BoxMin[3] = {0, 0, 0}, BoxMax[3] = {-1, -1, -1}; // of what joined or left, inclusive; nothing: the volume's size and -1
+    int BricksInside = 0, BricksOutside = 0;     // bricks their corners put wholly under / wholly beside the lasso
+    int BricksProjected = 0;                     // bricks projected voxel by voxel
+    int Launches = 0;
+    uint64_t MaskPixels = 0;                     // pixels of the view inside the lasso
+};
+
 // What an island call found (include/tbrm_islands.h): ARaymarchVolume::KeepLargestIslands / RemoveSmallIslands / SplitIslands /
 // FillLabelHoles
 struct FIslandsResult {
@@ -598,6 +611,48 @@ public:
     }
     // the median: a strict majority of the box
     bool MedianLabel(int Label, double RadiusInVolumeUnits, int Iterations, FSmoothResult& Out) { return SmoothLabel(Label, RadiusInVolumeUnits, Iterations, Out, 1, 2); }
+
+    // Scissors (include/tbrm_scissors.h; no counterpart in the reference): the lasso Polygon — x0, y0, x1, y1, .. in pixels of the view
+    // Camera rendered, closed by itself, even-odd — cuts or fills Label in the voxels whose centre Camera sees under it between the
+    // depths DepthMin and DepthMax along the camera's forward (world units: a hit's Depth; HUGE_VAL: no far limit), on the device. Op
+    // is TBRM_SCISSORS_*: voxels that join get Label (over any label), voxels that leave get EraseLabel; bMeasureOnly counts them and
+    // writes nothing. Like the other label edits it requests no recompute. Needs a label volume.
+    bool ScissorLabel(const tbrm_camera& Camera, const std::vector<double>& Polygon, int Op, int Label, double DepthMin, double DepthMax, FScissorsResult& Out,
+                      int EraseLabel = 0, bool bMeasureOnly = false)
+    {
+        Out = FScissorsResult{};
+        if (!RaymarchResources.Handle || Label < 0 || Label > 255 || Polygon.size() < 6 || (Polygon.size() & 1)) return false;
+        const tbrm_world_params w = WorldParameters.abi();
+        const int32_t dims[3] = {RaymarchResources.SizeX, RaymarchResources.SizeY, RaymarchResources.SizeZ};
+        tbrm_scissors_desc d{};
+        if (tbrm_host_scissors_projection(dims, &w, &Camera, DepthMin, DepthMax, &d.projection) != TBRM_OK) return false;
+        std::vector<uint32_t> Mask((size_t) ((Camera.width + 31) / 32) * (size_t) Camera.height);
+        if (tbrm_host_scissors_polygon(Polygon.data(), Polygon.size() / 2, Camera.width, Camera.height, Mask.data(), Mask.size()) != TBRM_OK) return false;
+        d.op = Op;
+        d.new_label = bMeasureOnly ? -1 : Label;
+        d.erase_label = EraseLabel;
+        d.source[Label >> 5] = 1u << (Label & 31);
+        for (uint32_t& m : d.writable) m = 0xffffffffu;
+        tbrm_scissors_result r{};
+        if (tbrm_scissors_labels(RaymarchResources.Handle, &d, Mask.data(), Mask.size(), &r) != TBRM_OK) return false;
+        Out.SourceVoxels = r.source_voxels;
+        Out.ResultVoxels = r.result_voxels;
+        Out.Added = r.added;
+        Out.Removed = r.removed;
+        Out.Relabelled = r.relabelled;
+        for (int c = 0; c < 3; ++c) { Out.BoxMin[c] = r.bbox_min[c]; Out.BoxMax[c] = r.bbox_max[c]; }
+        Out.BricksInside = r.bricks_inside;
+        Out.BricksOutside = r.bricks_outside;
+        Out.BricksProjected = r.bricks_projected;
+        Out.Launches = r.launches;
+        for (uint32_t m : Mask)
+            for (; m; m &= m - 1) ++Out.MaskPixels;
+        return true;
+    }
+    // the three everyday cuts, through the whole depth of the view
+    bool EraseInsideLasso(const tbrm_camera& Camera, const std::vector<double>& Polygon, int Label, FScissorsResult& Out) { return ScissorLabel(Camera, Polygon, TBRM_SCISSORS_ERASE_INSIDE, Label, 0.0, HUGE_VAL, Out); }
+    bool KeepInsideLasso(const tbrm_camera& Camera, const std::vector<double>& Polygon, int Label, FScissorsResult& Out) { return ScissorLabel(Camera, Polygon, TBRM_SCISSORS_ERASE_OUTSIDE, Label, 0.0, HUGE_VAL, Out); }
+    bool FillInsideLasso(const tbrm_camera& Camera, const std::vector<double>& Polygon, int Label, FScissorsResult& Out) { return ScissorLabel(Camera, Polygon, TBRM_SCISSORS_FILL_INSIDE, Label, 0.0, HUGE_VAL, Out); }
 
     // The islands of one label (include/tbrm_islands.h; no counterpart in the reference): its connected components, ordered by size,
     // on the device. The four tools are parameter sets of one rule. Like the other label edits they request no recompute. They need a

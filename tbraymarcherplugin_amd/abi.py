@@ -312,6 +312,62 @@ def smooth_radii(spacing, radius):
     return tuple(int(v) for v in r)
 
 
+# every symbol include/tbrm_scissors.h declares (view-space scissors; tests/test_scissors_abi.py checks the header against this list)
+SCISSORS_SYMBOLS = ["tbrm_scissors_abi_version", "tbrm_scissors_labels", "tbrm_scissors_counters", "tbrm_host_scissors_projection", "tbrm_host_scissors_polygon"]
+
+SCISSORS_ABI_VERSION = 1  # TBRM_SCISSORS_ABI_VERSION of include/tbrm_scissors.h
+SCISSORS_MAX_IMAGE = 16384
+SCISSORS_COORD_BITS = 46
+SCISSORS_ERASE_INSIDE, SCISSORS_ERASE_OUTSIDE, SCISSORS_FILL_INSIDE, SCISSORS_FILL_OUTSIDE = 0, 1, 2, 3
+SCISSORS_OPS = {"erase_inside": SCISSORS_ERASE_INSIDE, "erase_outside": SCISSORS_ERASE_OUTSIDE, "fill_inside": SCISSORS_FILL_INSIDE, "fill_outside": SCISSORS_FILL_OUTSIDE}
+
+
+class SCISSORS_PROJECTION(C.Structure):  # tbrm_scissors_projection
+    _fields_ = [("u", C.c_int64 * 4), ("v", C.c_int64 * 4), ("w", C.c_int64 * 4), ("w_min", C.c_int64), ("w_max", C.c_int64),
+                ("width", C.c_int32), ("height", C.c_int32), ("scale_log2", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SCISSORS_DESC(C.Structure):  # tbrm_scissors_desc
+    _fields_ = [("origin", C.c_int32 * 3), ("extent", C.c_int32 * 3), ("op", C.c_int32), ("new_label", C.c_int32), ("erase_label", C.c_int32), ("reserved", C.c_int32),
+                ("source", C.c_uint32 * 8), ("writable", C.c_uint32 * 8), ("projection", SCISSORS_PROJECTION)]
+
+
+class SCISSORS_RESULT(C.Structure):  # tbrm_scissors_result
+    _fields_ = [("source_voxels", C.c_uint64), ("result_voxels", C.c_uint64), ("added", C.c_uint64), ("removed", C.c_uint64), ("relabelled", C.c_uint64),
+                ("bbox_min", C.c_int32 * 3), ("bbox_max", C.c_int32 * 3), ("bricks_inside", C.c_int32), ("bricks_outside", C.c_int32),
+                ("bricks_projected", C.c_int32), ("launches", C.c_int32)]
+
+
+def scissors_mask_shape(width, height):
+    """a mask as numpy: uint32 [height, ceil(width / 32)]; pixel px of row py is bit px & 31 of [py, px >> 5]"""
+    return int(height), (int(width) + 31) // 32
+
+
+def make_scissors_projection(u, v, w, w_min, w_max, width, height):
+    """hand-made rows: u, v, w are four integers each"""
+    p = SCISSORS_PROJECTION()
+    p.u[:], p.v[:], p.w[:] = [int(a) for a in u], [int(a) for a in v], [int(a) for a in w]
+    p.w_min, p.w_max, p.width, p.height = int(w_min), int(w_max), int(width), int(height)
+    return p
+
+
+def scissors_projection(dims, world, camera, depth_min=0.0, depth_max=float("inf")):
+    """tbrm_host_scissors_projection: the integer rows of `camera` for a volume of dims (x, y, z) under world's volume transform;
+    depth_min, depth_max: world units along the camera's forward (a hit map's depth)"""
+    d = (C.c_int32 * 3)(*[int(v) for v in dims])
+    out = SCISSORS_PROJECTION()
+    check(load().tbrm_host_scissors_projection(d, C.byref(world), C.byref(camera), float(depth_min), float(depth_max), C.byref(out)))
+    return out
+
+
+def scissors_polygon(points, width, height):
+    """tbrm_host_scissors_polygon: the lasso through `points` ((x, y) in pixels of the view) as a mask (scissors_mask_shape)"""
+    xy = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 2))
+    mask = np.zeros(scissors_mask_shape(width, height), dtype=np.uint32)
+    check(load().tbrm_host_scissors_polygon(xy.ctypes.data_as(C.c_void_p), xy.shape[0], int(width), int(height), mask.ctypes.data_as(C.c_void_p), mask.size))
+    return mask
+
+
 class ISLAND(C.Structure):  # tbrm_island
     _fields_ = [("voxels", C.c_uint64), ("first", C.c_int32 * 3), ("label", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -491,6 +547,14 @@ def load():
     lib.tbrm_smooth_labels.argtypes = [vp, P(SMOOTH_DESC), P(SMOOTH_RESULT)]
     lib.tbrm_host_smooth_radii.argtypes = [P(C.c_double * 3), C.c_double, P(C.c_int32 * 3)]
     lib.tbrm_smooth_counters.argtypes = [vp, P(C.c_uint64 * 4)]
+    have = lib.tbrm_scissors_abi_version() if hasattr(lib, "tbrm_scissors_abi_version") else -1
+    if have != SCISSORS_ABI_VERSION:
+        raise ImportError(f"{LIB_PATH} has scissors ABI version {have}, this binding is written against {SCISSORS_ABI_VERSION}: rebuild it "
+                          "(`python tbraymarcherplugin_amd/build.py --force`)")
+    lib.tbrm_scissors_labels.argtypes = [vp, P(SCISSORS_DESC), vp, C.c_size_t, P(SCISSORS_RESULT)]
+    lib.tbrm_scissors_counters.argtypes = [vp, P(C.c_uint64 * 4)]
+    lib.tbrm_host_scissors_projection.argtypes = [P(C.c_int32 * 3), P(WorldParams), P(Camera), C.c_double, C.c_double, P(SCISSORS_PROJECTION)]
+    lib.tbrm_host_scissors_polygon.argtypes = [vp, C.c_size_t, C.c_int32, C.c_int32, vp, C.c_size_t]
     _lib = lib
     return lib
 
@@ -1011,6 +1075,44 @@ class Resources:
         out = (C.c_uint64 * 4)()
         check(self.lib.tbrm_smooth_counters(self.handle, C.byref(out)))
         return {k: int(out[i]) for i, k in enumerate(self.SMOOTH_COUNTERS)}
+
+    # view-space scissors (include/tbrm_scissors.h): boxes as (x, y, z)
+    def scissors_desc(self, projection, op, source, new_label, origin=None, extent=None, writable=None, erase_label=0):
+        """projection: a SCISSORS_PROJECTION (scissors_projection, make_scissors_projection); op: SCISSORS_* or its name;
+        source, writable, new_label: as in morph_desc"""
+        d = SCISSORS_DESC()
+        if extent is not None:
+            d.origin[:] = [int(v) for v in (origin if origin is not None else (0, 0, 0))]
+            d.extent[:] = [int(v) for v in extent]
+        d.op = SCISSORS_OPS[op] if isinstance(op, str) else int(op)
+        d.new_label, d.erase_label = int(new_label), int(erase_label)
+        for l in source:
+            d.source[int(l) >> 5] |= 1 << (int(l) & 31)
+        if writable is None:
+            d.writable[:] = [0xFFFFFFFF] * 8
+        else:
+            for l in writable:
+                d.writable[int(l) >> 5] |= 1 << (int(l) & 31)
+        C.memmove(C.byref(d.projection), C.byref(projection), C.sizeof(SCISSORS_PROJECTION))
+        return d
+
+    def scissor_labels(self, projection, mask, op, source, new_label, origin=None, extent=None, writable=None, erase_label=0):
+        """tbrm_scissors_labels; mask: uint32 [height, ceil(width / 32)] (scissors_polygon makes one): {"source_voxels", "result_voxels",
+        "added", "removed", "relabelled", "bbox_min", "bbox_max", "bricks_inside", "bricks_outside", "bricks_projected", "launches"}"""
+        d = self.scissors_desc(projection, op, source, new_label, origin, extent, writable, erase_label)
+        m = np.ascontiguousarray(mask, dtype=np.uint32)
+        out = SCISSORS_RESULT()
+        check(self.lib.tbrm_scissors_labels(self.handle, C.byref(d), m.ctypes.data_as(C.c_void_p), m.size, C.byref(out)))
+        return {"source_voxels": int(out.source_voxels), "result_voxels": int(out.result_voxels), "added": int(out.added), "removed": int(out.removed),
+                "relabelled": int(out.relabelled), "bbox_min": tuple(out.bbox_min[:]), "bbox_max": tuple(out.bbox_max[:]), "bricks_inside": int(out.bricks_inside),
+                "bricks_outside": int(out.bricks_outside), "bricks_projected": int(out.bricks_projected), "launches": int(out.launches)}
+
+    SCISSORS_COUNTERS = ("scissors_calls", "launches", "bricks_projected", "bricks_written")
+
+    def scissors_counters(self):
+        out = (C.c_uint64 * 4)()
+        check(self.lib.tbrm_scissors_counters(self.handle, C.byref(out)))
+        return {k: int(out[i]) for i, k in enumerate(self.SCISSORS_COUNTERS)}
 
     # the islands of a label (include/tbrm_islands.h): boxes and first voxels as (x, y, z)
     def islands_desc(self, source, connectivity=6, max_islands=0, min_voxels=0, keep_label=-1, label_step=0, drop_label=-1, spare_border=False,

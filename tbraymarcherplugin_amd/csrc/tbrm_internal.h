@@ -446,6 +446,8 @@ enum Tunable : int {
                              // brick of the range is (the test hook and the A/B switch). The result does not depend on it
     TUNE_SMOOTH_SKIP,        // tbrm_smooth_labels: 1: bricks whose result the board classes give are not computed; 0: every brick of the range
                              // is (the test hook and the A/B switch). The result does not depend on it
+    TUNE_SCISSORS_SKIP,      // tbrm_scissors_labels: 1: bricks whose result the source set or their corners give are not projected; 0: every brick of
+                             // the range is, voxel by voxel (the test hook and the A/B switch). The result does not depend on it
     TUNE_COUNT
 };
 int tune(Tunable t);

@@ -429,6 +429,10 @@ struct tbrm_resources {
     char* d_margin = nullptr;
     size_t margin_bytes = 0;
     uint64_t margin_counters[4]{};     // tbrm_margin_counters
+    // view-space scissors (tbrm_api_scissors.cpp; include/tbrm_scissors.h): the mask as uploaded and its summary, only ever grown
+    char* d_scissors = nullptr;
+    size_t scissors_bytes = 0;
+    uint64_t scissors_counters[4]{};   // tbrm_scissors_counters
     uint64_t smooth_counters[4]{};     // tbrm_smooth_counters (include/tbrm_smooth.h; the call works in d_grow and takes no scratch of its own)
 };
 
