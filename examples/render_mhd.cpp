@@ -5,7 +5,7 @@
 //
 //   g++ -std=c++17 -O2 -I include examples/render_mhd.cpp -o render_mhd -L tbraymarcherplugin_amd/lib -ltbrm -lz
 //       (plus -Wl,-rpath,$PWD/tbraymarcherplugin_amd/lib -Wl,-rpath,/opt/rocm/lib to run it in place)
-//   ./render_mhd volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]] [--margin OP,RADIUS[,LABEL]] [--smooth RADIUS[,ITERATIONS[,LABEL]]] [--islands OP,N[,LABEL]] [--scissors OP,LABEL,x0,y0,x1,y1,x2,y2[,..]]
+//   ./render_mhd volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]] [--margin OP,RADIUS[,LABEL]] [--smooth RADIUS[,ITERATIONS[,LABEL]]] [--islands OP,N[,LABEL]] [--scissors OP,LABEL,x0,y0,x1,y1,x2,y2[,..]] [--compete COST,SHIFT,LIMIT,LABEL@X,Y,Z,R[,LABEL@X,Y,Z,R..]]
 //       --light-color: the key light's colour (components in [0, 1]) on an RGB light volume (include/tbrm_color_lights.h); the fill stays white
 //       --auto-window: the window comes from the data (ARaymarchVolume::AutoWindow, include/tbrm_volume_stats.h): the span between
 //                      the LOW and HIGH percentiles of the value histogram, 0.01,0.99 when not given
@@ -29,6 +29,11 @@
 //                      cuts or fills label LABEL in the voxels the view sees under it, through its whole depth (ARaymarchVolume::ScissorLabel,
 //                      include/tbrm_scissors.h): OP is erase_inside, erase_outside (keep only what is under the lasso), fill_inside or
 //                      fill_outside; voxels that leave the label get label 0; printed as one "scissors" line
+//       --compete: after every other edit, grow from seeds (ARaymarchVolume::GrowFromSeeds, include/tbrm_compete.h): a ball of R voxels
+//                      round the voxel (X, Y, Z) is painted with LABEL for every LABEL@X,Y,Z,R, then the painted labels compete for every
+//                      other voxel: a step costs COST along the axis of the file's finest ElementSpacing (the others in proportion) plus
+//                      the difference of the two voxels' 16-bit codes >> SHIFT, up to the cost LIMIT (0: no limit); printed as one
+//                      "compete" line
 //       --islands: after --grow, --morph, --margin and --smooth, the islands of label LABEL (the grown label when not given) (ARaymarchVolume::KeepLargestIslands
 //                      and its kin, include/tbrm_islands.h), 6-connected: OP is keep (the N largest stay, the others get label 0), remove
 //                      (islands of fewer than N voxels get label 0), split (the N largest get LABEL, LABEL + 1, ..) or fill (what the
@@ -152,8 +157,30 @@ int main(int argc, char** argv)
             argc -= 2;
             break;
         }
+    struct CompeteBall { int label, x, y, z, r; };
+    std::vector<CompeteBall> compete_balls;
+    int compete_cost = 0, compete_shift = 0;
+    long long compete_limit = 0;
+    bool compete = false;
+    for (int i = 1; i + 1 < argc; ++i)
+        if (!std::strcmp(argv[i], "--compete")) {
+            int used = 0;
+            if (std::sscanf(argv[i + 1], "%d,%d,%lld%n", &compete_cost, &compete_shift, &compete_limit, &used) < 3) { argc = 0; break; }
+            for (const char* at = argv[i + 1] + used; *at == ',';) {
+                CompeteBall b{};
+                int n = 0;
+                if (std::sscanf(at + 1, "%d@%d,%d,%d,%d%n", &b.label, &b.x, &b.y, &b.z, &b.r, &n) < 5) { compete_balls.clear(); break; }
+                compete_balls.push_back(b);
+                at += 1 + n;
+            }
+            if (compete_balls.empty() || compete_limit < 0 || compete_limit > 0xFFFFFFll) { argc = 0; break; }
+            compete = true;
+            for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
+            argc -= 2;
+            break;
+        }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]] [--margin OP,RADIUS[,LABEL]] [--smooth RADIUS[,ITERATIONS[,LABEL]]] [--islands OP,N[,LABEL]] [--scissors OP,LABEL,x0,y0,x1,y1,x2,y2[,..]]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]] [--margin OP,RADIUS[,LABEL]] [--smooth RADIUS[,ITERATIONS[,LABEL]]] [--islands OP,N[,LABEL]] [--scissors OP,LABEL,x0,y0,x1,y1,x2,y2[,..]] [--compete COST,SHIFT,LIMIT,LABEL@X,Y,Z,R[,LABEL@X,Y,Z,R..]]\n", argv[0]);
         return 2;
     }
     const int width = argc > 3 ? std::atoi(argv[3]) : 512, height = argc > 4 ? std::atoi(argv[4]) : 512;
@@ -298,6 +325,36 @@ int main(int argc, char** argv)
                     scissors_op, scissors_label, scissors_points.size() / 2, (unsigned long long) m.MaskPixels, (unsigned long long) m.SourceVoxels,
                     (unsigned long long) m.ResultVoxels, (unsigned long long) m.Added, (unsigned long long) m.Removed, m.BoxMin[0], m.BoxMin[1], m.BoxMin[2], m.BoxMax[0],
                     m.BoxMax[1], m.BoxMax[2], m.BricksInside, m.BricksOutside, m.BricksProjected, m.Launches);
+    }
+    if (compete) { // after every other edit, before the frame: the balls are painted over what is there, then everything else is competed for
+        const int nx = info.Dimensions[0], ny = info.Dimensions[1], nz = info.Dimensions[2];
+        std::vector<uint8_t> labels((size_t) nx * ny * nz, 0);
+        std::vector<int> seeds;
+        bool ok = tbrm_attach_empty_label_volume(volume.RaymarchResources.Handle) == TBRM_OK &&
+                  tbrm_download_label_volume(volume.RaymarchResources.Handle, labels.data(), labels.size()) == TBRM_OK;
+        for (const auto& b : compete_balls) {
+            if (b.label < 1 || b.label > 255 || b.r < 0) { ok = false; break; }
+            seeds.push_back(b.label);
+            for (int z = std::max(b.z - b.r, 0); z <= std::min(b.z + b.r, nz - 1); ++z)
+                for (int y = std::max(b.y - b.r, 0); y <= std::min(b.y + b.r, ny - 1); ++y)
+                    for (int x = std::max(b.x - b.r, 0); x <= std::min(b.x + b.r, nx - 1); ++x)
+                        if ((x - b.x) * (x - b.x) + (y - b.y) * (y - b.y) + (z - b.z) * (z - b.z) <= b.r * b.r) labels[((size_t) z * ny + y) * nx + x] = (uint8_t) b.label;
+        }
+        FCompeteOptions opt;
+        opt.SpacingCost = compete_cost;
+        opt.ValueShift = compete_shift;
+        opt.CostLimit = (uint32_t) compete_limit;
+        FCompeteResult m;
+        if (!ok || !volume.SetLabelVolume(labels.data(), labels.size()) || !volume.GrowFromSeeds(seeds, opt, m)) {
+            std::fprintf(stderr, "compete failed: %s\n", ok ? tbrm_last_error() : "LABEL must be 1 .. 255, R >= 0, and the volume must take labels");
+            return 1;
+        }
+        std::printf("compete step %d %d %d shift %d limit %lld seeds %llu claimable %llu claimed %llu relabelled %llu max_cost %u box %d %d %d .. %d %d %d passes %d per_label",
+                    m.StepCost[0], m.StepCost[1], m.StepCost[2], compete_shift, compete_limit, (unsigned long long) m.SeedVoxels, (unsigned long long) m.Claimable,
+                    (unsigned long long) m.Claimed, (unsigned long long) m.Relabelled, m.MaxCost, m.BoxMin[0], m.BoxMin[1], m.BoxMin[2], m.BoxMax[0], m.BoxMax[1], m.BoxMax[2], m.Passes);
+        for (int l = 0; l < 256; ++l)
+            if (m.ClaimedPerLabel[l]) std::printf(" %d:%llu", l, (unsigned long long) m.ClaimedPerLabel[l]);
+        std::printf("\n");
     }
     if (!volume.RenderLit(cam, rgba.data())) {
         std::fprintf(stderr, "render failed: %s\n", tbrm_last_error());

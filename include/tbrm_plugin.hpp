@@ -26,6 +26,7 @@
 #include "tbrm_margin.h"
 #include "tbrm_smooth.h"
 #include "tbrm_scissors.h"
+#include "tbrm_compete.h"
 
 #include <algorithm>
 #include <cmath>
@@ -324,6 +325,30 @@ struct FScissorsResult {
     int BricksProjected = 0;                     // bricks projected voxel by voxel
     int Launches = 0;
     uint64_t MaskPixels = 0;                     // pixels of the view inside the lasso
+};
+
+// What a grow-from-seeds call found (include/tbrm_compete.h): ARaymarchVolume::GrowFromSeeds
+struct FCompeteResult {
+    uint64_t SeedVoxels = 0, Claimable = 0, Claimed = 0; // the painted voxels, the voxels they competed for, those a seed reached
+    uint64_t Relabelled = 0;                     // label bytes that changed
+    uint64_t ClaimedPerLabel[256] = {};
+    uint32_t MaxCost = 0;                        // the largest cost of a claimed voxel
+    int Passes = 0;
+    int BoxMin[3] = {0, 0, 0}, BoxMax[3] = {-1, -1, -1}; // of the claimed voxels, inclusive; none: the volume's size and -1
+    int StepCost[3] = {0, 0, 0};                 // what the call charged per step along each axis
+};
+
+// The options of ARaymarchVolume::GrowFromSeeds; the defaults let every voxel that is no seed be claimed
+struct FCompeteOptions {
+    double Lo = 0.0, Hi = -1.0;                  // the gate in stored units; Hi < Lo: the format's whole range (float: every finite value)
+    int StepCost[3] = {-1, -1, -1};              // per axis, 0 .. 65535; negative: StepCostFromSpacing(SpacingCost)
+    int SpacingCost = 16;                        // ... the cost of a step along the axis of the finest spacing
+    int ValueShift = 0;
+    uint32_t CostLimit = 0;                      // 0: none but the key's, 2^24 - 1
+    double FloatLo = 0.0, FloatHi = 1.0;         // R32_FLOAT volumes: the values that become the codes 0 .. 65535
+    std::vector<int> Writable;                   // the labels that may be claimed; empty: every label
+    int Origin[3] = {0, 0, 0}, Extent[3] = {0, 0, 0}; // the box; all-zero extent: the whole volume
+    bool bMeasureOnly = false;
 };
 
 // What an island call found (include/tbrm_islands.h): ARaymarchVolume::KeepLargestIslands / RemoveSmallIslands / SplitIslands /
@@ -653,6 +678,72 @@ public:
     bool EraseInsideLasso(const tbrm_camera& Camera, const std::vector<double>& Polygon, int Label, FScissorsResult& Out) { return ScissorLabel(Camera, Polygon, TBRM_SCISSORS_ERASE_INSIDE, Label, 0.0, HUGE_VAL, Out); }
     bool KeepInsideLasso(const tbrm_camera& Camera, const std::vector<double>& Polygon, int Label, FScissorsResult& Out) { return ScissorLabel(Camera, Polygon, TBRM_SCISSORS_ERASE_OUTSIDE, Label, 0.0, HUGE_VAL, Out); }
     bool FillInsideLasso(const tbrm_camera& Camera, const std::vector<double>& Polygon, int Label, FScissorsResult& Out) { return ScissorLabel(Camera, Polygon, TBRM_SCISSORS_FILL_INSIDE, Label, 0.0, HUGE_VAL, Out); }
+
+    // Grow from seeds (include/tbrm_compete.h; no counterpart in the reference): the voxels that hold one of SeedLabels compete for
+    // the claimable voxels of the box, each of which goes to the label that reaches it at the least cost over face steps, on the
+    // device. Like the other label edits it requests no recompute. Needs a label volume.
+    // The step costs of a spacing: Finest along the axis of the smallest spacing, the others in proportion, rounded and clamped to
+    // 1 .. 65535; unit spacing (VoxelSpacing all zero): Finest along every axis.
+    void StepCostFromSpacing(int Finest, int Out[3]) const
+    {
+        const bool unit = VoxelSpacing[0] == 0.0 && VoxelSpacing[1] == 0.0 && VoxelSpacing[2] == 0.0;
+        double least = HUGE_VAL;
+        for (double s : VoxelSpacing)
+            if (s > 0.0 && s < least) least = s;
+        for (int c = 0; c < 3; ++c) {
+            const double v = unit || !(VoxelSpacing[c] > 0.0) ? (double) Finest : std::floor((double) Finest * VoxelSpacing[c] / least + 0.5);
+            Out[c] = v < 1.0 ? 1 : (v > (double) TBRM_COMPETE_MAX_STEP_COST ? TBRM_COMPETE_MAX_STEP_COST : (int) v);
+        }
+    }
+    bool GrowFromSeeds(const std::vector<int>& SeedLabels, const FCompeteOptions& Options, FCompeteResult& Out, std::vector<uint32_t>* Costs = nullptr)
+    {
+        Out = FCompeteResult{};
+        if (!RaymarchResources.Handle || SeedLabels.empty()) return false;
+        tbrm_compete_desc d{};
+        for (int c = 0; c < 3; ++c) { d.origin[c] = Options.Origin[c]; d.extent[c] = Options.Extent[c]; }
+        d.connectivity = 6;
+        d.measure_only = Options.bMeasureOnly ? 1 : 0;
+        int fromSpacing[3];
+        StepCostFromSpacing(Options.SpacingCost, fromSpacing);
+        for (int c = 0; c < 3; ++c) Out.StepCost[c] = d.step_cost[c] = Options.StepCost[c] >= 0 ? Options.StepCost[c] : fromSpacing[c];
+        d.value_shift = Options.ValueShift;
+        d.cost_limit = Options.CostLimit;
+        const bool isFloat = RaymarchResources.DataFormat == TBRM_FMT_R32_FLOAT;
+        d.lo = Options.Lo;
+        d.hi = Options.Hi;
+        if (Options.Hi < Options.Lo) {
+            d.lo = isFloat ? -3.4028234663852886e38 : 0.0;
+            d.hi = isFloat ? 3.4028234663852886e38 : (RaymarchResources.DataFormat == TBRM_FMT_G8 ? 255.0 : 65535.0);
+        }
+        if (isFloat && tbrm_host_compete_float_range(Options.FloatLo, Options.FloatHi, &d.float_origin, &d.float_scale) != TBRM_OK) return false;
+        for (int l : SeedLabels) {
+            if (l < 0 || l > 255) return false;
+            d.seeds[l >> 5] |= 1u << (l & 31);
+        }
+        if (Options.Writable.empty())
+            for (uint32_t& w : d.writable) w = 0xffffffffu;
+        for (int l : Options.Writable) {
+            if (l < 0 || l > 255) return false;
+            d.writable[l >> 5] |= 1u << (l & 31);
+        }
+        if (Costs) {
+            const bool whole = d.extent[0] == 0 && d.extent[1] == 0 && d.extent[2] == 0;
+            const size_t n = whole ? (size_t) RaymarchResources.SizeX * RaymarchResources.SizeY * RaymarchResources.SizeZ
+                                   : (size_t) std::max(d.extent[0], 0) * (size_t) std::max(d.extent[1], 0) * (size_t) std::max(d.extent[2], 0);
+            Costs->assign(n, TBRM_COMPETE_NO_COST);
+        }
+        tbrm_compete_result r{};
+        if (tbrm_compete_labels(RaymarchResources.Handle, &d, Costs && !Costs->empty() ? Costs->data() : nullptr, &r) != TBRM_OK) return false;
+        Out.SeedVoxels = r.seed_voxels;
+        Out.Claimable = r.claimable;
+        Out.Claimed = r.claimed;
+        Out.Relabelled = r.relabelled;
+        for (int l = 0; l < 256; ++l) Out.ClaimedPerLabel[l] = r.claimed_per_label[l];
+        Out.MaxCost = r.max_cost;
+        Out.Passes = r.passes;
+        for (int c = 0; c < 3; ++c) { Out.BoxMin[c] = r.bbox_min[c]; Out.BoxMax[c] = r.bbox_max[c]; }
+        return true;
+    }
 
     // The islands of one label (include/tbrm_islands.h; no counterpart in the reference): its connected components, ordered by size,
     // on the device. The four tools are parameter sets of one rule. Like the other label edits they request no recompute. They need a

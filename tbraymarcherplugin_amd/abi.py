@@ -338,6 +338,34 @@ class SCISSORS_RESULT(C.Structure):  # tbrm_scissors_result
                 ("bricks_projected", C.c_int32), ("launches", C.c_int32)]
 
 
+# every symbol include/tbrm_compete.h declares (competitive growing from seed labels; tests/test_compete_abi.py checks the header against this list)
+COMPETE_SYMBOLS = ["tbrm_compete_abi_version", "tbrm_compete_labels", "tbrm_host_compete_float_range", "tbrm_compete_counters"]
+
+COMPETE_ABI_VERSION = 1  # TBRM_COMPETE_ABI_VERSION of include/tbrm_compete.h
+COMPETE_MAX_COST = 0xFFFFFF
+COMPETE_MAX_STEP_COST = 65535
+COMPETE_MAX_SHIFT = 16
+COMPETE_NO_COST = 0xFFFFFFFF
+
+
+class COMPETE_DESC(C.Structure):  # tbrm_compete_desc
+    _fields_ = [("origin", C.c_int32 * 3), ("extent", C.c_int32 * 3), ("connectivity", C.c_int32), ("measure_only", C.c_int32), ("step_cost", C.c_int32 * 3),
+                ("value_shift", C.c_int32), ("cost_limit", C.c_uint32), ("reserved", C.c_int32), ("lo", C.c_double), ("hi", C.c_double),
+                ("float_origin", C.c_float), ("float_scale", C.c_float), ("seeds", C.c_uint32 * 8), ("writable", C.c_uint32 * 8)]
+
+
+class COMPETE_RESULT(C.Structure):  # tbrm_compete_result
+    _fields_ = [("seed_voxels", C.c_uint64), ("claimable", C.c_uint64), ("claimed", C.c_uint64), ("relabelled", C.c_uint64), ("claimed_per_label", C.c_uint64 * 256),
+                ("max_cost", C.c_uint32), ("passes", C.c_int32), ("bbox_min", C.c_int32 * 3), ("bbox_max", C.c_int32 * 3)]
+
+
+def compete_float_range(lo, hi):
+    """tbrm_host_compete_float_range: (float_origin, float_scale) that map the values [lo, hi] onto the codes 0 .. 65535"""
+    o, s = C.c_float(), C.c_float()
+    check(load().tbrm_host_compete_float_range(float(lo), float(hi), C.byref(o), C.byref(s)))
+    return o.value, s.value
+
+
 def scissors_mask_shape(width, height):
     """a mask as numpy: uint32 [height, ceil(width / 32)]; pixel px of row py is bit px & 31 of [py, px >> 5]"""
     return int(height), (int(width) + 31) // 32
@@ -555,6 +583,13 @@ def load():
     lib.tbrm_scissors_counters.argtypes = [vp, P(C.c_uint64 * 4)]
     lib.tbrm_host_scissors_projection.argtypes = [P(C.c_int32 * 3), P(WorldParams), P(Camera), C.c_double, C.c_double, P(SCISSORS_PROJECTION)]
     lib.tbrm_host_scissors_polygon.argtypes = [vp, C.c_size_t, C.c_int32, C.c_int32, vp, C.c_size_t]
+    have = lib.tbrm_compete_abi_version() if hasattr(lib, "tbrm_compete_abi_version") else -1
+    if have != COMPETE_ABI_VERSION:
+        raise ImportError(f"{LIB_PATH} has compete ABI version {have}, this binding is written against {COMPETE_ABI_VERSION}: rebuild it "
+                          "(`python tbraymarcherplugin_amd/build.py --force`)")
+    lib.tbrm_compete_labels.argtypes = [vp, P(COMPETE_DESC), vp, P(COMPETE_RESULT)]
+    lib.tbrm_host_compete_float_range.argtypes = [C.c_double, C.c_double, P(C.c_float), P(C.c_float)]
+    lib.tbrm_compete_counters.argtypes = [vp, P(C.c_uint64 * 4)]
     _lib = lib
     return lib
 
@@ -1113,6 +1148,53 @@ class Resources:
         out = (C.c_uint64 * 4)()
         check(self.lib.tbrm_scissors_counters(self.handle, C.byref(out)))
         return {k: int(out[i]) for i, k in enumerate(self.SCISSORS_COUNTERS)}
+
+    # competitive growing from seed labels (include/tbrm_compete.h): lo / hi in stored units, boxes as (x, y, z)
+    def compete_desc(self, seeds, lo, hi, step_cost=(1, 1, 1), value_shift=0, cost_limit=0, origin=None, extent=None, writable=None, measure_only=False,
+                     float_range=None, connectivity=6):
+        """seeds: the label values that grow; writable: the label values that may be claimed (None: every label); float_range:
+        (float_origin, float_scale) of an R32_FLOAT handle (compete_float_range makes one)"""
+        d = COMPETE_DESC()
+        if extent is not None:
+            d.origin[:] = [int(v) for v in (origin if origin is not None else (0, 0, 0))]
+            d.extent[:] = [int(v) for v in extent]
+        d.connectivity, d.measure_only, d.value_shift, d.cost_limit = int(connectivity), int(measure_only), int(value_shift), int(cost_limit)
+        d.step_cost[:] = [int(v) for v in step_cost]
+        d.lo, d.hi = float(lo), float(hi)
+        if float_range is not None:
+            d.float_origin, d.float_scale = float(float_range[0]), float(float_range[1])
+        for l in seeds:
+            d.seeds[int(l) >> 5] |= 1 << (int(l) & 31)
+        if writable is None:
+            d.writable[:] = [0xFFFFFFFF] * 8
+        else:
+            for l in writable:
+                d.writable[int(l) >> 5] |= 1 << (int(l) & 31)
+        return d
+
+    def compete_labels(self, seeds, lo, hi, step_cost=(1, 1, 1), value_shift=0, cost_limit=0, origin=None, extent=None, writable=None, measure_only=False,
+                       float_range=None, connectivity=6, costs=False):
+        """tbrm_compete_labels: {"seed_voxels", "claimable", "claimed", "relabelled", "claimed_per_label" ({label: voxels}, the labels that
+        claimed any), "max_cost", "passes", "bbox_min", "bbox_max"}; with costs=True (that, the costs of the box as uint32 [ez, ey, ex])"""
+        d = self.compete_desc(seeds, lo, hi, step_cost, value_shift, cost_limit, origin, extent, writable, measure_only, float_range, connectivity)
+        box = None
+        if costs:
+            whole = extent is None or tuple(int(v) for v in extent) == (0, 0, 0)
+            e = (self.desc.dim_x, self.desc.dim_y, self.desc.dim_z) if whole else tuple(int(v) for v in extent)
+            box = np.empty((max(e[2], 0), max(e[1], 0), max(e[0], 0)), dtype=np.uint32)
+        out = COMPETE_RESULT()
+        check(self.lib.tbrm_compete_labels(self.handle, C.byref(d), box.ctypes.data_as(C.c_void_p) if box is not None and box.size else None, C.byref(out)))
+        res = {"seed_voxels": int(out.seed_voxels), "claimable": int(out.claimable), "claimed": int(out.claimed), "relabelled": int(out.relabelled),
+               "claimed_per_label": {l: int(n) for l, n in enumerate(out.claimed_per_label) if n}, "max_cost": int(out.max_cost), "passes": int(out.passes),
+               "bbox_min": tuple(out.bbox_min[:]), "bbox_max": tuple(out.bbox_max[:])}
+        return (res, box) if costs else res
+
+    COMPETE_COUNTERS = ("compete_calls", "passes", "brick_visits", "bricks_written")
+
+    def compete_counters(self):
+        out = (C.c_uint64 * 4)()
+        check(self.lib.tbrm_compete_counters(self.handle, C.byref(out)))
+        return {k: int(out[i]) for i, k in enumerate(self.COMPETE_COUNTERS)}
 
     # the islands of a label (include/tbrm_islands.h): boxes and first voxels as (x, y, z)
     def islands_desc(self, source, connectivity=6, max_islands=0, min_voxels=0, keep_label=-1, label_step=0, drop_label=-1, spare_border=False,

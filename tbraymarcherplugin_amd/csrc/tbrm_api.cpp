@@ -540,6 +540,8 @@ int tbrm_resources_destroy(tbrm_resources* r)
     for (char* d : r->d_islands) (void) hipFree(d);
     (void) hipFree(r->d_margin);
     (void) hipFree(r->d_scissors);
+    (void) hipFree(r->d_compete);
+    (void) hipFree(r->d_compete_costs);
     (void) hipFree(r->d_alpha_prefix);
     (void) hipFree(r->d_counter);
     (void) hipFree(r->d_ray_tab);

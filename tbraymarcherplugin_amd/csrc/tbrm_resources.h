@@ -434,6 +434,13 @@ struct tbrm_resources {
     size_t scissors_bytes = 0;
     uint64_t scissors_counters[4]{};   // tbrm_scissors_counters
     uint64_t smooth_counters[4]{};     // tbrm_smooth_counters (include/tbrm_smooth.h; the call works in d_grow and takes no scratch of its own)
+    // competitive growing (tbrm_api_compete.cpp; include/tbrm_compete.h): the keys, claimable bits, activity and control words of the
+    // bricks a box touches, and the costs of a box when a call asks for them; each only ever grown
+    char* d_compete = nullptr;
+    size_t compete_bytes = 0;
+    char* d_compete_costs = nullptr;
+    size_t compete_costs_bytes = 0;
+    uint64_t compete_counters[4]{};    // tbrm_compete_counters
 };
 
 
