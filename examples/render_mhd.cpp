@@ -5,7 +5,7 @@
 //
 //   g++ -std=c++17 -O2 -I include examples/render_mhd.cpp -o render_mhd -L tbraymarcherplugin_amd/lib -ltbrm -lz
 //       (plus -Wl,-rpath,$PWD/tbraymarcherplugin_amd/lib -Wl,-rpath,/opt/rocm/lib to run it in place)
-//   ./render_mhd volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]] [--margin OP,RADIUS[,LABEL]] [--smooth RADIUS[,ITERATIONS[,LABEL]]] [--islands OP,N[,LABEL]] [--scissors OP,LABEL,x0,y0,x1,y1,x2,y2[,..]] [--compete COST,SHIFT,LIMIT,LABEL@X,Y,Z,R[,LABEL@X,Y,Z,R..]]
+//   ./render_mhd volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]] [--margin OP,RADIUS[,LABEL]] [--smooth RADIUS[,ITERATIONS[,LABEL]]] [--islands OP,N[,LABEL]] [--scissors OP,LABEL,x0,y0,x1,y1,x2,y2[,..]] [--compete COST,SHIFT,LIMIT,LABEL@X,Y,Z,R[,LABEL@X,Y,Z,R..]] [--paint LABEL,RADIUS@X,Y,Z[;X,Y,Z..]]
 //       --light-color: the key light's colour (components in [0, 1]) on an RGB light volume (include/tbrm_color_lights.h); the fill stays white
 //       --auto-window: the window comes from the data (ARaymarchVolume::AutoWindow, include/tbrm_volume_stats.h): the span between
 //                      the LOW and HIGH percentiles of the value histogram, 0.01,0.99 when not given
@@ -34,6 +34,10 @@
 //                      other voxel: a step costs COST along the axis of the file's finest ElementSpacing (the others in proportion) plus
 //                      the difference of the two voxels' 16-bit codes >> SHIFT, up to the cost LIMIT (0: no limit); printed as one
 //                      "compete" line
+//       --paint: after every other edit, a brush stroke (ARaymarchVolume::PaintLabel, include/tbrm_paint.h): capsules of RADIUS — a
+//                      distance in the units of the file's ElementSpacing — through the points (X, Y, Z), voxels that need not be whole
+//                      (rounded to eighths) nor inside the volume, are painted with LABEL over whatever is there; one point is a ball; an
+//                      empty label volume is attached when there is none; printed as one "paint" line
 //       --islands: after --grow, --morph, --margin and --smooth, the islands of label LABEL (the grown label when not given) (ARaymarchVolume::KeepLargestIslands
 //                      and its kin, include/tbrm_islands.h), 6-connected: OP is keep (the N largest stay, the others get label 0), remove
 //                      (islands of fewer than N voxels get label 0), split (the N largest get LABEL, LABEL + 1, ..) or fill (what the
@@ -179,8 +183,34 @@ int main(int argc, char** argv)
             argc -= 2;
             break;
         }
+    std::vector<int32_t> paint_points;
+    int paint_label = -1;
+    double paint_radius = 0.0;
+    bool paint = false;
+    for (int i = 1; i + 1 < argc; ++i)
+        if (!std::strcmp(argv[i], "--paint")) {
+            int used = 0;
+            if (std::sscanf(argv[i + 1], "%d,%lf@%n", &paint_label, &paint_radius, &used) < 2 || used == 0) { argc = 0; break; }
+            for (const char* at = argv[i + 1] + used;;) {
+                double v[3];
+                int n = 0;
+                if (std::sscanf(at, "%lf,%lf,%lf%n", &v[0], &v[1], &v[2], &n) < 3) { paint_points.clear(); break; }
+                for (double c : v) paint_points.push_back((int32_t) std::nearbyint(8.0 * c));
+                at += n;
+                if (*at != ';') {
+                    if (*at) paint_points.clear();
+                    break;
+                }
+                ++at;
+            }
+            if (paint_points.empty()) { argc = 0; break; }
+            paint = true;
+            for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
+            argc -= 2;
+            break;
+        }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]] [--margin OP,RADIUS[,LABEL]] [--smooth RADIUS[,ITERATIONS[,LABEL]]] [--islands OP,N[,LABEL]] [--scissors OP,LABEL,x0,y0,x1,y1,x2,y2[,..]] [--compete COST,SHIFT,LIMIT,LABEL@X,Y,Z,R[,LABEL@X,Y,Z,R..]]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]] [--margin OP,RADIUS[,LABEL]] [--smooth RADIUS[,ITERATIONS[,LABEL]]] [--islands OP,N[,LABEL]] [--scissors OP,LABEL,x0,y0,x1,y1,x2,y2[,..]] [--compete COST,SHIFT,LIMIT,LABEL@X,Y,Z,R[,LABEL@X,Y,Z,R..]] [--paint LABEL,RADIUS@X,Y,Z[;X,Y,Z..]]\n", argv[0]);
         return 2;
     }
     const int width = argc > 3 ? std::atoi(argv[3]) : 512, height = argc > 4 ? std::atoi(argv[4]) : 512;
@@ -355,6 +385,17 @@ int main(int argc, char** argv)
         for (int l = 0; l < 256; ++l)
             if (m.ClaimedPerLabel[l]) std::printf(" %d:%llu", l, (unsigned long long) m.ClaimedPerLabel[l]);
         std::printf("\n");
+    }
+    if (paint) { // after every other edit, before the frame
+        FPaintResult m;
+        if (tbrm_attach_empty_label_volume(volume.RaymarchResources.Handle) != TBRM_OK || !volume.PaintLabel(paint_points, paint_radius, paint_label, m)) {
+            std::fprintf(stderr, "paint failed: %s\n", paint_label < 0 || paint_label > 255 ? "LABEL must be 0 .. 255" : tbrm_last_error());
+            return 1;
+        }
+        std::printf("paint label %d radius %g points %d segments %d stamp %llu added %llu removed %llu relabelled %llu box %d %d %d .. %d %d %d bricks %d whole %d untouched %d evaluated launches %d\n",
+                    paint_label, paint_radius, m.Points, m.Segments, (unsigned long long) m.StampVoxels, (unsigned long long) m.Added, (unsigned long long) m.Removed,
+                    (unsigned long long) m.Relabelled, m.BoxMin[0], m.BoxMin[1], m.BoxMin[2], m.BoxMax[0], m.BoxMax[1], m.BoxMax[2], m.BricksWhole, m.BricksUntouched,
+                    m.BricksEvaluated, m.Launches);
     }
     if (!volume.RenderLit(cam, rgba.data())) {
         std::fprintf(stderr, "render failed: %s\n", tbrm_last_error());

@@ -27,6 +27,7 @@
 #include "tbrm_smooth.h"
 #include "tbrm_scissors.h"
 #include "tbrm_compete.h"
+#include "tbrm_paint.h"
 
 #include <algorithm>
 #include <cmath>
@@ -271,6 +272,7 @@ struct FVolumeHit {
     float Value = 0.0f;  // the filtered data value there, in the window's units
     int Label = -1;      // the label volume's voxel there; -1 without a label volume or a hit
     int Sample = -1;     // the sample's index along the ray
+    float Uvw[3] = {0, 0, 0}; // the sample's position in the volume's unit cube (tbrm_hit::uvw): what PaintAlongHits strings into a stroke
 };
 
 // What a region growing call found (include/tbrm_segment.h): ARaymarchVolume::GrowRegion / GrowRegionAt
@@ -336,6 +338,28 @@ struct FCompeteResult {
     int Passes = 0;
     int BoxMin[3] = {0, 0, 0}, BoxMax[3] = {-1, -1, -1}; // of the claimed voxels, inclusive; none: the volume's size and -1
     int StepCost[3] = {0, 0, 0};                 // what the call charged per step along each axis
+};
+
+// What a brush stroke found (include/tbrm_paint.h): ARaymarchVolume::PaintLabel, EraseLabel and PaintAlongHits
+struct FPaintResult {
+    uint64_t StampVoxels = 0;                    // voxels of the box within the stroke (and inside the gate)
+    uint64_t Added = 0, Removed = 0;             // voxels that joined / left the label
+    uint64_t Relabelled = 0;                     // label bytes that changed
+    int BoxMin[3] = {0, 0, 0}, BoxMax[3] = {-1, -1, -1}; // of what joined or left, inclusive; nothing: the volume's size and -1
+    int Points = 0, Segments = 0;                // of the stroke as painted
+    int BricksWhole = 0, BricksUntouched = 0, BricksEvaluated = 0;
+    int Launches = 0;
+    uint32_t Weights[3] = {0, 0, 0}, Limit = 0;  // the squared distance the radius and the spacing became (tbrm_host_paint_brush)
+};
+
+// The options of a brush stroke; the defaults paint over every label, anywhere, whatever the voxel's value
+struct FPaintOptions {
+    bool bGate = false;                          // paint only voxels whose stored value lies in Lo .. Hi
+    double Lo = 0.0, Hi = 0.0;
+    std::vector<int> Writable;                   // the labels a painted voxel may overwrite; empty: every label
+    int Origin[3] = {0, 0, 0}, Extent[3] = {0, 0, 0}; // the box; all-zero extent: the whole volume
+    int EraseTo = 0;                             // the label of voxels that leave
+    bool bMeasureOnly = false;
 };
 
 // The options of ARaymarchVolume::GrowFromSeeds; the defaults let every voxel that is no seed be claimed
@@ -745,6 +769,82 @@ public:
         return true;
     }
 
+    // The paint brush (include/tbrm_paint.h; no counterpart in the reference): a stroke of capsules of RadiusWorld — a distance in the
+    // unit of VoxelSpacing (voxels when there is none) — through Points (x0, y0, z0, x1, .. in eighths of a voxel: the centre of voxel i
+    // is at 8 i; one point is a ball) is painted into Label (Op TBRM_PAINT_PAINT: voxels that join get Label) or erased from it
+    // (TBRM_PAINT_ERASE: voxels that leave get Options.EraseTo), on the device, at the cost of the bricks the stroke touches. Like the
+    // other label edits it requests no recompute. Needs a label volume.
+    bool PaintStroke(int Op, const std::vector<int32_t>& Points, double RadiusWorld, int Label, FPaintResult& Out, const FPaintOptions& Options = FPaintOptions())
+    {
+        Out = FPaintResult{};
+        if (!RaymarchResources.Handle || Label < 0 || Label > 255 || Points.empty() || Points.size() % 3) return false;
+        const bool unit = VoxelSpacing[0] == 0.0 && VoxelSpacing[1] == 0.0 && VoxelSpacing[2] == 0.0;
+        const double spacing[3] = {unit ? 1.0 : VoxelSpacing[0], unit ? 1.0 : VoxelSpacing[1], unit ? 1.0 : VoxelSpacing[2]};
+        tbrm_paint_desc d{};
+        if (tbrm_host_paint_brush(spacing, RadiusWorld, d.weights, &d.limit) != TBRM_OK) return false;
+        for (int c = 0; c < 3; ++c) { d.origin[c] = Options.Origin[c]; d.extent[c] = Options.Extent[c]; }
+        d.op = Op;
+        d.new_label = Options.bMeasureOnly ? -1 : Label;
+        d.erase_label = Options.EraseTo;
+        d.gate = Options.bGate ? 1 : 0;
+        d.lo = Options.Lo;
+        d.hi = Options.Hi;
+        d.source[Label >> 5] = 1u << (Label & 31);
+        if (Options.Writable.empty())
+            for (uint32_t& w : d.writable) w = 0xffffffffu;
+        for (int l : Options.Writable) {
+            if (l < 0 || l > 255) return false;
+            d.writable[l >> 5] |= 1u << (l & 31);
+        }
+        tbrm_paint_result r{};
+        if (tbrm_paint_labels(RaymarchResources.Handle, &d, Points.data(), Points.size() / 3, &r) != TBRM_OK) return false;
+        Out.StampVoxels = r.stamp_voxels;
+        Out.Added = r.added;
+        Out.Removed = r.removed;
+        Out.Relabelled = r.relabelled;
+        for (int c = 0; c < 3; ++c) { Out.BoxMin[c] = r.bbox_min[c]; Out.BoxMax[c] = r.bbox_max[c]; Out.Weights[c] = d.weights[c]; }
+        Out.Points = (int) (Points.size() / 3);
+        Out.Segments = r.segments;
+        Out.BricksWhole = r.bricks_whole;
+        Out.BricksUntouched = r.bricks_untouched;
+        Out.BricksEvaluated = r.bricks_evaluated;
+        Out.Launches = r.launches;
+        Out.Limit = d.limit;
+        return true;
+    }
+    bool PaintLabel(const std::vector<int32_t>& Points, double RadiusWorld, int Label, FPaintResult& Out, const FPaintOptions& Options = FPaintOptions())
+    {
+        return PaintStroke(TBRM_PAINT_PAINT, Points, RadiusWorld, Label, Out, Options);
+    }
+    bool EraseLabel(const std::vector<int32_t>& Points, double RadiusWorld, int Label, FPaintResult& Out, const FPaintOptions& Options = FPaintOptions())
+    {
+        return PaintStroke(TBRM_PAINT_ERASE, Points, RadiusWorld, Label, Out, Options);
+    }
+    // A stroke along picked points of the rendered surface: the hits of Hits (PickVolume; records without a hit are passed over) in
+    // their order become the stroke's points (tbrm_host_paint_stroke: quantised to eighths of a voxel, repeats dropped, long segments
+    // split). No hit among them: false.
+    bool PaintAlongHits(const std::vector<FVolumeHit>& Hits, double RadiusWorld, int Label, FPaintResult& Out, int Op = TBRM_PAINT_PAINT,
+                        const FPaintOptions& Options = FPaintOptions())
+    {
+        Out = FPaintResult{};
+        if (!RaymarchResources.Handle) return false;
+        std::vector<float> Uvw;
+        for (const FVolumeHit& h : Hits)
+            if (h.bHit) Uvw.insert(Uvw.end(), h.Uvw, h.Uvw + 3);
+        if (Uvw.empty()) return false;
+        const bool unit = VoxelSpacing[0] == 0.0 && VoxelSpacing[1] == 0.0 && VoxelSpacing[2] == 0.0;
+        const double spacing[3] = {unit ? 1.0 : VoxelSpacing[0], unit ? 1.0 : VoxelSpacing[1], unit ? 1.0 : VoxelSpacing[2]};
+        uint32_t weights[3], limit = 0;
+        if (tbrm_host_paint_brush(spacing, RadiusWorld, weights, &limit) != TBRM_OK) return false;
+        const int32_t dims[3] = {RaymarchResources.SizeX, RaymarchResources.SizeY, RaymarchResources.SizeZ};
+        size_t n = 0;
+        tbrm_host_paint_stroke(dims, Uvw.data(), Uvw.size() / 3, weights, nullptr, 0, &n); // (how many points: the call itself says "too small")
+        if (n == 0) return false;
+        std::vector<int32_t> Points(3 * n);
+        if (tbrm_host_paint_stroke(dims, Uvw.data(), Uvw.size() / 3, weights, Points.data(), n, &n) != TBRM_OK) return false;
+        return PaintStroke(Op, Points, RadiusWorld, Label, Out, Options);
+    }
+
     // The islands of one label (include/tbrm_islands.h; no counterpart in the reference): its connected components, ordered by size,
     // on the device. The four tools are parameter sets of one rule. Like the other label edits they request no recompute. They need a
     // label volume.
@@ -964,6 +1064,7 @@ public:
         Out.Value = h.value;
         Out.Label = h.label;
         Out.Sample = h.sample;
+        for (int c = 0; c < 3; ++c) Out.Uvw[c] = h.uvw[c];
         return true;
     }
     // The visible surface as a depth buffer, Camera.width x Camera.height floats in the convention of the march's own scene depth

@@ -359,6 +359,57 @@ class COMPETE_RESULT(C.Structure):  # tbrm_compete_result
                 ("max_cost", C.c_uint32), ("passes", C.c_int32), ("bbox_min", C.c_int32 * 3), ("bbox_max", C.c_int32 * 3)]
 
 
+# every symbol include/tbrm_paint.h declares (the 3D paint brush; tests/test_paint_abi.py checks the header against this list)
+PAINT_SYMBOLS = ["tbrm_paint_abi_version", "tbrm_paint_labels", "tbrm_paint_counters", "tbrm_host_paint_brush", "tbrm_host_paint_stroke"]
+
+PAINT_ABI_VERSION = 1  # TBRM_PAINT_ABI_VERSION of include/tbrm_paint.h
+PAINT_MAX_POINTS = 4096
+PAINT_MAX_COORD = 1 << 18
+PAINT_MAX_DIM = 16384
+PAINT_MAX_WEIGHT = 65535
+PAINT_MAX_LIMIT = (1 << 30) - 1
+PAINT_MAX_REACH = 64
+PAINT_PAINT, PAINT_ERASE = 0, 1
+PAINT_OPS = {"paint": PAINT_PAINT, "erase": PAINT_ERASE}
+
+
+class PAINT_DESC(C.Structure):  # tbrm_paint_desc
+    _fields_ = [("origin", C.c_int32 * 3), ("extent", C.c_int32 * 3), ("op", C.c_int32), ("new_label", C.c_int32), ("erase_label", C.c_int32), ("gate", C.c_int32),
+                ("weights", C.c_uint32 * 3), ("limit", C.c_uint32), ("lo", C.c_double), ("hi", C.c_double), ("source", C.c_uint32 * 8), ("writable", C.c_uint32 * 8)]
+
+
+class PAINT_RESULT(C.Structure):  # tbrm_paint_result
+    _fields_ = [("stamp_voxels", C.c_uint64), ("added", C.c_uint64), ("removed", C.c_uint64), ("relabelled", C.c_uint64), ("bbox_min", C.c_int32 * 3),
+                ("bbox_max", C.c_int32 * 3), ("segments", C.c_int32), ("bricks_whole", C.c_int32), ("bricks_untouched", C.c_int32), ("bricks_evaluated", C.c_int32),
+                ("launches", C.c_int32), ("reserved", C.c_int32)]
+
+
+def paint_brush(spacing, radius):
+    """tbrm_host_paint_brush: (weights, limit) of a brush of `radius` on voxels of `spacing` (x, y, z; the same unit)"""
+    sp = (C.c_double * 3)(*[float(v) for v in spacing])
+    w, limit = (C.c_uint32 * 3)(), C.c_uint32()
+    check(load().tbrm_host_paint_brush(sp, float(radius), w, C.byref(limit)))
+    return tuple(int(v) for v in w), int(limit.value)
+
+
+def paint_stroke(dims, uvw, weights, capacity=None):
+    """tbrm_host_paint_stroke: unit-cube positions [n, 3] (a hit map's uvw) -> the stroke's points, int32 [m, 3] in eighths of a voxel;
+    capacity: the room offered (None: whatever the stroke needs)"""
+    d = (C.c_int32 * 3)(*[int(v) for v in dims])
+    w = (C.c_uint32 * 3)(*[int(v) for v in weights])
+    pos = np.ascontiguousarray(np.asarray(uvw, dtype=np.float32).reshape(-1, 3))
+    n_out = C.c_size_t()
+    lib = load()
+    if capacity is None:
+        code = lib.tbrm_host_paint_stroke(d, pos.ctypes.data_as(C.c_void_p), pos.shape[0], w, None, 0, C.byref(n_out))
+        if n_out.value == 0:
+            check(code)
+        capacity = n_out.value
+    out = np.zeros((int(capacity), 3), dtype=np.int32)
+    check(lib.tbrm_host_paint_stroke(d, pos.ctypes.data_as(C.c_void_p), pos.shape[0], w, out.ctypes.data_as(C.c_void_p), int(capacity), C.byref(n_out)))
+    return out[:n_out.value]
+
+
 def compete_float_range(lo, hi):
     """tbrm_host_compete_float_range: (float_origin, float_scale) that map the values [lo, hi] onto the codes 0 .. 65535"""
     o, s = C.c_float(), C.c_float()
@@ -590,6 +641,14 @@ def load():
     lib.tbrm_compete_labels.argtypes = [vp, P(COMPETE_DESC), vp, P(COMPETE_RESULT)]
     lib.tbrm_host_compete_float_range.argtypes = [C.c_double, C.c_double, P(C.c_float), P(C.c_float)]
     lib.tbrm_compete_counters.argtypes = [vp, P(C.c_uint64 * 4)]
+    have = lib.tbrm_paint_abi_version() if hasattr(lib, "tbrm_paint_abi_version") else -1
+    if have != PAINT_ABI_VERSION:
+        raise ImportError(f"{LIB_PATH} has paint ABI version {have}, this binding is written against {PAINT_ABI_VERSION}: rebuild it "
+                          "(`python tbraymarcherplugin_amd/build.py --force`)")
+    lib.tbrm_paint_labels.argtypes = [vp, P(PAINT_DESC), vp, C.c_size_t, P(PAINT_RESULT)]
+    lib.tbrm_paint_counters.argtypes = [vp, P(C.c_uint64 * 4)]
+    lib.tbrm_host_paint_brush.argtypes = [P(C.c_double * 3), C.c_double, P(C.c_uint32 * 3), P(C.c_uint32)]
+    lib.tbrm_host_paint_stroke.argtypes = [P(C.c_int32 * 3), vp, C.c_size_t, P(C.c_uint32 * 3), vp, C.c_size_t, P(C.c_size_t)]
     _lib = lib
     return lib
 
@@ -1195,6 +1254,49 @@ class Resources:
         out = (C.c_uint64 * 4)()
         check(self.lib.tbrm_compete_counters(self.handle, C.byref(out)))
         return {k: int(out[i]) for i, k in enumerate(self.COMPETE_COUNTERS)}
+
+    # the 3D paint brush (include/tbrm_paint.h): points in eighths of a voxel, boxes as (x, y, z)
+    def paint_desc(self, weights, limit, op, source, new_label, gate=None, origin=None, extent=None, writable=None, erase_label=0):
+        """weights, limit: the brush (paint_brush makes them); op: PAINT_* or its name; gate: None or (lo, hi) in stored units;
+        source, writable, new_label: as in morph_desc"""
+        d = PAINT_DESC()
+        if extent is not None:
+            d.origin[:] = [int(v) for v in (origin if origin is not None else (0, 0, 0))]
+            d.extent[:] = [int(v) for v in extent]
+        d.op = PAINT_OPS[op] if isinstance(op, str) else int(op)
+        d.new_label, d.erase_label = int(new_label), int(erase_label)
+        d.weights[:] = [int(v) for v in weights]
+        d.limit = int(limit)
+        if gate is not None:
+            d.gate, d.lo, d.hi = 1, float(gate[0]), float(gate[1])
+        for l in source:
+            d.source[int(l) >> 5] |= 1 << (int(l) & 31)
+        if writable is None:
+            d.writable[:] = [0xFFFFFFFF] * 8
+        else:
+            for l in writable:
+                d.writable[int(l) >> 5] |= 1 << (int(l) & 31)
+        return d
+
+    PAINT_FIELDS = ("stamp_voxels", "added", "removed", "relabelled", "segments", "bricks_whole", "bricks_untouched", "bricks_evaluated", "launches")
+
+    def paint_labels(self, points, weights, limit, op, source, new_label, gate=None, origin=None, extent=None, writable=None, erase_label=0):
+        """tbrm_paint_labels; points: int32 [n, 3] in eighths of a voxel (paint_stroke makes them from unit-cube positions):
+        PAINT_FIELDS, "bbox_min" and "bbox_max" as a dict"""
+        d = self.paint_desc(weights, limit, op, source, new_label, gate, origin, extent, writable, erase_label)
+        pts = np.ascontiguousarray(np.asarray(points, dtype=np.int32).reshape(-1, 3))
+        out = PAINT_RESULT()
+        check(self.lib.tbrm_paint_labels(self.handle, C.byref(d), pts.ctypes.data_as(C.c_void_p), pts.shape[0], C.byref(out)))
+        res = {k: int(getattr(out, k)) for k in self.PAINT_FIELDS}
+        res.update(bbox_min=tuple(out.bbox_min[:]), bbox_max=tuple(out.bbox_max[:]))
+        return res
+
+    PAINT_COUNTERS = ("paint_calls", "launches", "bricks_evaluated", "bricks_written")
+
+    def paint_counters(self):
+        out = (C.c_uint64 * 4)()
+        check(self.lib.tbrm_paint_counters(self.handle, C.byref(out)))
+        return {k: int(out[i]) for i, k in enumerate(self.PAINT_COUNTERS)}
 
     # the islands of a label (include/tbrm_islands.h): boxes and first voxels as (x, y, z)
     def islands_desc(self, source, connectivity=6, max_islands=0, min_voxels=0, keep_label=-1, label_step=0, drop_label=-1, spare_border=False,

@@ -448,6 +448,9 @@ enum Tunable : int {
                              // is (the test hook and the A/B switch). The result does not depend on it
     TUNE_SCISSORS_SKIP,      // tbrm_scissors_labels: 1: bricks whose result the source set or their corners give are not projected; 0: every brick of
                              // the range is, voxel by voxel (the test hook and the A/B switch). The result does not depend on it
+    TUNE_PAINT_SKIP,         // tbrm_paint_labels: 1: a brick tests only the segments whose grown box it meets, and one whose corners lie within
+                             // one segment is taken whole; 0: every brick of the range tests every voxel against every segment (the test
+                             // hook and the A/B switch). The result does not depend on it
     TUNE_COUNT
 };
 int tune(Tunable t);

@@ -441,6 +441,10 @@ struct tbrm_resources {
     char* d_compete_costs = nullptr;
     size_t compete_costs_bytes = 0;
     uint64_t compete_counters[4]{};    // tbrm_compete_counters
+    // the paint brush (tbrm_api_paint.cpp; include/tbrm_paint.h): the stroke's segments and runs as staged, only ever grown
+    char* d_paint = nullptr;
+    size_t paint_bytes = 0;
+    uint64_t paint_counters[4]{};      // tbrm_paint_counters
 };
 
 
