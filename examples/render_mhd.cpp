@@ -5,7 +5,7 @@
 //
 //   g++ -std=c++17 -O2 -I include examples/render_mhd.cpp -o render_mhd -L tbraymarcherplugin_amd/lib -ltbrm -lz
 //       (plus -Wl,-rpath,$PWD/tbraymarcherplugin_amd/lib -Wl,-rpath,/opt/rocm/lib to run it in place)
-//   ./render_mhd volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]] [--margin OP,RADIUS[,LABEL]] [--smooth RADIUS[,ITERATIONS[,LABEL]]] [--islands OP,N[,LABEL]] [--scissors OP,LABEL,x0,y0,x1,y1,x2,y2[,..]] [--compete COST,SHIFT,LIMIT,LABEL@X,Y,Z,R[,LABEL@X,Y,Z,R..]] [--paint LABEL,RADIUS@X,Y,Z[;X,Y,Z..]]
+//   ./render_mhd volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]] [--margin OP,RADIUS[,LABEL]] [--smooth RADIUS[,ITERATIONS[,LABEL]]] [--islands OP,N[,LABEL]] [--scissors OP,LABEL,x0,y0,x1,y1,x2,y2[,..]] [--compete COST,SHIFT,LIMIT,LABEL@X,Y,Z,R[,LABEL@X,Y,Z,R..]] [--paint LABEL,RADIUS@X,Y,Z[;X,Y,Z..]] [--surface LABEL,FILE.obj]
 //       --light-color: the key light's colour (components in [0, 1]) on an RGB light volume (include/tbrm_color_lights.h); the fill stays white
 //       --auto-window: the window comes from the data (ARaymarchVolume::AutoWindow, include/tbrm_volume_stats.h): the span between
 //                      the LOW and HIGH percentiles of the value histogram, 0.01,0.99 when not given
@@ -34,6 +34,9 @@
 //                      other voxel: a step costs COST along the axis of the file's finest ElementSpacing (the others in proportion) plus
 //                      the difference of the two voxels' 16-bit codes >> SHIFT, up to the cost LIMIT (0: no limit); printed as one
 //                      "compete" line
+//       --surface: after every edit, the surface of label LABEL as a triangle mesh (ARaymarchVolume::ExtractLabelSurface,
+//                      include/tbrm_surface.h) written to FILE.obj as a Wavefront OBJ: positions in the units of the file's ElementSpacing
+//                      (voxels when it has none), one normal per vertex; printed as one "surface" line
 //       --paint: after every other edit, a brush stroke (ARaymarchVolume::PaintLabel, include/tbrm_paint.h): capsules of RADIUS — a
 //                      distance in the units of the file's ElementSpacing — through the points (X, Y, Z), voxels that need not be whole
 //                      (rounded to eighths) nor inside the volume, are painted with LABEL over whatever is there; one point is a ball; an
@@ -47,6 +50,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "tbrm_volume_io.hpp" // includes tbrm_plugin.hpp
@@ -209,8 +213,21 @@ int main(int argc, char** argv)
             argc -= 2;
             break;
         }
+    int surface_label = -1;
+    std::string surface_file;
+    bool surface = false;
+    for (int i = 1; i + 1 < argc; ++i)
+        if (!std::strcmp(argv[i], "--surface")) {
+            int used = 0;
+            if (std::sscanf(argv[i + 1], "%d,%n", &surface_label, &used) < 1 || used == 0 || !argv[i + 1][used]) { argc = 0; break; }
+            surface_file = argv[i + 1] + used;
+            surface = true;
+            for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
+            argc -= 2;
+            break;
+        }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]] [--margin OP,RADIUS[,LABEL]] [--smooth RADIUS[,ITERATIONS[,LABEL]]] [--islands OP,N[,LABEL]] [--scissors OP,LABEL,x0,y0,x1,y1,x2,y2[,..]] [--compete COST,SHIFT,LIMIT,LABEL@X,Y,Z,R[,LABEL@X,Y,Z,R..]] [--paint LABEL,RADIUS@X,Y,Z[;X,Y,Z..]]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s volume.mhd out.ppm [width height steps] [--light-color r,g,b] [--auto-window[=LOW,HIGH]] [--pick X,Y] [--grow X,Y,TOL[,LABEL]] [--morph OP,R[,LABEL]] [--margin OP,RADIUS[,LABEL]] [--smooth RADIUS[,ITERATIONS[,LABEL]]] [--islands OP,N[,LABEL]] [--scissors OP,LABEL,x0,y0,x1,y1,x2,y2[,..]] [--compete COST,SHIFT,LIMIT,LABEL@X,Y,Z,R[,LABEL@X,Y,Z,R..]] [--paint LABEL,RADIUS@X,Y,Z[;X,Y,Z..]] [--surface LABEL,FILE.obj]\n", argv[0]);
         return 2;
     }
     const int width = argc > 3 ? std::atoi(argv[3]) : 512, height = argc > 4 ? std::atoi(argv[4]) : 512;
@@ -396,6 +413,36 @@ int main(int argc, char** argv)
                     paint_label, paint_radius, m.Points, m.Segments, (unsigned long long) m.StampVoxels, (unsigned long long) m.Added, (unsigned long long) m.Removed,
                     (unsigned long long) m.Relabelled, m.BoxMin[0], m.BoxMin[1], m.BoxMin[2], m.BoxMax[0], m.BoxMax[1], m.BoxMax[2], m.BricksWhole, m.BricksUntouched,
                     m.BricksEvaluated, m.Launches);
+    }
+    if (surface) { // after every edit, before the frame
+        FLabelSurface m;
+        if (!volume.ExtractLabelSurface(surface_label, m)) {
+            std::fprintf(stderr, "surface failed: %s\n", surface_label < 0 || surface_label > 255 ? "LABEL must be 0 .. 255" : tbrm_last_error());
+            return 1;
+        }
+        FILE* f = std::fopen(surface_file.c_str(), "w");
+        if (!f) {
+            std::fprintf(stderr, "surface failed: cannot write %s\n", surface_file.c_str());
+            return 1;
+        }
+        // the unit cube back to the file's units: voxel i at i * spacing
+        const bool unit = volume.VoxelSpacing[0] == 0.0 && volume.VoxelSpacing[1] == 0.0 && volume.VoxelSpacing[2] == 0.0;
+        const int size[3] = {volume.RaymarchResources.SizeX, volume.RaymarchResources.SizeY, volume.RaymarchResources.SizeZ};
+        std::fprintf(f, "# label %d: %llu voxels, %llu vertices, %llu triangles\n", surface_label, (unsigned long long) m.SetVoxels, (unsigned long long) m.Vertices,
+                     (unsigned long long) (2 * m.Quads));
+        for (size_t i = 0; i < m.Positions.size(); i += 3) {
+            double p[3];
+            for (int c = 0; c < 3; ++c) p[c] = (double) m.Positions[i + c] * (size[c] - 1) * (unit ? 1.0 : volume.VoxelSpacing[c]);
+            std::fprintf(f, "v %.6f %.6f %.6f\n", p[0], p[1], p[2]);
+        }
+        for (size_t i = 0; i < m.Normals.size(); i += 3) std::fprintf(f, "vn %.6f %.6f %.6f\n", m.Normals[i], m.Normals[i + 1], m.Normals[i + 2]);
+        for (size_t i = 0; i < m.Triangles.size(); i += 3)
+            std::fprintf(f, "f %u//%u %u//%u %u//%u\n", m.Triangles[i] + 1, m.Triangles[i] + 1, m.Triangles[i + 1] + 1, m.Triangles[i + 1] + 1, m.Triangles[i + 2] + 1, m.Triangles[i + 2] + 1);
+        std::fclose(f);
+        std::printf("surface label %d voxels %llu vertices %llu quads %llu axis %llu %llu %llu cells %d %d %d .. %d %d %d blocks %d evaluated %d skipped launches %d file %s\n", surface_label,
+                    (unsigned long long) m.SetVoxels, (unsigned long long) m.Vertices, (unsigned long long) m.Quads, (unsigned long long) m.QuadsAxis[0], (unsigned long long) m.QuadsAxis[1],
+                    (unsigned long long) m.QuadsAxis[2], m.CellMin[0], m.CellMin[1], m.CellMin[2], m.CellMax[0], m.CellMax[1], m.CellMax[2], m.BlocksEvaluated, m.BlocksSkipped, m.Launches,
+                    surface_file.c_str());
     }
     if (!volume.RenderLit(cam, rgba.data())) {
         std::fprintf(stderr, "render failed: %s\n", tbrm_last_error());

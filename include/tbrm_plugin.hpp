@@ -28,6 +28,7 @@
 #include "tbrm_scissors.h"
 #include "tbrm_compete.h"
 #include "tbrm_paint.h"
+#include "tbrm_surface.h"
 
 #include <algorithm>
 #include <cmath>
@@ -350,6 +351,19 @@ struct FPaintResult {
     int BricksWhole = 0, BricksUntouched = 0, BricksEvaluated = 0;
     int Launches = 0;
     uint32_t Weights[3] = {0, 0, 0}, Limit = 0;  // the squared distance the radius and the spacing became (tbrm_host_paint_brush)
+};
+
+// The surface of a label as a mesh (include/tbrm_surface.h): ARaymarchVolume::ExtractLabelSurface / MeasureLabelSurface
+struct FLabelSurface {
+    std::vector<float> Positions;                // x, y, z per vertex, in the volume's local unit cube (voxel i at i / (N - 1))
+    std::vector<float> Normals;                  // x, y, z per vertex: the record's integer normal scaled by the voxel spacing and
+                                                 // normalised; (0, 0, 0) where the cell is ambiguous
+    std::vector<uint32_t> Triangles;             // three indices each, counter-clockwise seen from outside
+    std::vector<tbrm_surface_vertex> Records;    // the exact records the positions come from
+    uint64_t SetVoxels = 0, Vertices = 0, Quads = 0;
+    uint64_t QuadsAxis[3] = {0, 0, 0};
+    int CellMin[3] = {0, 0, 0}, CellMax[3] = {-1, -1, -1}; // of the active cells, inclusive; none: the volume's size and -1
+    int BlocksEvaluated = 0, BlocksSkipped = 0, Launches = 0;
 };
 
 // The options of a brush stroke; the defaults paint over every label, anywhere, whatever the voxel's value
@@ -843,6 +857,73 @@ public:
         std::vector<int32_t> Points(3 * n);
         if (tbrm_host_paint_stroke(dims, Uvw.data(), Uvw.size() / 3, weights, Points.data(), n, &n) != TBRM_OK) return false;
         return PaintStroke(Op, Points, RadiusWorld, Label, Out, Options);
+    }
+
+    // The surface of Label as an indexed triangle mesh (include/tbrm_surface.h; the reference's closed surfaces are surface nets on the
+    // binary label map too): extracted on the device, one vertex per cell of 2 x 2 x 2 voxels the label's boundary passes through.
+    // Positions are in the volume's local unit cube — the space the hit maps' Uvw live in — so the actor's transform places the mesh
+    // where the volume is rendered. Origin / Extent cut the label to a box (all-zero extent: the whole volume); the surface is closed
+    // at the box's faces. A read: it changes no label and requests no recompute. Needs a label volume.
+    bool SurfaceDesc(int Label, const int Origin[3], const int Extent[3], tbrm_surface_desc& d) const
+    {
+        if (!RaymarchResources.Handle || Label < 0 || Label > 255) return false;
+        d = tbrm_surface_desc{};
+        for (int c = 0; c < 3; ++c) { d.origin[c] = Origin && Extent ? Origin[c] : 0; d.extent[c] = Extent ? Extent[c] : 0; }
+        d.source[Label >> 5] = 1u << (Label & 31);
+        const int32_t dims[3] = {RaymarchResources.SizeX, RaymarchResources.SizeY, RaymarchResources.SizeZ};
+        return tbrm_host_surface_unit_cube(dims, d.scale, d.offset) == TBRM_OK;
+    }
+    static void SurfaceCounts(const tbrm_surface_result& r, FLabelSurface& Out)
+    {
+        Out.SetVoxels = r.set_voxels;
+        Out.Vertices = r.vertices;
+        Out.Quads = r.quads;
+        for (int c = 0; c < 3; ++c) { Out.QuadsAxis[c] = r.quads_axis[c]; Out.CellMin[c] = r.cell_min[c]; Out.CellMax[c] = r.cell_max[c]; }
+        Out.BlocksEvaluated = r.blocks_evaluated;
+        Out.BlocksSkipped = r.blocks_skipped;
+        Out.Launches = r.launches;
+    }
+    bool MeasureLabelSurface(int Label, FLabelSurface& Out, const int Origin[3] = nullptr, const int Extent[3] = nullptr)
+    {
+        Out = FLabelSurface{};
+        tbrm_surface_desc d{};
+        if (!SurfaceDesc(Label, Origin, Extent, d)) return false;
+        d.flags = TBRM_SURFACE_MEASURE;
+        tbrm_surface_result r{};
+        if (tbrm_label_surface(RaymarchResources.Handle, &d, nullptr, nullptr, nullptr, &r) != TBRM_OK) return false;
+        SurfaceCounts(r, Out);
+        return true;
+    }
+    bool ExtractLabelSurface(int Label, FLabelSurface& Out, const int Origin[3] = nullptr, const int Extent[3] = nullptr)
+    {
+        if (!MeasureLabelSurface(Label, Out, Origin, Extent)) return false;
+        tbrm_surface_desc d{};
+        SurfaceDesc(Label, Origin, Extent, d);
+        d.flags = TBRM_SURFACE_TRIANGLES;
+        d.vertex_capacity = Out.Vertices;
+        d.quad_capacity = Out.Quads;
+        Out.Records.resize((size_t) Out.Vertices);
+        Out.Positions.resize(3 * (size_t) Out.Vertices);
+        Out.Triangles.resize(6 * (size_t) Out.Quads);
+        tbrm_surface_result r{};
+        if (tbrm_label_surface(RaymarchResources.Handle, &d, Out.Records.data(), Out.Triangles.data(), Out.Positions.data(), &r) != TBRM_OK) {
+            Out = FLabelSurface{};
+            return false;
+        }
+        SurfaceCounts(r, Out);
+        // the gradient of an indicator on voxels of unequal spacing: each component over its spacing
+        const bool unit = VoxelSpacing[0] == 0.0 && VoxelSpacing[1] == 0.0 && VoxelSpacing[2] == 0.0;
+        Out.Normals.resize(3 * (size_t) Out.Vertices);
+        for (size_t i = 0; i < Out.Records.size(); ++i) {
+            double n[3], len = 0.0;
+            for (int c = 0; c < 3; ++c) {
+                n[c] = (double) Out.Records[i].normal[c] / (unit ? 1.0 : VoxelSpacing[c]);
+                len += n[c] * n[c];
+            }
+            len = std::sqrt(len);
+            for (int c = 0; c < 3; ++c) Out.Normals[3 * i + c] = len > 0.0 ? (float) (n[c] / len) : 0.0f;
+        }
+        return true;
     }
 
     // The islands of one label (include/tbrm_islands.h; no counterpart in the reference): its connected components, ordered by size,

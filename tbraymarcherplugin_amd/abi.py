@@ -384,6 +384,50 @@ class PAINT_RESULT(C.Structure):  # tbrm_paint_result
                 ("launches", C.c_int32), ("reserved", C.c_int32)]
 
 
+# every symbol include/tbrm_surface.h declares (the surface of a label as a mesh; tests/test_surface_abi.py checks the header against this list)
+SURFACE_SYMBOLS = ["tbrm_surface_abi_version", "tbrm_label_surface", "tbrm_label_surface_device", "tbrm_surface_counters", "tbrm_host_surface_positions",
+                   "tbrm_host_surface_unit_cube"]
+
+SURFACE_ABI_VERSION = 1  # TBRM_SURFACE_ABI_VERSION of include/tbrm_surface.h
+SURFACE_MAX_DIM = 1 << 19
+SURFACE_TRIANGLES, SURFACE_MEASURE = 1, 2
+# tbrm_surface_vertex as a numpy record
+SURFACE_VERTEX_DTYPE = np.dtype([("cell", "<i4", 3), ("sum", "u1", 3), ("edges", "u1"), ("normal", "i1", 3), ("corners", "u1")])
+
+
+class SURFACE_VERTEX(C.Structure):  # tbrm_surface_vertex
+    _fields_ = [("cell", C.c_int32 * 3), ("sum", C.c_uint8 * 3), ("edges", C.c_uint8), ("normal", C.c_int8 * 3), ("corners", C.c_uint8)]
+
+
+class SURFACE_DESC(C.Structure):  # tbrm_surface_desc
+    _fields_ = [("origin", C.c_int32 * 3), ("extent", C.c_int32 * 3), ("flags", C.c_uint32), ("reserved", C.c_int32), ("vertex_capacity", C.c_uint64),
+                ("quad_capacity", C.c_uint64), ("scale", C.c_float * 3), ("offset", C.c_float * 3), ("source", C.c_uint32 * 8)]
+
+
+class SURFACE_RESULT(C.Structure):  # tbrm_surface_result
+    _fields_ = [("set_voxels", C.c_uint64), ("vertices", C.c_uint64), ("quads", C.c_uint64), ("quads_axis", C.c_uint64 * 3), ("cell_min", C.c_int32 * 3),
+                ("cell_max", C.c_int32 * 3), ("blocks_evaluated", C.c_int32), ("blocks_skipped", C.c_int32), ("launches", C.c_int32), ("written", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+def surface_unit_cube(dims):
+    """tbrm_host_surface_unit_cube: (scale, offset) that put voxel i at i / (N - 1), as float32 triples"""
+    d = (C.c_int32 * 3)(*[int(v) for v in dims])
+    scale, offset = (C.c_float * 3)(), (C.c_float * 3)()
+    check(load().tbrm_host_surface_unit_cube(d, scale, offset))
+    return tuple(np.float32(v) for v in scale), tuple(np.float32(v) for v in offset)
+
+
+def surface_positions(vertices, scale=(1.0, 1.0, 1.0), offset=(0.0, 0.0, 0.0)):
+    """tbrm_host_surface_positions: the float32 positions [n, 3] of vertex records (SURFACE_VERTEX_DTYPE)"""
+    v = np.ascontiguousarray(np.asarray(vertices, dtype=SURFACE_VERTEX_DTYPE).reshape(-1))
+    out = np.zeros((v.shape[0], 3), dtype=np.float32)
+    sc = (C.c_float * 3)(*[float(x) for x in scale])
+    of = (C.c_float * 3)(*[float(x) for x in offset])
+    check(load().tbrm_host_surface_positions(v.ctypes.data_as(C.c_void_p), v.shape[0], sc, of, out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
 def paint_brush(spacing, radius):
     """tbrm_host_paint_brush: (weights, limit) of a brush of `radius` on voxels of `spacing` (x, y, z; the same unit)"""
     sp = (C.c_double * 3)(*[float(v) for v in spacing])
@@ -649,6 +693,15 @@ def load():
     lib.tbrm_paint_counters.argtypes = [vp, P(C.c_uint64 * 4)]
     lib.tbrm_host_paint_brush.argtypes = [P(C.c_double * 3), C.c_double, P(C.c_uint32 * 3), P(C.c_uint32)]
     lib.tbrm_host_paint_stroke.argtypes = [P(C.c_int32 * 3), vp, C.c_size_t, P(C.c_uint32 * 3), vp, C.c_size_t, P(C.c_size_t)]
+    have = lib.tbrm_surface_abi_version() if hasattr(lib, "tbrm_surface_abi_version") else -1
+    if have != SURFACE_ABI_VERSION:
+        raise ImportError(f"{LIB_PATH} has surface ABI version {have}, this binding is written against {SURFACE_ABI_VERSION}: rebuild it "
+                          "(`python tbraymarcherplugin_amd/build.py --force`)")
+    lib.tbrm_label_surface.argtypes = [vp, P(SURFACE_DESC), vp, vp, vp, P(SURFACE_RESULT)]
+    lib.tbrm_label_surface_device.argtypes = [vp, P(SURFACE_DESC), vp, vp, vp, P(SURFACE_RESULT)]
+    lib.tbrm_surface_counters.argtypes = [vp, P(C.c_uint64 * 6)]
+    lib.tbrm_host_surface_positions.argtypes = [vp, C.c_size_t, P(C.c_float * 3), P(C.c_float * 3), vp]
+    lib.tbrm_host_surface_unit_cube.argtypes = [P(C.c_int32 * 3), P(C.c_float * 3), P(C.c_float * 3)]
     _lib = lib
     return lib
 
@@ -1297,6 +1350,71 @@ class Resources:
         out = (C.c_uint64 * 4)()
         check(self.lib.tbrm_paint_counters(self.handle, C.byref(out)))
         return {k: int(out[i]) for i, k in enumerate(self.PAINT_COUNTERS)}
+
+    # the surface of a set of labels as an indexed mesh (include/tbrm_surface.h): boxes as (x, y, z)
+    def surface_desc(self, source, origin=None, extent=None, triangles=False, measure=False, scale=None, offset=None, vertex_capacity=0, quad_capacity=0):
+        """source: the label values of the set; scale, offset: of the positions (None: voxel-index coordinates)"""
+        d = SURFACE_DESC()
+        if extent is not None:
+            d.origin[:] = [int(v) for v in (origin if origin is not None else (0, 0, 0))]
+            d.extent[:] = [int(v) for v in extent]
+        d.flags = (SURFACE_TRIANGLES if triangles else 0) | (SURFACE_MEASURE if measure else 0)
+        d.vertex_capacity, d.quad_capacity = int(vertex_capacity), int(quad_capacity)
+        d.scale[:] = [float(v) for v in (scale if scale is not None else (1.0, 1.0, 1.0))]
+        d.offset[:] = [float(v) for v in (offset if offset is not None else (0.0, 0.0, 0.0))]
+        for l in source:
+            d.source[int(l) >> 5] |= 1 << (int(l) & 31)
+        return d
+
+    SURFACE_FIELDS = ("set_voxels", "vertices", "quads", "blocks_evaluated", "blocks_skipped", "launches", "written")
+
+    @classmethod
+    def surface_result(cls, out):
+        res = {k: int(getattr(out, k)) for k in cls.SURFACE_FIELDS}
+        res.update(quads_axis=tuple(int(v) for v in out.quads_axis), cell_min=tuple(out.cell_min[:]), cell_max=tuple(out.cell_max[:]))
+        return res
+
+    def measure_label_surface(self, source, origin=None, extent=None):
+        """tbrm_label_surface with TBRM_SURFACE_MEASURE: the result fields, nothing written"""
+        d = self.surface_desc(source, origin, extent, measure=True)
+        out = SURFACE_RESULT()
+        check(self.lib.tbrm_label_surface(self.handle, C.byref(d), None, None, None, C.byref(out)))
+        return self.surface_result(out)
+
+    def label_surface(self, source, origin=None, extent=None, triangles=False, positions=True, scale=None, offset=None):
+        """measures, allocates, extracts: the result fields and "vertex" (SURFACE_VERTEX_DTYPE [n]), "indices" (uint32 [quads, 4 or 6]),
+        "positions" (float32 [n, 3], or None) as numpy arrays"""
+        n = self.measure_label_surface(source, origin, extent)
+        d = self.surface_desc(source, origin, extent, triangles, False, scale, offset, n["vertices"], n["quads"])
+        vertex = np.zeros(n["vertices"], dtype=SURFACE_VERTEX_DTYPE)
+        indices = np.zeros((n["quads"], 6 if triangles else 4), dtype=np.uint32)
+        pos = np.zeros((n["vertices"], 3), dtype=np.float32) if positions else None
+        out = SURFACE_RESULT()
+        check(self.lib.tbrm_label_surface(self.handle, C.byref(d), vertex.ctypes.data_as(C.c_void_p), indices.ctypes.data_as(C.c_void_p),
+                                          pos.ctypes.data_as(C.c_void_p) if positions else None, C.byref(out)))
+        res = self.surface_result(out)
+        res.update(vertex=vertex, indices=indices, positions=pos)
+        return res
+
+    def label_surface_device(self, source, vertices, indices, positions=None, origin=None, extent=None, triangles=False, scale=None, offset=None):
+        """tbrm_label_surface_device onto the caller's torch tensors on the handle's device: vertices (uint8 [capacity, 20] or int32
+        [capacity, 5]), indices (int32 / uint32-sized [capacity, 4 or 6]), positions (float32 [capacity, 3]) or None; the capacities
+        are the tensors' first dimensions. Returns the result fields"""
+        per = 6 if triangles else 4
+        assert vertices.is_contiguous() and indices.is_contiguous() and vertices.element_size() * vertices[0].numel() == 20 and indices.element_size() * indices[0].numel() == 4 * per
+        assert positions is None or (positions.is_contiguous() and positions.shape[0] >= vertices.shape[0] and positions.element_size() * positions[0].numel() == 12)
+        d = self.surface_desc(source, origin, extent, triangles, False, scale, offset, vertices.shape[0], indices.shape[0])
+        out = SURFACE_RESULT()
+        check(self.lib.tbrm_label_surface_device(self.handle, C.byref(d), vertices.data_ptr(), indices.data_ptr(), positions.data_ptr() if positions is not None else None,
+                                                 C.byref(out)))
+        return self.surface_result(out)
+
+    SURFACE_COUNTERS = ("surface_calls", "vertices_written", "quads_written", "blocks_evaluated", "scratch_bytes", "scratch_allocations")
+
+    def surface_counters(self):
+        out = (C.c_uint64 * 6)()
+        check(self.lib.tbrm_surface_counters(self.handle, C.byref(out)))
+        return {k: int(out[i]) for i, k in enumerate(self.SURFACE_COUNTERS)}
 
     # the islands of a label (include/tbrm_islands.h): boxes and first voxels as (x, y, z)
     def islands_desc(self, source, connectivity=6, max_islands=0, min_voxels=0, keep_label=-1, label_step=0, drop_label=-1, spare_border=False,

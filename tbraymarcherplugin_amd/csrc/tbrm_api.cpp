@@ -38,7 +38,7 @@ const TunableDef kTunables[TUNE_COUNT] = {
     {"chain_rect_planes", 1}, {"occ_overlap", 2}, {"light_sweep", 1}, {"sweep_prefetch", 0}, {"stream_priority", 0}, {"sweep_debug", 0},
     {"sweep_timeout_ms", 0}, {"fast_window_div", 1}, {"slab_sweep", 0}, {"gpu_timing", 1}, {"ray_tables", 1}, {"sweep_epoch_preset", 0}, {"occ_dual", 1}, {"sweep_chain", 4}, {"ray_xcd_rows", 1},
     {"ray_labels", 0}, {"stats_groups", 0}, {"occ_run", 4}, {"view_cache_mb", 1536}, {"grow_batch", 16}, {"morph_steps", 8},
-    {"margin_skip", 1}, {"smooth_skip", 1}, {"scissors_skip", 1}, {"paint_skip", 1},
+    {"margin_skip", 1}, {"smooth_skip", 1}, {"scissors_skip", 1}, {"paint_skip", 1}, {"surface_skip", 1},
 };
 struct TunableStore {
     std::atomic<int> v[TUNE_COUNT];
@@ -543,6 +543,7 @@ int tbrm_resources_destroy(tbrm_resources* r)
     (void) hipFree(r->d_compete);
     (void) hipFree(r->d_compete_costs);
     (void) hipFree(r->d_paint);
+    for (char* d : r->d_surface) (void) hipFree(d);
     (void) hipFree(r->d_alpha_prefix);
     (void) hipFree(r->d_counter);
     (void) hipFree(r->d_ray_tab);

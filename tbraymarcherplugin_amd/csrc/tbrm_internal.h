@@ -451,6 +451,8 @@ enum Tunable : int {
     TUNE_PAINT_SKIP,         // tbrm_paint_labels: 1: a brick tests only the segments whose grown box it meets, and one whose corners lie within
                              // one segment is taken whole; 0: every brick of the range tests every voxel against every segment (the test
                              // hook and the A/B switch). The result does not depend on it
+    TUNE_SURFACE_SKIP,       // tbrm_label_surface: 1: blocks of cells whose eight boards are all empty, or all full inside the box, are not
+                             // computed; 0: every block of the range is (the test hook and the A/B switch). The result does not depend on it
     TUNE_COUNT
 };
 int tune(Tunable t);

@@ -445,6 +445,11 @@ struct tbrm_resources {
     char* d_paint = nullptr;
     size_t paint_bytes = 0;
     uint64_t paint_counters[4]{};      // tbrm_paint_counters
+    // the surface of a label (tbrm_api_surface.cpp; include/tbrm_surface.h): [0] what the kernels keep per block of cells, [1] the
+    // staging of the host form's outputs; each only ever grown
+    char* d_surface[2] = {nullptr, nullptr};
+    size_t surface_bytes[2]{};
+    uint64_t surface_counters[6]{};    // tbrm_surface_counters ([4] is computed from surface_bytes)
 };
 
 
