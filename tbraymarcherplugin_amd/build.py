@@ -12,7 +12,7 @@ LIB_PATH = os.path.join(LIB_DIR, "libtbrm.so")
 # (source, object name, extra flags): tbrm_light_chain.hip is compiled once per light-volume format so that the two halves
 # of the chain kernel's instantiations build in parallel
 UNITS = [
-    ("tbrm_api.cpp", "tbrm_api", []), ("tbrm_api_render.cpp", "tbrm_api_render", []), ("tbrm_api_slabs.cpp", "tbrm_api_slabs", []), ("tbrm_api_labels.cpp", "tbrm_api_labels", []), ("tbrm_api_color_lights.cpp", "tbrm_api_color_lights", []), ("tbrm_api_volume_region.cpp", "tbrm_api_volume_region", []), ("tbrm_api_volume_stats.cpp", "tbrm_api_volume_stats", []), ("tbrm_api_hit.cpp", "tbrm_api_hit", []), ("tbrm_api_segment.cpp", "tbrm_api_segment", []), ("tbrm_api_morph.cpp", "tbrm_api_morph", []), ("tbrm_api_islands.cpp", "tbrm_api_islands", []), ("tbrm_api_margin.cpp", "tbrm_api_margin", []), ("tbrm_api_smooth.cpp", "tbrm_api_smooth", []), ("tbrm_api_scissors.cpp", "tbrm_api_scissors", []), ("tbrm_api_compete.cpp", "tbrm_api_compete", []), ("tbrm_api_paint.cpp", "tbrm_api_paint", []), ("tbrm_api_surface.cpp", "tbrm_api_surface", []), ("tbrm_light_plan.cpp", "tbrm_light_plan", []), ("tbrm_factor_cache.cpp", "tbrm_factor_cache", []), ("tbrm_light_enqueue.cpp", "tbrm_light_enqueue", []),
+    ("tbrm_api.cpp", "tbrm_api", []), ("tbrm_api_render.cpp", "tbrm_api_render", []), ("tbrm_api_slabs.cpp", "tbrm_api_slabs", []), ("tbrm_api_labels.cpp", "tbrm_api_labels", []), ("tbrm_api_color_lights.cpp", "tbrm_api_color_lights", []), ("tbrm_api_volume_region.cpp", "tbrm_api_volume_region", []), ("tbrm_api_volume_stats.cpp", "tbrm_api_volume_stats", []), ("tbrm_api_hit.cpp", "tbrm_api_hit", []), ("tbrm_api_segment.cpp", "tbrm_api_segment", []), ("tbrm_board_edit.cpp", "tbrm_board_edit", []), ("tbrm_api_morph.cpp", "tbrm_api_morph", []), ("tbrm_api_islands.cpp", "tbrm_api_islands", []), ("tbrm_api_margin.cpp", "tbrm_api_margin", []), ("tbrm_api_smooth.cpp", "tbrm_api_smooth", []), ("tbrm_api_scissors.cpp", "tbrm_api_scissors", []), ("tbrm_api_compete.cpp", "tbrm_api_compete", []), ("tbrm_api_paint.cpp", "tbrm_api_paint", []), ("tbrm_api_surface.cpp", "tbrm_api_surface", []), ("tbrm_light_plan.cpp", "tbrm_light_plan", []), ("tbrm_factor_cache.cpp", "tbrm_factor_cache", []), ("tbrm_light_enqueue.cpp", "tbrm_light_enqueue", []),
     ("tbrm_light_operators.cpp", "tbrm_light_operators", []), ("tbrm_block_lists.cpp", "tbrm_block_lists", []), ("tbrm_host_math.cpp", "tbrm_host_math", []),
     # tbrm_kernels.hip four times: everything but, and then only, the RGB-light form of k_raymarch_lit (colour handles), the view
     # cache's kernels (its recording forms, k_view_scan, k_relight) and the hit march (k_raymarch_hit, include/tbrm_hit.h)
@@ -25,7 +25,7 @@ UNITS = [
     for m in (1, 0, 2, 5)
 ]
 SOURCES = sorted({u[0] for u in UNITS})
-HEADERS = ["tbrm_ray_replay.inc", "tbrm_ray_locate.inc", "tbrm_ray_leap.inc", "tbrm_internal.h", "tbrm_resources.h", "tbrm_device_math.h", "tbrm_device_sampling.h", "tbrm_host_math.h", "tbrm_light_chain.h", "tbrm_light_sweep.h", "tbrm_sweep_tile.h", "tbrm_light_passes.h", "tbrm_stats_divisor.h", "tbrm_morph_plan.h", "tbrm_islands_rule.h", "tbrm_islands_kernels.h", "tbrm_margin_plan.h", "tbrm_margin_kernels.h", "tbrm_smooth_plan.h", "tbrm_smooth_kernels.h", "tbrm_scissors_plan.h", "tbrm_scissors_kernels.h", "tbrm_compete_plan.h", "tbrm_compete_kernels.h", "tbrm_paint_plan.h", "tbrm_paint_kernels.h", "tbrm_surface_plan.h", "tbrm_surface_kernels.h", "tbrm_brick_boards.h", "tbrm_occ_footprint.h", "tbrm_box.h",
+HEADERS = ["tbrm_ray_replay.inc", "tbrm_ray_locate.inc", "tbrm_ray_leap.inc", "tbrm_internal.h", "tbrm_resources.h", "tbrm_device_math.h", "tbrm_device_sampling.h", "tbrm_host_math.h", "tbrm_light_chain.h", "tbrm_light_sweep.h", "tbrm_sweep_tile.h", "tbrm_light_passes.h", "tbrm_stats_divisor.h", "tbrm_morph_plan.h", "tbrm_islands_rule.h", "tbrm_islands_kernels.h", "tbrm_margin_plan.h", "tbrm_margin_kernels.h", "tbrm_smooth_plan.h", "tbrm_smooth_kernels.h", "tbrm_scissors_plan.h", "tbrm_scissors_kernels.h", "tbrm_compete_plan.h", "tbrm_compete_kernels.h", "tbrm_paint_plan.h", "tbrm_paint_kernels.h", "tbrm_surface_plan.h", "tbrm_surface_kernels.h", "tbrm_brick_boards.h", "tbrm_board_edit.h", "tbrm_occ_footprint.h", "tbrm_box.h",
            "../../include/tbrm.h", "../../include/tbrm_labels.h", "../../include/tbrm_color_lights.h", "../../include/tbrm_volume_region.h", "../../include/tbrm_volume_stats.h", "../../include/tbrm_view_cache.h", "../../include/tbrm_hit.h", "../../include/tbrm_segment.h", "../../include/tbrm_morphology.h", "../../include/tbrm_islands.h", "../../include/tbrm_margin.h", "../../include/tbrm_smooth.h", "../../include/tbrm_scissors.h", "../../include/tbrm_compete.h", "../../include/tbrm_paint.h", "../../include/tbrm_surface.h"]
 
 # -ffp-contract=off + explicit fma is the arithmetic contract with the oracle (DESIGN.md "Arithmetic spec").

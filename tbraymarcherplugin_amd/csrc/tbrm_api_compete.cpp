@@ -23,20 +23,6 @@ static_assert(kCompeteMaxBatch == kGrowMaxBatch, "the passes are batched by regi
 
 namespace {
 
-// only ever grown: a call that needs no more than one before it allocates nothing
-int ensure_bytes(tbrm_resources* r, char*& buffer, size_t& have, size_t bytes, const char* what)
-{
-    if (have >= bytes) return TBRM_OK;
-    HIP_TRY(hipStreamSynchronize(r->stream));
-    (void) hipFree(buffer);
-    buffer = nullptr;
-    have = 0;
-    count_alloc(r, 1, what);
-    HIP_TRY(hipMalloc((void**) &buffer, bytes));
-    have = bytes;
-    return TBRM_OK;
-}
-
 int refuse(const CompeteVerdict& v, const tbrm_compete_desc* d)
 {
     switch (v.what) {
@@ -69,12 +55,7 @@ int tbrm_host_compete_float_range(double lo, double hi, float* float_origin, flo
     return TBRM_OK;
 }
 
-int tbrm_compete_counters(const tbrm_resources* r, uint64_t out[4])
-{
-    if (!r || !out) return fail(TBRM_ERR_INVALID_ARG, "null argument");
-    for (int k = 0; k < 4; ++k) out[k] = r->compete_counters[k];
-    return TBRM_OK;
-}
+int tbrm_compete_counters(const tbrm_resources* r, uint64_t out[4]) { return copy_counters(r, &tbrm_resources::compete_counters, out); }
 
 int tbrm_compete_labels(tbrm_resources* r, const tbrm_compete_desc* d, uint32_t* costs_out, tbrm_compete_result* out)
 {
@@ -100,7 +81,7 @@ int tbrm_compete_labels(tbrm_resources* r, const tbrm_compete_desc* d, uint32_t*
 
     p.data = r->d_data;
     p.labels = r->d_labels;
-    p.fmt = r->desc.data_format == TBRM_FMT_G8 ? FMT_U8 : (r->desc.data_format == TBRM_FMT_G16 ? FMT_U16 : FMT_F32);
+    p.fmt = data_fmt(r);
     p.bnx = r->dbn[0];
     p.bnxy = r->dbn[0] * r->dbn[1];
     if (is_float) { p.lo_f = (float) d->lo; p.hi_f = (float) d->hi; p.float_origin = d->float_origin; p.float_scale = d->float_scale; }

@@ -111,6 +111,30 @@ int labels_changed(tbrm_resources* r, const int32_t bbox_min[3], const int32_t b
     return refresh_live(r);
 }
 
+int fail_value_range(const tbrm_resources* r, double lo, double hi, bool relative)
+{
+    const double top = r->desc.data_format == TBRM_FMT_G8 ? 255.0 : 65535.0, least = relative ? -top : 0.0;
+    switch (value_range_refusal(lo, hi, r->desc.data_format == TBRM_FMT_R32_FLOAT, least, top)) {
+    case RANGE_ORDER: return fail(TBRM_ERR_INVALID_ARG, "range [%g, %g]: needs lo <= hi", lo, hi);
+    case RANGE_FLOAT: return fail(TBRM_ERR_INVALID_ARG, "range [%g, %g]: both must be finite as float32", lo, hi);
+    case RANGE_CODES: return fail(TBRM_ERR_INVALID_ARG, "range [%g, %g]: needs integral codes with %g <= lo <= hi <= %g", lo, hi, least, top);
+    default: return TBRM_OK;
+    }
+}
+
+int ensure_bytes(tbrm_resources* r, char*& buffer, size_t& have, size_t bytes, const char* what)
+{
+    if (have >= bytes) return TBRM_OK;
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    (void) hipFree(buffer);
+    buffer = nullptr;
+    have = 0;
+    if (what) count_alloc(r, 1, what);
+    HIP_TRY(hipMalloc((void**) &buffer, bytes));
+    have = bytes;
+    return TBRM_OK;
+}
+
 } // namespace tbrm_host
 
 namespace {

@@ -1,18 +1,15 @@
 // tbrm_api_margin.cpp — Euclidean margins of labels (include/tbrm_margin.h): validation, the plan (tbrm_margin_plan.h),
 // the scratch and the counters around the kernels of tbrm_margin_kernels.hip.
 //
-// A call is: the source set of the planned bricks from the label bytes into board 0 (k_morph_load, as it stands), one or two
-// transforms board -> board (k_margin_states, k_margin_xy, k_margin_z), the comparison of the final board with the label bytes inside
-// the box (k_morph_write, as it stands) and behind a write what every label write ends with (labels_changed). The
-// boards, their classes and the control words are the scratch of region growing; the states, the field and a distance map's staging
-// are the handle's d_margin.
-#include "tbrm_resources.h"
+// Between the frame's load and write (tbrm_board_edit.h): one or two transforms board -> board (k_margin_states,
+// k_margin_xy, k_margin_z). The states, the field and a distance map's staging are the handle's d_margin. tbrm_label_distance takes
+// the frame's load and ends on its own: one transform, the map out in chunks, nothing compared or written.
+#include "tbrm_board_edit.h"
 #include "tbrm_margin_kernels.h"
 #include "tbrm_margin_plan.h"
 #include "../../include/tbrm_margin.h"
 
 #include <algorithm>
-#include <cstring>
 
 using namespace tbrm;
 using namespace tbrm_host;
@@ -45,55 +42,31 @@ MarginScratch margin_scratch(char* base, size_t bricks)
     return m;
 }
 
-// at least what `bricks` bricks need: a call that needs no more than an earlier one allocates nothing
-int ensure_margin_scratch(tbrm_resources* r, size_t bricks)
-{
-    const size_t bytes = margin_scratch(nullptr, bricks).bytes;
-    if (r->margin_bytes >= bytes) return TBRM_OK;
-    HIP_TRY(hipStreamSynchronize(r->stream));
-    if (r->d_margin) HIP_TRY(hipFree(r->d_margin));
-    r->d_margin = nullptr;
-    r->margin_bytes = 0;
-    HIP_TRY(hipMalloc((void**) &r->d_margin, bytes));
-    r->margin_bytes = bytes;
-    return TBRM_OK;
-}
-
 // what both calls check of a desc before the handle's state; the box and the plan
-int margin_arguments(const tbrm_resources* r, const tbrm_margin_desc* d, MorphParams& p, MarginPlan& plan)
+int margin_arguments(const tbrm_resources* r, const tbrm_margin_desc* d, BoardEdit& edit, MarginPlan& plan)
 {
     if (d->op < TBRM_MARGIN_EXPAND || d->op > TBRM_MARGIN_CLOSE) return fail(TBRM_ERR_INVALID_ARG, "op %d: must be TBRM_MARGIN_EXPAND .. TBRM_MARGIN_CLOSE", (int) d->op);
-    if (d->new_label < -1 || d->new_label > 255) return fail(TBRM_ERR_INVALID_ARG, "new_label %d: must be 0 .. 255, or -1 to measure only", (int) d->new_label);
-    if (d->erase_label < 0 || d->erase_label > 255) return fail(TBRM_ERR_INVALID_ARG, "erase_label %d: must be 0 .. 255", (int) d->erase_label);
-    if (d->reserved != 0) return fail(TBRM_ERR_INVALID_ARG, "reserved = %d: must be 0", (int) d->reserved);
+    if (int e = label_codes(d->new_label, d->erase_label, d->reserved)) return e;
     int reach[3];
     if (!margin_reaches(d->weights, d->limit, reach))
         return fail(TBRM_ERR_INVALID_ARG, "weights (%u, %u, %u), limit %u: every weight must be >= 1, limit 1 .. 2^31 - 1, every reach isqrt(limit / weight) at most %d and one of them at least 1",
                     d->weights[0], d->weights[1], d->weights[2], d->limit, TBRM_MARGIN_MAX_REACH);
-    const tbrm_resources::Dims dims = r->data_dims();
-    const BoxVerdict v = box_resolve(dims, d->origin, d->extent, true, &p.box, nullptr);
-    if (v.what != BOX_OK) return fail_box(v, true, dims, d->origin, d->extent);
-    for (int c = 0; c < 3; ++c) p.dims[c] = dims[c];
-    if (int e = begin_label_edit(r, "no label volume")) return e;
+    if (int e = edit.begin(r, d->origin, d->extent)) return e;
+    const MorphParams& p = edit.p;
     if (!margin_plan(p.dims, p.box.origin, p.box.end, d->op, d->weights, d->limit, &plan)) return fail(TBRM_ERR_INVALID_ARG, "no plan for these arguments");
     return TBRM_OK;
 }
 
-// the parameters of the morphology kernels this call borrows (k_morph_load, k_morph_write) and of its own
-void margin_params(const tbrm_resources* r, const tbrm_margin_desc* d, const MarginPlan& plan, const GrowScratch& g, const MarginScratch& m,
-                   MorphParams& p, MarginParams& q)
+// the scratch of both kinds, the frame's bind, the plan's ranges and the parameters of the call's own kernels
+int margin_params(tbrm_resources* r, const tbrm_margin_desc* d, const MarginPlan& plan, BoardEdit& edit, MarginScratch& m, MarginParams& q)
 {
-    p.labels = r->d_labels;
-    p.bnx = r->dbn[0];
-    p.bnxy = r->dbn[0] * r->dbn[1];
-    for (int c = 0; c < 3; ++c) { p.range.b0[c] = plan.b0[c]; p.range.nb[c] = plan.nb[c]; p.wrange.b0[c] = plan.wb0[c]; p.wrange.nb[c] = plan.wnb[c]; }
-    for (int w = 0; w < 8; ++w) { p.source[w] = d->source[w]; p.writable[w] = d->writable[w]; }
-    p.bits = g.bits;
-    p.cls[0] = g.act[0];
-    p.cls[1] = g.act[1];
-    p.new_label = d->new_label;
-    p.erase_label = d->erase_label;
-    p.ctl = g.ctl;
+    MorphParams& p = edit.p;
+    if (int e = edit.bind(r, d)) return e;
+    edit.ranges(plan);
+    const size_t bricks = (size_t) range_bricks(p.range);
+    // (not counted in tbrm_path_counters [12], unlike the other operators' scratch)
+    if (int e = ensure_bytes(r, r->d_margin, r->margin_bytes, margin_scratch(nullptr, bricks).bytes, nullptr)) return e;
+    m = margin_scratch(r->d_margin, bricks);
 
     q.bnx = p.bnx;
     q.bnxy = p.bnxy;
@@ -106,14 +79,15 @@ void margin_params(const tbrm_resources* r, const tbrm_margin_desc* d, const Mar
         q.kb[c] = (plan.reach[c] + kBrick - 1) / kBrick;
     }
     q.limit = d->limit;
-    q.bits = g.bits;
-    q.cls[0] = g.act[0];
-    q.cls[1] = g.act[1];
+    q.bits = p.bits;
+    q.cls[0] = p.cls[0];
+    q.cls[1] = p.cls[1];
     q.skip = tune(TUNE_MARGIN_SKIP) != 0;
     q.state = m.state;
     q.field = m.field;
     q.dist = m.dist;
-    q.ctl = g.ctl;
+    q.ctl = p.ctl;
+    return TBRM_OK;
 }
 
 } // namespace
@@ -131,88 +105,56 @@ int tbrm_host_margin_weights(const double spacing[3], double radius, uint32_t we
     return TBRM_OK;
 }
 
-int tbrm_margin_counters(const tbrm_resources* r, uint64_t out[4])
-{
-    if (!r || !out) return fail(TBRM_ERR_INVALID_ARG, "null argument");
-    for (int k = 0; k < 4; ++k) out[k] = r->margin_counters[k];
-    return TBRM_OK;
-}
+int tbrm_margin_counters(const tbrm_resources* r, uint64_t out[4]) { return copy_counters(r, &tbrm_resources::margin_counters, out); }
 
 int tbrm_margin_labels(tbrm_resources* r, const tbrm_margin_desc* d, tbrm_margin_result* out)
 {
     if (!r || !d || !out) return fail(TBRM_ERR_INVALID_ARG, "null argument");
     if (int e = refuse_resident(r)) return e;
-    MorphParams p{};
+    BoardEdit edit(MORPH_CTL_WORDS);
     MarginParams q{};
     MarginPlan plan;
-    if (int e = margin_arguments(r, d, p, plan)) return e;
-    if (int e = ensure_grow_scratch(r)) return e;
-    const BrickRange range{{plan.b0[0], plan.b0[1], plan.b0[2]}, {plan.nb[0], plan.nb[1], plan.nb[2]}};
-    const size_t bricks = (size_t) range_bricks(range);
-    if (int e = ensure_margin_scratch(r, bricks)) return e;
-    margin_params(r, d, plan, grow_scratch(r), margin_scratch(r->d_margin, bricks), p, q);
+    MarginScratch m;
+    if (int e = margin_arguments(r, d, edit, plan)) return e;
+    if (int e = margin_params(r, d, plan, edit, m, q)) return e;
 
-    int32_t ctl[MORPH_CTL_WORDS];
-    ctl_start(ctl, MORPH_CTL_WORDS, MORPH_MIN_X, p.dims);
-    HIP_TRY(hipMemcpyAsync(p.ctl, ctl, sizeof(ctl), hipMemcpyHostToDevice, r->stream));
-    HIP_TRY(launch_morph_load(p, r->stream));
+    if (int e = edit.load(r)) return e;
     for (int i = 0; i < plan.transforms; ++i) {
         q.from = i & 1;
         q.shrink = plan.shrink[i];
         HIP_TRY(launch_margin_states(q, r->stream));
         HIP_TRY(launch_margin_xy(q, r->stream));
         q.layer0 = 0;
-        HIP_TRY(launch_margin_z(q, false, range.nb[2], r->stream));
+        HIP_TRY(launch_margin_z(q, false, q.range.nb[2], r->stream));
     }
-    p.from = plan.transforms & 1; // the board the last transform wrote
-    HIP_TRY(launch_morph_write(p, r->stream));
-    HIP_TRY(hipMemcpyAsync(ctl, p.ctl, sizeof(ctl), hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(hipStreamSynchronize(r->stream));
+    if (int e = edit.write(r, plan.transforms & 1)) return e; // the board the last transform wrote
 
-    uint64_t counts[MORPH_CTL_COUNTS];
-    memcpy(counts, ctl, sizeof(counts));
     memset(out, 0, sizeof(*out));
-    out->source_voxels = counts[MORPH_SOURCE];
-    out->result_voxels = counts[MORPH_RESULT];
-    out->added = counts[MORPH_ADDED];
-    out->removed = counts[MORPH_REMOVED];
-    out->relabelled = counts[MORPH_RELABELLED];
-    for (int c = 0; c < 3; ++c) { out->bbox_min[c] = ctl[MORPH_MIN_X + c]; out->bbox_max[c] = ctl[MORPH_MAX_X + c]; out->reach[c] = plan.reach[c]; }
+    edit.result(out);
+    for (int c = 0; c < 3; ++c) out->reach[c] = plan.reach[c];
     out->launches = plan.transforms * kMarginLaunchesPerTransform;
-    ++r->margin_counters[0];
-    r->margin_counters[1] += (uint64_t) out->launches;
-    r->margin_counters[2] += counts[MORPH_WINDOWS];
-    r->margin_counters[3] += counts[MORPH_BRICKS_WRITTEN];
-
-    if (d->new_label >= 0) return labels_changed(r, out->bbox_min, out->bbox_max); // (nothing joined or left: nothing to do)
-    return TBRM_OK;
+    return edit.end(r, r->margin_counters, out->launches);
 }
 
 int tbrm_label_distance(tbrm_resources* r, const tbrm_margin_desc* d, int32_t inside, void* out_host, size_t out_bytes)
 {
     if (!r || !d || !out_host) return fail(TBRM_ERR_INVALID_ARG, "null argument");
     if (int e = refuse_resident(r)) return e;
-    MorphParams p{};
+    BoardEdit edit(MORPH_CTL_WORDS);
+    const MorphParams& p = edit.p;
     MarginParams q{};
     MarginPlan plan;
+    MarginScratch m;
     tbrm_margin_desc one = *d;
-    if (int e = margin_arguments(r, &one, p, plan)) return e; // (the op is checked, then replaced: a map is one transform)
+    if (int e = margin_arguments(r, &one, edit, plan)) return e; // (the op is checked, then replaced: a map is one transform)
     one.op = inside ? TBRM_MARGIN_SHRINK : TBRM_MARGIN_EXPAND;
     if (!margin_plan(p.dims, p.box.origin, p.box.end, one.op, one.weights, one.limit, &plan)) return fail(TBRM_ERR_INVALID_ARG, "no plan for these arguments");
     const size_t ex = (size_t) (p.box.end[0] - p.box.origin[0]), ey = (size_t) (p.box.end[1] - p.box.origin[1]), ez = (size_t) (p.box.end[2] - p.box.origin[2]);
     if (out_bytes != ex * ey * ez * sizeof(uint32_t))
         return fail(TBRM_ERR_INVALID_ARG, "out_bytes = %zu: the box holds %zu x %zu x %zu voxels of 4 bytes", out_bytes, ex, ey, ez);
-    if (int e = ensure_grow_scratch(r)) return e;
-    const BrickRange range{{plan.b0[0], plan.b0[1], plan.b0[2]}, {plan.nb[0], plan.nb[1], plan.nb[2]}};
-    const size_t bricks = (size_t) range_bricks(range);
-    if (int e = ensure_margin_scratch(r, bricks)) return e;
-    const MarginScratch m = margin_scratch(r->d_margin, bricks);
-    margin_params(r, &one, plan, grow_scratch(r), m, p, q);
+    if (int e = margin_params(r, &one, plan, edit, m, q)) return e;
 
-    int32_t ctl[MORPH_CTL_WORDS];
-    ctl_start(ctl, MORPH_CTL_WORDS, MORPH_MIN_X, p.dims);
-    HIP_TRY(hipMemcpyAsync(p.ctl, ctl, sizeof(ctl), hipMemcpyHostToDevice, r->stream));
-    HIP_TRY(launch_morph_load(p, r->stream));
+    if (int e = edit.load(r)) return e;
     q.from = 0;
     q.shrink = plan.shrink[0];
     HIP_TRY(launch_margin_states(q, r->stream));
@@ -224,20 +166,17 @@ int tbrm_label_distance(tbrm_resources* r, const tbrm_margin_desc* d, int32_t in
     for (size_t z = 0; z < ez; z += per_chunk) {
         q.z0 = p.box.origin[2] + (int) z;
         q.z1 = p.box.origin[2] + (int) std::min(ez, z + per_chunk);
-        q.layer0 = (q.z0 >> kBrickShift) - range.b0[2];
+        q.layer0 = (q.z0 >> kBrickShift) - q.range.b0[2];
         const int layers = ((q.z1 - 1) >> kBrickShift) - (q.z0 >> kBrickShift) + 1;
         HIP_TRY(launch_margin_z(q, true, layers, r->stream));
         HIP_TRY(hipMemcpyAsync((uint32_t*) out_host + z * ex * ey, m.dist, (size_t) (q.z1 - q.z0) * ex * ey * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
         HIP_TRY(hipStreamSynchronize(r->stream)); // (the next chunk overwrites the staging)
         ++launches;
     }
-    HIP_TRY(hipMemcpyAsync(ctl, p.ctl, sizeof(ctl), hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(hipStreamSynchronize(r->stream));
-    uint64_t counts[MORPH_CTL_COUNTS];
-    memcpy(counts, ctl, sizeof(counts));
+    if (int e = edit.read_ctl(r)) return e;
     ++r->margin_counters[0];
     r->margin_counters[1] += (uint64_t) launches;
-    r->margin_counters[2] += counts[MORPH_WINDOWS];
+    r->margin_counters[2] += edit.count(MORPH_WINDOWS);
     return TBRM_OK;
 }
 

@@ -1,18 +1,13 @@
 // tbrm_api_paint.cpp — the 3D paint brush (include/tbrm_paint.h): validation, the stroke's staging and the counters
 // around the kernel of tbrm_paint_kernels.hip, and the two host functions (tbrm_paint_plan.h).
 //
-// A call is: the plan of the stroke (segments, runs, the work box) on the host and into the handle's staging, the source set of the
-// work box's bricks from the label bytes into board 0 (k_morph_load, as it stands), k_paint board 0 -> board 1, the comparison of
-// board 1 with the label bytes inside the work box (k_morph_write, as it stands) and behind a write what every label write ends with
-// (labels_changed). Outside the work box M is empty and R = S: cutting the box to it changes nothing but the cost. The
-// boards, their classes and the control words are the scratch of region growing.
-#include "tbrm_resources.h"
+// Ahead of the frame's load (tbrm_board_edit.h): the plan of the stroke (segments, runs, the work box) on the host and
+// into the handle's staging. Between load and write: k_paint board 0 -> board 1. The frame works on the work box: outside it M is
+// empty and R = S, so cutting the box to it changes nothing but the cost.
+#include "tbrm_board_edit.h"
 #include "tbrm_paint_kernels.h"
 #include "../../include/tbrm_paint.h"
 #include "../../include/tbrm_margin.h"
-
-#include <cmath>
-#include <cstring>
 
 using namespace tbrm;
 using namespace tbrm_host;
@@ -40,23 +35,8 @@ PaintScratch paint_scratch(char* base, size_t n_segs, size_t n_runs)
     return s;
 }
 
-// only ever grown: a call with a stroke no longer than one before it allocates nothing
-int ensure_paint_scratch(tbrm_resources* r, size_t n_segs, size_t n_runs)
-{
-    const size_t bytes = paint_scratch(nullptr, n_segs, n_runs).bytes;
-    if (r->paint_bytes >= bytes) return TBRM_OK;
-    HIP_TRY(hipStreamSynchronize(r->stream));
-    (void) hipFree(r->d_paint);
-    r->d_paint = nullptr;
-    r->paint_bytes = 0;
-    count_alloc(r, 1, "paint stroke staging");
-    HIP_TRY(hipMalloc((void**) &r->d_paint, bytes));
-    r->paint_bytes = bytes;
-    return TBRM_OK;
-}
-
 // what the call checks of a desc and a stroke before the handle's state; the box
-int paint_arguments_of(const tbrm_resources* r, const tbrm_paint_desc* d, const int32_t* points, size_t n_points, MorphParams& p)
+int paint_arguments_of(const tbrm_resources* r, const tbrm_paint_desc* d, const int32_t* points, size_t n_points, BoardEdit& edit)
 {
     const tbrm_resources::Dims dims = r->data_dims();
     const int dd[3] = {dims[0], dims[1], dims[2]};
@@ -76,41 +56,22 @@ int paint_arguments_of(const tbrm_resources* r, const tbrm_paint_desc* d, const 
         return fail(TBRM_ERR_INVALID_ARG, "point %d: coordinate %d = %d, must be within +-%d eighths of a voxel", v.index, v.axis, (int) points[3 * (size_t) v.index + v.axis], TBRM_PAINT_MAX_COORD);
     case PAINT_SEGMENT: return fail(TBRM_ERR_INVALID_ARG, "segment %d: its squared length must be below 2^30 (tbrm_host_paint_stroke splits it)", v.index);
     }
-    if (d->new_label < -1 || d->new_label > 255) return fail(TBRM_ERR_INVALID_ARG, "new_label %d: must be 0 .. 255, or -1 to measure only", (int) d->new_label);
-    if (d->erase_label < 0 || d->erase_label > 255) return fail(TBRM_ERR_INVALID_ARG, "erase_label %d: must be 0 .. 255", (int) d->erase_label);
-    if (d->gate) { // the rules of tbrm_grow_desc without relative_to_seed
-        if (!(d->lo <= d->hi)) return fail(TBRM_ERR_INVALID_ARG, "range [%g, %g]: needs lo <= hi", d->lo, d->hi);
-        if (r->desc.data_format == TBRM_FMT_R32_FLOAT) {
-            if (!std::isfinite(d->lo) || !std::isfinite(d->hi) || !std::isfinite((float) d->lo) || !std::isfinite((float) d->hi))
-                return fail(TBRM_ERR_INVALID_ARG, "range [%g, %g]: both must be finite as float32", d->lo, d->hi);
-        } else {
-            const double top = r->desc.data_format == TBRM_FMT_G8 ? 255.0 : 65535.0;
-            if (!(d->lo >= 0.0 && d->hi <= top) || d->lo != std::floor(d->lo) || d->hi != std::floor(d->hi))
-                return fail(TBRM_ERR_INVALID_ARG, "range [%g, %g]: needs integral codes with 0 <= lo <= hi <= %g", d->lo, d->hi, top);
-        }
-    }
-    const BoxVerdict b = box_resolve(dims, d->origin, d->extent, true, &p.box, nullptr);
-    if (b.what != BOX_OK) return fail_box(b, true, dims, d->origin, d->extent);
-    for (int c = 0; c < 3; ++c) p.dims[c] = dims[c];
-    return begin_label_edit(r, "no label volume");
+    if (int e = label_codes(d->new_label, d->erase_label, 0)) return e; // (the desc has no reserved field)
+    if (d->gate)
+        if (int e = fail_value_range(r, d->lo, d->hi, false)) return e;
+    return edit.begin(r, d->origin, d->extent);
 }
 
-// the parameters of the morphology kernels this call borrows (k_morph_load, k_morph_write) and of its own
-void paint_params(const tbrm_resources* r, const tbrm_paint_desc* d, const PaintPlan& plan, const GrowScratch& g, const PaintScratch& m, MorphParams& p, PaintParams& q)
+// the staging, the frame's bind on the work box and the parameters of the call's own kernel
+int paint_params(tbrm_resources* r, const tbrm_paint_desc* d, const PaintPlan& plan, BoardEdit& edit, PaintScratch& m, PaintParams& q)
 {
-    p.labels = r->d_labels;
-    p.bnx = r->dbn[0];
-    p.bnxy = r->dbn[0] * r->dbn[1];
+    MorphParams& p = edit.p;
+    if (int e = edit.bind(r, d)) return e;
     p.box = plan.work;
     p.range = plan.range;
     p.wrange = plan.range; // no reach: the bricks of the work box
-    for (int w = 0; w < 8; ++w) { p.source[w] = d->source[w]; p.writable[w] = d->writable[w]; }
-    p.bits = g.bits;
-    p.cls[0] = g.act[0];
-    p.cls[1] = g.act[1];
-    p.new_label = d->new_label;
-    p.erase_label = d->erase_label;
-    p.ctl = g.ctl;
+    if (int e = ensure_bytes(r, r->d_paint, r->paint_bytes, paint_scratch(nullptr, plan.segs.size(), plan.runs.size()).bytes, "paint stroke staging")) return e;
+    m = paint_scratch(r->d_paint, plan.segs.size(), plan.runs.size());
 
     q.bnx = p.bnx;
     q.bnxy = p.bnxy;
@@ -125,15 +86,16 @@ void paint_params(const tbrm_resources* r, const tbrm_paint_desc* d, const Paint
     q.n_segs = (int) plan.segs.size();
     q.n_runs = (int) plan.runs.size();
     q.data = r->d_data;
-    q.fmt = !d->gate ? kPaintNoGate : (r->desc.data_format == TBRM_FMT_G8 ? FMT_U8 : (r->desc.data_format == TBRM_FMT_G16 ? FMT_U16 : FMT_F32));
+    q.fmt = d->gate ? data_fmt(r) : kPaintNoGate;
     if (d->gate) {
         if (q.fmt == FMT_F32) { q.lo_f = (float) d->lo; q.hi_f = (float) d->hi; }
         else { q.lo_code = (uint32_t) d->lo; q.hi_code = (uint32_t) d->hi; }
     }
-    q.bits = g.bits;
-    q.cls[0] = g.act[0];
-    q.cls[1] = g.act[1];
-    q.ctl = g.ctl;
+    q.bits = p.bits;
+    q.cls[0] = p.cls[0];
+    q.cls[1] = p.cls[1];
+    q.ctl = p.ctl;
+    return TBRM_OK;
 }
 
 } // namespace
@@ -173,20 +135,17 @@ int tbrm_host_paint_stroke(const int32_t dims[3], const float* uvw, size_t n, co
     return TBRM_OK;
 }
 
-int tbrm_paint_counters(const tbrm_resources* r, uint64_t out[4])
-{
-    if (!r || !out) return fail(TBRM_ERR_INVALID_ARG, "null argument");
-    for (int k = 0; k < 4; ++k) out[k] = r->paint_counters[k];
-    return TBRM_OK;
-}
+int tbrm_paint_counters(const tbrm_resources* r, uint64_t out[4]) { return copy_counters(r, &tbrm_resources::paint_counters, out); }
 
 int tbrm_paint_labels(tbrm_resources* r, const tbrm_paint_desc* d, const int32_t* points_xyz, size_t n_points, tbrm_paint_result* out)
 {
     if (!r || !d || !points_xyz || !out) return fail(TBRM_ERR_INVALID_ARG, "null argument");
     if (int e = refuse_resident(r)) return e;
-    MorphParams p{};
+    BoardEdit edit(PAINT_CTL_WORDS);
+    const MorphParams& p = edit.p;
     PaintParams q{};
-    if (int e = paint_arguments_of(r, d, points_xyz, n_points, p)) return e;
+    PaintScratch m;
+    if (int e = paint_arguments_of(r, d, points_xyz, n_points, edit)) return e;
     PaintPlan plan;
     paint_plan(p.box, d->weights, d->limit, points_xyz, n_points, plan);
 
@@ -196,40 +155,20 @@ int tbrm_paint_labels(tbrm_resources* r, const tbrm_paint_desc* d, const int32_t
     ++r->paint_counters[0];
     if (plan.empty) return TBRM_OK; // the stroke misses the box: nothing is launched, nothing changes
 
-    if (int e = ensure_grow_scratch(r)) return e;
-    if (int e = ensure_paint_scratch(r, plan.segs.size(), plan.runs.size())) return e;
-    const PaintScratch m = paint_scratch(r->d_paint, plan.segs.size(), plan.runs.size());
-    paint_params(r, d, plan, grow_scratch(r), m, p, q);
-
-    int32_t ctl[PAINT_CTL_WORDS];
-    ctl_start(ctl, PAINT_CTL_WORDS, MORPH_MIN_X, p.dims);
-    HIP_TRY(hipMemcpyAsync(p.ctl, ctl, sizeof(ctl), hipMemcpyHostToDevice, r->stream));
+    if (int e = paint_params(r, d, plan, edit, m, q)) return e;
     HIP_TRY(hipMemcpyAsync(m.segs, plan.segs.data(), plan.segs.size() * sizeof(PaintSegment), hipMemcpyHostToDevice, r->stream));
     HIP_TRY(hipMemcpyAsync(m.runs, plan.runs.data(), plan.runs.size() * sizeof(PaintRun), hipMemcpyHostToDevice, r->stream));
-    HIP_TRY(launch_morph_load(p, r->stream));
+    if (int e = edit.load(r)) return e;
     HIP_TRY(launch_paint(q, r->stream));
-    p.from = 1; // the board k_paint wrote
-    HIP_TRY(launch_morph_write(p, r->stream));
-    HIP_TRY(hipMemcpyAsync(ctl, p.ctl, sizeof(ctl), hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(hipStreamSynchronize(r->stream)); // (also: the plan's vectors have been read)
+    if (int e = edit.write(r, 1)) return e; // the board k_paint wrote (the wait also: the plan's vectors have been read)
 
-    uint64_t counts[PAINT_CTL_WORDS / 2];
-    memcpy(counts, ctl, sizeof(counts));
-    out->stamp_voxels = counts[PAINT_CTL_STAMP];
-    out->added = counts[MORPH_ADDED];
-    out->removed = counts[MORPH_REMOVED];
-    out->relabelled = counts[MORPH_RELABELLED];
-    for (int c = 0; c < 3; ++c) { out->bbox_min[c] = ctl[MORPH_MIN_X + c]; out->bbox_max[c] = ctl[MORPH_MAX_X + c]; }
-    out->bricks_whole = (int32_t) counts[PAINT_CTL_WHOLE];
-    out->bricks_untouched = (int32_t) counts[PAINT_CTL_UNTOUCHED];
-    out->bricks_evaluated = (int32_t) counts[MORPH_WINDOWS];
+    edit.changes(out);
+    out->stamp_voxels = edit.count(PAINT_CTL_STAMP);
+    out->bricks_whole = (int32_t) edit.count(PAINT_CTL_WHOLE);
+    out->bricks_untouched = (int32_t) edit.count(PAINT_CTL_UNTOUCHED);
+    out->bricks_evaluated = (int32_t) edit.count(MORPH_WINDOWS);
     out->launches = kPaintLaunches;
-    r->paint_counters[1] += (uint64_t) kPaintLaunches;
-    r->paint_counters[2] += counts[MORPH_WINDOWS];
-    r->paint_counters[3] += counts[MORPH_BRICKS_WRITTEN];
-
-    if (d->new_label >= 0) return labels_changed(r, out->bbox_min, out->bbox_max); // (nothing joined or left: nothing to do)
-    return TBRM_OK;
+    return edit.end(r, r->paint_counters, kPaintLaunches, false); // (the call was counted above)
 }
 
 } // extern "C"

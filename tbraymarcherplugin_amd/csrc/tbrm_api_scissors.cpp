@@ -1,15 +1,11 @@
 // tbrm_api_scissors.cpp — view-space scissors (include/tbrm_scissors.h): validation, the mask's staging and the
 // counters around the kernels of tbrm_scissors_kernels.hip, and the two host functions (tbrm_scissors_plan.h).
 //
-// A call is: the mask into the handle's staging and its summary beside it, the source set of the box's bricks from the label bytes
-// into board 0 (k_morph_load, as it stands), k_scissors board 0 -> board 1, the comparison of board 1 with the label bytes inside the
-// box (k_morph_write, as it stands) and behind a write what every label write ends with (labels_changed). The boards,
-// their classes and the control words are the scratch of region growing.
-#include "tbrm_resources.h"
+// Ahead of the frame's load (tbrm_board_edit.h): the mask into the handle's staging and its summary beside it.
+// Between load and write: k_scissors board 0 -> board 1.
+#include "tbrm_board_edit.h"
 #include "tbrm_scissors_kernels.h"
 #include "../../include/tbrm_scissors.h"
-
-#include <cstring>
 
 using namespace tbrm;
 using namespace tbrm_host;
@@ -36,23 +32,8 @@ ScissorsScratch scissors_scratch(char* base, int width, int height)
     return s;
 }
 
-// only ever grown: a call with a mask no larger than one before it allocates nothing
-int ensure_scissors_scratch(tbrm_resources* r, int width, int height)
-{
-    const size_t bytes = scissors_scratch(nullptr, width, height).bytes;
-    if (r->scissors_bytes >= bytes) return TBRM_OK;
-    HIP_TRY(hipStreamSynchronize(r->stream));
-    (void) hipFree(r->d_scissors);
-    r->d_scissors = nullptr;
-    r->scissors_bytes = 0;
-    count_alloc(r, 1, "scissors mask staging");
-    HIP_TRY(hipMalloc((void**) &r->d_scissors, bytes));
-    r->scissors_bytes = bytes;
-    return TBRM_OK;
-}
-
 // what the call checks of a desc and a mask before the handle's state; the box
-int scissors_arguments_of(const tbrm_resources* r, const tbrm_scissors_desc* d, const uint32_t* mask, size_t n_words, MorphParams& p)
+int scissors_arguments_of(const tbrm_resources* r, const tbrm_scissors_desc* d, const uint32_t* mask, size_t n_words, BoardEdit& edit)
 {
     const tbrm_resources::Dims dims = r->data_dims();
     const int dd[3] = {dims[0], dims[1], dims[2]};
@@ -77,31 +58,20 @@ int scissors_arguments_of(const tbrm_resources* r, const tbrm_scissors_desc* d, 
         return fail(TBRM_ERR_INVALID_ARG, "n_words %zu: a mask of width %d and height %d has %zu words", n_words, (int) j.width, (int) j.height, scissors_mask_words(j.width, j.height));
     const int stray = scissors_mask_stray_row(mask, j.width, j.height);
     if (stray >= 0) return fail(TBRM_ERR_INVALID_ARG, "mask_words: row %d has a bit at or beyond width %d", stray, (int) j.width);
-    if (d->new_label < -1 || d->new_label > 255) return fail(TBRM_ERR_INVALID_ARG, "new_label %d: must be 0 .. 255, or -1 to measure only", (int) d->new_label);
-    if (d->erase_label < 0 || d->erase_label > 255) return fail(TBRM_ERR_INVALID_ARG, "erase_label %d: must be 0 .. 255", (int) d->erase_label);
-    if (d->reserved != 0) return fail(TBRM_ERR_INVALID_ARG, "reserved = %d: must be 0", (int) d->reserved);
-    const BoxVerdict v = box_resolve(dims, d->origin, d->extent, true, &p.box, &p.range);
-    if (v.what != BOX_OK) return fail_box(v, true, dims, d->origin, d->extent);
-    for (int c = 0; c < 3; ++c) p.dims[c] = dims[c];
-    return begin_label_edit(r, "no label volume");
+    if (int e = label_codes(d->new_label, d->erase_label, d->reserved)) return e;
+    return edit.begin(r, d->origin, d->extent, &edit.p.range);
 }
 
-// the parameters of the morphology kernels this call borrows (k_morph_load, k_morph_write) and of its own
-void scissors_params(const tbrm_resources* r, const tbrm_scissors_desc* d, const GrowScratch& g, const ScissorsScratch& m, MorphParams& p, ScissorsParams& q)
+// the staging, the frame's bind and the parameters of the call's own kernels
+int scissors_params(tbrm_resources* r, const tbrm_scissors_desc* d, BoardEdit& edit, ScissorsScratch& m, ScissorsParams& q)
 {
-    p.labels = r->d_labels;
-    p.bnx = r->dbn[0];
-    p.bnxy = r->dbn[0] * r->dbn[1];
-    p.wrange = p.range; // no reach: the bricks of the box
-    for (int w = 0; w < 8; ++w) { p.source[w] = d->source[w]; p.writable[w] = d->writable[w]; }
-    p.bits = g.bits;
-    p.cls[0] = g.act[0];
-    p.cls[1] = g.act[1];
-    p.new_label = d->new_label;
-    p.erase_label = d->erase_label;
-    p.ctl = g.ctl;
-
+    MorphParams& p = edit.p;
     const tbrm_scissors_projection& j = d->projection;
+    if (int e = edit.bind(r, d)) return e;
+    p.wrange = p.range; // no reach: the bricks of the box
+    if (int e = ensure_bytes(r, r->d_scissors, r->scissors_bytes, scissors_scratch(nullptr, j.width, j.height).bytes, "scissors mask staging")) return e;
+    m = scissors_scratch(r->d_scissors, j.width, j.height);
+
     q.bnx = p.bnx;
     q.bnxy = p.bnxy;
     q.range = p.range;
@@ -118,10 +88,11 @@ void scissors_params(const tbrm_resources* r, const tbrm_scissors_desc* d, const
     q.summary = q.skip ? m.summary : nullptr;
     q.cells_x = scissors_cells_x(j.width);
     q.cells_y = scissors_cells_y(j.height);
-    q.bits = g.bits;
-    q.cls[0] = g.act[0];
-    q.cls[1] = g.act[1];
-    q.ctl = g.ctl;
+    q.bits = p.bits;
+    q.cls[0] = p.cls[0];
+    q.cls[1] = p.cls[1];
+    q.ctl = p.ctl;
+    return TBRM_OK;
 }
 
 } // namespace
@@ -157,62 +128,35 @@ int tbrm_host_scissors_polygon(const double* xy, size_t n_points, int32_t width,
     return TBRM_OK;
 }
 
-int tbrm_scissors_counters(const tbrm_resources* r, uint64_t out[4])
-{
-    if (!r || !out) return fail(TBRM_ERR_INVALID_ARG, "null argument");
-    for (int k = 0; k < 4; ++k) out[k] = r->scissors_counters[k];
-    return TBRM_OK;
-}
+int tbrm_scissors_counters(const tbrm_resources* r, uint64_t out[4]) { return copy_counters(r, &tbrm_resources::scissors_counters, out); }
 
 int tbrm_scissors_labels(tbrm_resources* r, const tbrm_scissors_desc* d, const uint32_t* mask_words, size_t n_words, tbrm_scissors_result* out)
 {
     if (!r || !d || !mask_words || !out) return fail(TBRM_ERR_INVALID_ARG, "null argument");
     if (int e = refuse_resident(r)) return e;
-    MorphParams p{};
+    BoardEdit edit(SCISSORS_CTL_WORDS);
     ScissorsParams q{};
-    if (int e = scissors_arguments_of(r, d, mask_words, n_words, p)) return e;
-    if (int e = ensure_grow_scratch(r)) return e;
-    const tbrm_scissors_projection& j = d->projection;
-    if (int e = ensure_scissors_scratch(r, j.width, j.height)) return e;
-    const ScissorsScratch m = scissors_scratch(r->d_scissors, j.width, j.height);
-    scissors_params(r, d, grow_scratch(r), m, p, q);
+    ScissorsScratch m;
+    if (int e = scissors_arguments_of(r, d, mask_words, n_words, edit)) return e;
+    if (int e = scissors_params(r, d, edit, m, q)) return e;
 
-    int32_t ctl[SCISSORS_CTL_WORDS];
-    ctl_start(ctl, SCISSORS_CTL_WORDS, MORPH_MIN_X, p.dims);
-    HIP_TRY(hipMemcpyAsync(p.ctl, ctl, sizeof(ctl), hipMemcpyHostToDevice, r->stream));
     HIP_TRY(hipMemcpyAsync(m.mask, mask_words, n_words * sizeof(uint32_t), hipMemcpyHostToDevice, r->stream));
     int launches = 1;
     if (q.skip) {
         HIP_TRY(launch_scissors_summary(q, r->stream));
         launches += kScissorsSummaryLaunches;
     }
-    HIP_TRY(launch_morph_load(p, r->stream));
+    if (int e = edit.load(r)) return e;
     HIP_TRY(launch_scissors(q, r->stream));
-    p.from = 1; // the board k_scissors wrote
-    HIP_TRY(launch_morph_write(p, r->stream));
-    HIP_TRY(hipMemcpyAsync(ctl, p.ctl, sizeof(ctl), hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(hipStreamSynchronize(r->stream)); // (also: the caller's mask has been read)
+    if (int e = edit.write(r, 1)) return e; // the board k_scissors wrote (the wait also: the caller's mask has been read)
 
-    uint64_t counts[SCISSORS_CTL_WORDS / 2];
-    memcpy(counts, ctl, sizeof(counts));
     memset(out, 0, sizeof(*out));
-    out->source_voxels = counts[MORPH_SOURCE];
-    out->result_voxels = counts[MORPH_RESULT];
-    out->added = counts[MORPH_ADDED];
-    out->removed = counts[MORPH_REMOVED];
-    out->relabelled = counts[MORPH_RELABELLED];
-    for (int c = 0; c < 3; ++c) { out->bbox_min[c] = ctl[MORPH_MIN_X + c]; out->bbox_max[c] = ctl[MORPH_MAX_X + c]; }
-    out->bricks_inside = (int32_t) counts[SCISSORS_CTL_INSIDE];
-    out->bricks_outside = (int32_t) counts[SCISSORS_CTL_OUTSIDE];
-    out->bricks_projected = (int32_t) counts[MORPH_WINDOWS];
+    edit.result(out);
+    out->bricks_inside = (int32_t) edit.count(SCISSORS_CTL_INSIDE);
+    out->bricks_outside = (int32_t) edit.count(SCISSORS_CTL_OUTSIDE);
+    out->bricks_projected = (int32_t) edit.count(MORPH_WINDOWS);
     out->launches = launches;
-    ++r->scissors_counters[0];
-    r->scissors_counters[1] += (uint64_t) launches;
-    r->scissors_counters[2] += counts[MORPH_WINDOWS];
-    r->scissors_counters[3] += counts[MORPH_BRICKS_WRITTEN];
-
-    if (d->new_label >= 0) return labels_changed(r, out->bbox_min, out->bbox_max); // (nothing joined or left: nothing to do)
-    return TBRM_OK;
+    return edit.end(r, r->scissors_counters, launches);
 }
 
 } // extern "C"

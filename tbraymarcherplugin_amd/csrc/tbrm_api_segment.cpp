@@ -90,12 +90,7 @@ int tbrm_host_hit_voxel(const int32_t dims[3], const tbrm_hit* hit, int32_t out_
     return TBRM_OK;
 }
 
-int tbrm_segment_counters(const tbrm_resources* r, uint64_t out[4])
-{
-    if (!r || !out) return fail(TBRM_ERR_INVALID_ARG, "null argument");
-    for (int k = 0; k < 4; ++k) out[k] = r->grow_counters[k];
-    return TBRM_OK;
-}
+int tbrm_segment_counters(const tbrm_resources* r, uint64_t out[4]) { return copy_counters(r, &tbrm_resources::grow_counters, out); }
 
 int tbrm_attach_empty_label_volume(tbrm_resources* r)
 {
@@ -132,15 +127,7 @@ int tbrm_grow_region(tbrm_resources* r, const tbrm_grow_desc* d, const int32_t* 
     for (int c = 0; c < 3; ++c) box_voxels *= (uint64_t) (p.box.end[c] - p.box.origin[c]);
     const bool is_float = r->desc.data_format == TBRM_FMT_R32_FLOAT;
     const double top = r->desc.data_format == TBRM_FMT_G8 ? 255.0 : 65535.0;
-    if (!(d->lo <= d->hi)) return fail(TBRM_ERR_INVALID_ARG, "range [%g, %g]: needs lo <= hi", d->lo, d->hi);
-    if (is_float) {
-        if (!std::isfinite(d->lo) || !std::isfinite(d->hi) || !std::isfinite((float) d->lo) || !std::isfinite((float) d->hi))
-            return fail(TBRM_ERR_INVALID_ARG, "range [%g, %g]: both must be finite as float32", d->lo, d->hi);
-    } else {
-        const double least = d->relative_to_seed ? -top : 0.0;
-        if (!(d->lo >= least && d->hi <= top) || d->lo != std::floor(d->lo) || d->hi != std::floor(d->hi))
-            return fail(TBRM_ERR_INVALID_ARG, "range [%g, %g]: needs integral codes with %g <= lo <= hi <= %g", d->lo, d->hi, least, top);
-    }
+    if (int e = fail_value_range(r, d->lo, d->hi, d->relative_to_seed != 0)) return e;
     const bool writes = d->new_label >= 0;
     if (int e = begin_label_edit(r, writes ? "no label volume to write to" : nullptr)) return e;
     if (int e = ensure_grow_scratch(r)) return e;
@@ -170,7 +157,7 @@ int tbrm_grow_region(tbrm_resources* r, const tbrm_grow_desc* d, const int32_t* 
     const GrowScratch g = grow_scratch(r);
     p.data = r->d_data;
     p.labels = r->d_labels;
-    p.fmt = r->desc.data_format == TBRM_FMT_G8 ? FMT_U8 : (r->desc.data_format == TBRM_FMT_G16 ? FMT_U16 : FMT_F32);
+    p.fmt = data_fmt(r);
     p.bnx = r->dbn[0];
     p.bnxy = r->dbn[0] * r->dbn[1];
     for (int w = 0; w < 8; ++w) p.writable[w] = d->writable[w];

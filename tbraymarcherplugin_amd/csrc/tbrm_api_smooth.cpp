@@ -1,16 +1,12 @@
 // tbrm_api_smooth.cpp — smoothing of labels (include/tbrm_smooth.h): validation, the plan (tbrm_smooth_plan.h) and
 // the counters around the kernel of tbrm_smooth_kernels.hip.
 //
-// A call is: the source set of the planned bricks from the label bytes into board 0 (k_morph_load, as it stands), `iterations` passes
-// board -> board (k_smooth_count), the comparison of the final board with the label bytes inside the box (k_morph_write, as it
-// stands) and behind a write what every label write ends with (labels_changed). The boards, their classes and the
-// control words are the scratch of region growing; a call takes no other.
-#include "tbrm_resources.h"
+// Between the frame's load and write (tbrm_board_edit.h): `iterations` passes board -> board (k_smooth_count). A call
+// takes no scratch beyond region growing's.
+#include "tbrm_board_edit.h"
 #include "tbrm_smooth_kernels.h"
 #include "tbrm_smooth_plan.h"
 #include "../../include/tbrm_smooth.h"
-
-#include <cstring>
 
 using namespace tbrm;
 using namespace tbrm_host;
@@ -22,7 +18,7 @@ static_assert(kSmoothMaxRadius <= kRowWordShift, "a row word holds 16 bits eithe
 namespace {
 
 // what the call checks of a desc before the handle's state; the box and the plan
-int smooth_arguments_of(const tbrm_resources* r, const tbrm_smooth_desc* d, MorphParams& p, SmoothPlan& plan)
+int smooth_arguments_of(const tbrm_resources* r, const tbrm_smooth_desc* d, BoardEdit& edit, SmoothPlan& plan)
 {
     int axis = 0;
     switch (smooth_arguments(d->radius, d->rank_num, d->rank_den, d->iterations, &axis)) {
@@ -34,32 +30,19 @@ int smooth_arguments_of(const tbrm_resources* r, const tbrm_smooth_desc* d, Morp
     case SMOOTH_RANK_DEN: return fail(TBRM_ERR_INVALID_ARG, "rank_den %d: must be 1 .. %d", (int) d->rank_den, TBRM_SMOOTH_MAX_RANK_DEN);
     case SMOOTH_RANK_NUM: return fail(TBRM_ERR_INVALID_ARG, "rank_num %d: must be 0 .. rank_den - 1 = %d", (int) d->rank_num, (int) d->rank_den - 1);
     }
-    if (d->new_label < -1 || d->new_label > 255) return fail(TBRM_ERR_INVALID_ARG, "new_label %d: must be 0 .. 255, or -1 to measure only", (int) d->new_label);
-    if (d->erase_label < 0 || d->erase_label > 255) return fail(TBRM_ERR_INVALID_ARG, "erase_label %d: must be 0 .. 255", (int) d->erase_label);
-    if (d->reserved != 0) return fail(TBRM_ERR_INVALID_ARG, "reserved = %d: must be 0", (int) d->reserved);
-    const tbrm_resources::Dims dims = r->data_dims();
-    const BoxVerdict v = box_resolve(dims, d->origin, d->extent, true, &p.box, nullptr);
-    if (v.what != BOX_OK) return fail_box(v, true, dims, d->origin, d->extent);
-    for (int c = 0; c < 3; ++c) p.dims[c] = dims[c];
-    if (int e = begin_label_edit(r, "no label volume")) return e;
+    if (int e = label_codes(d->new_label, d->erase_label, d->reserved)) return e;
+    if (int e = edit.begin(r, d->origin, d->extent)) return e;
+    const MorphParams& p = edit.p;
     if (!smooth_plan(p.dims, p.box.origin, p.box.end, d->radius, d->iterations, &plan)) return fail(TBRM_ERR_INVALID_ARG, "no plan for these arguments");
     return TBRM_OK;
 }
 
-// the parameters of the morphology kernels this call borrows (k_morph_load, k_morph_write) and of its own
-void smooth_params(const tbrm_resources* r, const tbrm_smooth_desc* d, const SmoothPlan& plan, const GrowScratch& g, MorphParams& p, SmoothParams& q)
+// the frame's bind, the plan's ranges and the parameters of the call's own kernel
+int smooth_params(tbrm_resources* r, const tbrm_smooth_desc* d, const SmoothPlan& plan, BoardEdit& edit, SmoothParams& q)
 {
-    p.labels = r->d_labels;
-    p.bnx = r->dbn[0];
-    p.bnxy = r->dbn[0] * r->dbn[1];
-    for (int c = 0; c < 3; ++c) { p.range.b0[c] = plan.b0[c]; p.range.nb[c] = plan.nb[c]; p.wrange.b0[c] = plan.wb0[c]; p.wrange.nb[c] = plan.wnb[c]; }
-    for (int w = 0; w < 8; ++w) { p.source[w] = d->source[w]; p.writable[w] = d->writable[w]; }
-    p.bits = g.bits;
-    p.cls[0] = g.act[0];
-    p.cls[1] = g.act[1];
-    p.new_label = d->new_label;
-    p.erase_label = d->erase_label;
-    p.ctl = g.ctl;
+    MorphParams& p = edit.p;
+    if (int e = edit.bind(r, d)) return e;
+    edit.ranges(plan);
 
     q.bnx = p.bnx;
     q.bnxy = p.bnxy;
@@ -71,11 +54,12 @@ void smooth_params(const tbrm_resources* r, const tbrm_smooth_desc* d, const Smo
     }
     q.rank_num = (uint32_t) d->rank_num;
     q.rank_den = (uint32_t) d->rank_den;
-    q.bits = g.bits;
-    q.cls[0] = g.act[0];
-    q.cls[1] = g.act[1];
+    q.bits = p.bits;
+    q.cls[0] = p.cls[0];
+    q.cls[1] = p.cls[1];
     q.skip = tune(TUNE_SMOOTH_SKIP) != 0;
-    q.ctl = g.ctl;
+    q.ctl = p.ctl;
+    return TBRM_OK;
 }
 
 } // namespace
@@ -93,54 +77,30 @@ int tbrm_host_smooth_radii(const double spacing[3], double radius, int32_t radii
     return TBRM_OK;
 }
 
-int tbrm_smooth_counters(const tbrm_resources* r, uint64_t out[4])
-{
-    if (!r || !out) return fail(TBRM_ERR_INVALID_ARG, "null argument");
-    for (int k = 0; k < 4; ++k) out[k] = r->smooth_counters[k];
-    return TBRM_OK;
-}
+int tbrm_smooth_counters(const tbrm_resources* r, uint64_t out[4]) { return copy_counters(r, &tbrm_resources::smooth_counters, out); }
 
 int tbrm_smooth_labels(tbrm_resources* r, const tbrm_smooth_desc* d, tbrm_smooth_result* out)
 {
     if (!r || !d || !out) return fail(TBRM_ERR_INVALID_ARG, "null argument");
     if (int e = refuse_resident(r)) return e;
-    MorphParams p{};
+    BoardEdit edit(MORPH_CTL_WORDS);
     SmoothParams q{};
     SmoothPlan plan;
-    if (int e = smooth_arguments_of(r, d, p, plan)) return e;
-    if (int e = ensure_grow_scratch(r)) return e;
-    smooth_params(r, d, plan, grow_scratch(r), p, q);
+    if (int e = smooth_arguments_of(r, d, edit, plan)) return e;
+    if (int e = smooth_params(r, d, plan, edit, q)) return e;
 
-    int32_t ctl[MORPH_CTL_WORDS];
-    ctl_start(ctl, MORPH_CTL_WORDS, MORPH_MIN_X, p.dims);
-    HIP_TRY(hipMemcpyAsync(p.ctl, ctl, sizeof(ctl), hipMemcpyHostToDevice, r->stream));
-    HIP_TRY(launch_morph_load(p, r->stream));
+    if (int e = edit.load(r)) return e;
     for (int i = 0; i < plan.passes; ++i) {
         q.from = i & 1;
         HIP_TRY(launch_smooth_count(q, r->stream));
     }
-    p.from = plan.passes & 1; // the board the last pass wrote
-    HIP_TRY(launch_morph_write(p, r->stream));
-    HIP_TRY(hipMemcpyAsync(ctl, p.ctl, sizeof(ctl), hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(hipStreamSynchronize(r->stream));
+    if (int e = edit.write(r, plan.passes & 1)) return e; // the board the last pass wrote
 
-    uint64_t counts[MORPH_CTL_COUNTS];
-    memcpy(counts, ctl, sizeof(counts));
     memset(out, 0, sizeof(*out));
-    out->source_voxels = counts[MORPH_SOURCE];
-    out->result_voxels = counts[MORPH_RESULT];
-    out->added = counts[MORPH_ADDED];
-    out->removed = counts[MORPH_REMOVED];
-    out->relabelled = counts[MORPH_RELABELLED];
-    for (int c = 0; c < 3; ++c) { out->bbox_min[c] = ctl[MORPH_MIN_X + c]; out->bbox_max[c] = ctl[MORPH_MAX_X + c]; out->reach[c] = plan.reach[c]; }
+    edit.result(out);
+    for (int c = 0; c < 3; ++c) out->reach[c] = plan.reach[c];
     out->launches = plan.passes * kSmoothLaunchesPerPass;
-    ++r->smooth_counters[0];
-    r->smooth_counters[1] += (uint64_t) out->launches;
-    r->smooth_counters[2] += counts[MORPH_WINDOWS];
-    r->smooth_counters[3] += counts[MORPH_BRICKS_WRITTEN];
-
-    if (d->new_label >= 0) return labels_changed(r, out->bbox_min, out->bbox_max); // (nothing joined or left: nothing to do)
-    return TBRM_OK;
+    return edit.end(r, r->smooth_counters, out->launches);
 }
 
 } // extern "C"

@@ -56,13 +56,7 @@ SurfaceScratch surface_scratch(char* base, size_t n_blocks)
 int ensure_surface_buffer(tbrm_resources* r, int which, size_t bytes)
 {
     if (r->surface_bytes[which] >= bytes) return TBRM_OK;
-    HIP_TRY(hipStreamSynchronize(r->stream));
-    (void) hipFree(r->d_surface[which]);
-    r->d_surface[which] = nullptr;
-    r->surface_bytes[which] = 0;
-    count_alloc(r, 1, which ? "surface staging" : "surface scratch");
-    HIP_TRY(hipMalloc((void**) &r->d_surface[which], bytes));
-    r->surface_bytes[which] = bytes;
+    if (int e = ensure_bytes(r, r->d_surface[which], r->surface_bytes[which], bytes, which ? "surface staging" : "surface scratch")) return e;
     ++r->surface_counters[5];
     return TBRM_OK;
 }

@@ -145,12 +145,7 @@ int tbrm_download_volume_region(tbrm_resources* r, const int32_t origin[3], cons
     return TBRM_OK;
 }
 
-int tbrm_volume_region_counters(const tbrm_resources* r, uint64_t out[4])
-{
-    if (!r || !out) return fail(TBRM_ERR_INVALID_ARG, "null argument");
-    for (int k = 0; k < 4; ++k) out[k] = r->region_counters[k];
-    return TBRM_OK;
-}
+int tbrm_volume_region_counters(const tbrm_resources* r, uint64_t out[4]) { return copy_counters(r, &tbrm_resources::region_counters, out); }
 
 int tbrm_volume_skipping_digest(tbrm_resources* r, uint64_t out[4])
 {

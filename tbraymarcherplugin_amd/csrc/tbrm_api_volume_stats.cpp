@@ -36,7 +36,7 @@ int stats_box(const tbrm_resources* r, const int32_t* origin, const int32_t* ext
     const BoxVerdict v = box_resolve(dims, origin, extent, true, &p.box, &p.range);
     if (v.what != BOX_OK) return fail_box(v, true, dims, origin, extent);
     p.data = r->d_data;
-    p.fmt = r->desc.data_format == TBRM_FMT_G8 ? FMT_U8 : (r->desc.data_format == TBRM_FMT_G16 ? FMT_U16 : FMT_F32);
+    p.fmt = data_fmt(r);
     p.bnx = r->dbn[0];
     p.bnxy = r->dbn[0] * r->dbn[1];
     return TBRM_OK;
@@ -231,11 +231,6 @@ int tbrm_host_window_from_histogram(const uint64_t* counts, int32_t n_bins, doub
     return TBRM_OK;
 }
 
-int tbrm_volume_stats_counters(const tbrm_resources* r, uint64_t out[4])
-{
-    if (!r || !out) return fail(TBRM_ERR_INVALID_ARG, "null argument");
-    for (int k = 0; k < 4; ++k) out[k] = r->stats_counters[k];
-    return TBRM_OK;
-}
+int tbrm_volume_stats_counters(const tbrm_resources* r, uint64_t out[4]) { return copy_counters(r, &tbrm_resources::stats_counters, out); }
 
 } // extern "C"

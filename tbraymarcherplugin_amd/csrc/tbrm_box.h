@@ -1,8 +1,10 @@
-// tbrm_box.h — the box of a call against the volume, and the bricks a box touches, stated once: no device, no
-// handle, nothing but integers. Every entry point that takes an origin and an extent resolves them here;
+// tbrm_box.h — the box of a call against the volume, the bricks a box touches and a call's range of stored values,
+// stated once: no device, no handle, plain arithmetic. Every entry point that takes an origin and an extent resolves them here;
 // tests/cpp/brick_boards_test.cpp runs it on its own under the sanitizers.
 #pragma once
 #include <limits.h>
+
+#include <cmath>
 
 #include "tbrm_brick_boards.h"
 
@@ -51,6 +53,16 @@ inline void bbox_bricks(const int32_t mn[3], const int32_t mx[3], int b0[3], int
         b0[c] = mn[c] >> kBrickShift;
         b1[c] = (mx[c] >> kBrickShift) + 1;
     }
+}
+
+// A range lo .. hi of stored values as a call gives it: lo <= hi (a NaN fails); of float32 data both finite as float32; of UNORM data
+// integral codes within least .. top (tbrm_grow_region's relative_to_seed takes offsets: least = -top).
+enum RangeRefusal : int { RANGE_OK = 0, RANGE_ORDER, RANGE_FLOAT, RANGE_CODES };
+inline int value_range_refusal(double lo, double hi, bool is_float, double least, double top)
+{
+    if (!(lo <= hi)) return RANGE_ORDER;
+    if (is_float) return std::isfinite(lo) && std::isfinite(hi) && std::isfinite((float) lo) && std::isfinite((float) hi) ? RANGE_OK : RANGE_FLOAT;
+    return lo >= least && hi <= top && lo == std::floor(lo) && hi == std::floor(hi) ? RANGE_OK : RANGE_CODES;
 }
 
 } // namespace tbrm

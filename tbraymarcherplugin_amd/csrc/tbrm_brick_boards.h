@@ -23,6 +23,10 @@ namespace tbrm {
 constexpr int kBrick = 8;      // empty-space-skipping brick edge in voxels
 constexpr int kBrickShift = 3;
 
+enum : int { FMT_U8 = 0, FMT_U16 = 1, FMT_F32 = 2 };                    // the stored values of a volume
+enum : uint32_t { MORPH_EMPTY = 0, MORPH_FULL = 1, MORPH_MIXED = 2 }; // the class of a board: no bit, every in-volume bit, neither
+TBRM_BOARDS_HD uint32_t board_class(bool any, bool all) { return !any ? MORPH_EMPTY : (all ? MORPH_FULL : MORPH_MIXED); }
+
 struct BrickRange { int b0[3], nb[3]; };      // the bricks nb[c] from b0[c] on, on the volume's brick grid; position k runs x fastest
 struct VoxelBox { int origin[3], end[3]; };   // the voxels [origin, end)
 
@@ -137,6 +141,62 @@ template <int CONN26> TBRM_BOARDS_HD uint64_t slice_spread(uint64_t w)
 }
 
 #if defined(__HIPCC__)
+// ---- device only: a wave per brick ---------------------------------------------------------------------------------------------------
+// The prologue of a kernel that gives every brick of a range a wave, THREADS / 64 bricks to a workgroup: the brick's position k in the
+// range, its coordinates, its index b on the volume's grid and the lane's x row (y, z); false for a wave beyond the range.
+struct WaveBrick { uint32_t k; int bx, by, bz; size_t b; int y, z; };
+template <int THREADS> __device__ __forceinline__ bool wave_brick(const BrickRange& r, int bnx, int bnxy, WaveBrick& w)
+{
+    const int lane = threadIdx.x & 63;
+    w.k = blockIdx.x * (THREADS / 64) + (uint32_t) (threadIdx.x >> 6);
+    if (w.k >= (uint32_t) range_bricks(r)) return false;
+    range_brick(r, w.k, w.bx, w.by, w.bz);
+    w.b = grid_index(bnx, bnxy, w.bx, w.by, w.bz);
+    w.y = w.by * kBrick + (lane & 7);
+    w.z = w.bz * kBrick + (lane >> 3);
+    return true;
+}
+
+// a wave's result row (this lane's byte of the brick's board, `vol` its in-volume bits) and, from the whole wave, the board's class
+__device__ __forceinline__ void store_board_row(uint64_t* board, uint32_t* cls, int lane, uint32_t row, uint32_t vol)
+{
+    reinterpret_cast<uint8_t*>(board)[lane] = (uint8_t) row;
+    const bool any = __ballot(row != 0u) != 0ull, all = __ballot(row != vol) == 0ull;
+    if (lane == 0) *cls = board_class(any, all);
+}
+
+// ---- device only: the stored values of a row and the gate ----------------------------------------------------------------------------
+// the 8 values from element `first` of the bricked volume on (a row of a brick): codes in c (G8, G16) or floats in f (R32F)
+template <int FMT> __device__ __forceinline__ void row_values(const void* data, size_t first, uint32_t c[8], float f[8])
+{
+    if constexpr (FMT == FMT_U8) {
+        const uint2 v = *reinterpret_cast<const uint2*>((const uint8_t*) data + first);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) c[i] = byte_of(v, i);
+    } else if constexpr (FMT == FMT_U16) {
+        const uint4 v = *reinterpret_cast<const uint4*>((const uint16_t*) data + first);
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) c[i] = (w[i >> 1] >> (16 * (i & 1))) & 65535u;
+    } else {
+        const float4 a = *reinterpret_cast<const float4*>((const float*) data + first);
+        const float4 b = *reinterpret_cast<const float4*>((const float*) data + first + 4);
+        f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
+    }
+}
+
+// bit i: value i of the row lies in lo .. hi (a NaN fails both comparisons)
+template <int FMT> __device__ __forceinline__ uint32_t row_gate(const uint32_t c[8], const float f[8], uint32_t lo_code, uint32_t hi_code, float lo_f, float hi_f)
+{
+    uint32_t gate = 0u;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        if constexpr (FMT == FMT_F32) gate |= (uint32_t) (f[i] >= lo_f && f[i] <= hi_f) << i;
+        else gate |= (uint32_t) (c[i] >= lo_code && c[i] <= hi_code) << i;
+    }
+    return gate;
+}
+
 // ---- device only: reductions over the wave -------------------------------------------------------------------------------------------
 template <typename T> __device__ __forceinline__ T wave_sum(T v)
 {

@@ -34,29 +34,11 @@ constexpr int kCompeteMaxSteps = 520;
 
 namespace {
 
-template <int FMT> __device__ __forceinline__ void row_values(const CompeteParams& p, size_t first, uint32_t c[8], float f[8])
-{
-    if constexpr (FMT == FMT_U8) {
-        const uint2 v = *reinterpret_cast<const uint2*>((const uint8_t*) p.data + first);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) c[i] = byte_of(v, i);
-    } else if constexpr (FMT == FMT_U16) {
-        const uint4 v = *reinterpret_cast<const uint4*>((const uint16_t*) p.data + first);
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int i = 0; i < 8; ++i) c[i] = (w[i >> 1] >> (16 * (i & 1))) & 65535u;
-    } else {
-        const float4 a = *reinterpret_cast<const float4*>((const float*) p.data + first);
-        const float4 b = *reinterpret_cast<const float4*>((const float*) p.data + first + 4);
-        f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-    }
-}
-
 // the codes of the 8 voxels from `first` on (a row of a brick)
 template <int FMT> __device__ __forceinline__ void row_codes(const CompeteParams& p, size_t first, uint32_t c[8])
 {
     float f[8];
-    row_values<FMT>(p, first, c, f);
+    row_values<FMT>(p.data, first, c, f);
     if constexpr (FMT == FMT_F32) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) c[i] = compete_float_code(f[i], p.float_origin, p.float_scale); // (__fsub_rn, __fmul_rn: no FMA)
@@ -109,24 +91,21 @@ __global__ __launch_bounds__(kCompeteThreads) void k_compete_init(const CompeteP
     const int tid = threadIdx.x, lane = tid & 63;
     if (tid < 8) { s_seeds[tid] = p.seeds[tid]; s_writable[tid] = p.writable[tid]; }
     __syncthreads();
-    const uint32_t total = (uint32_t) range_bricks(p.range);
-    const uint32_t k = blockIdx.x * (kCompeteThreads / 64) + (uint32_t) (tid >> 6);
-    if (k >= total) return;
-    int bx, by, bz;
-    range_brick(p.range, k, bx, by, bz);
-    const size_t first = grid_index(p.bnx, p.bnxy, bx, by, bz) * 512 + (size_t) lane * 8;
+    WaveBrick w;
+    if (!wave_brick<kCompeteThreads>(p.range, p.bnx, p.bnxy, w)) return;
+    const uint32_t k = w.k;
+    const int bx = w.bx, by = w.by, bz = w.bz;
+    const size_t first = w.b * 512 + (size_t) lane * 8;
 
-    const uint32_t inside = row_in_box(p.box, bx, by * kBrick + (lane & 7), bz * kBrick + (lane >> 3));
+    const uint32_t inside = row_in_box(p.box, bx, w.y, w.z);
     uint32_t c[8];
     float f[8];
-    row_values<FMT>(p, first, c, f);
-    uint32_t gate = 0u, nan = 0u;
+    row_values<FMT>(p.data, first, c, f);
+    const uint32_t gate = row_gate<FMT>(c, f, p.lo_code, p.hi_code, p.lo_f, p.hi_f);
+    uint32_t nan = 0u;
+    if constexpr (FMT == FMT_F32) {
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        if constexpr (FMT == FMT_F32) {
-            gate |= (uint32_t) (f[i] >= p.lo_f && f[i] <= p.hi_f) << i; // (a NaN fails both)
-            nan |= (uint32_t) (f[i] != f[i]) << i;
-        } else gate |= (uint32_t) (c[i] >= p.lo_code && c[i] <= p.hi_code) << i;
+        for (int i = 0; i < 8; ++i) nan |= (uint32_t) (f[i] != f[i]) << i;
     }
     const uint2 l = *reinterpret_cast<const uint2*>(p.labels + first);
     const uint32_t seed = row_in_mask(l, s_seeds) & inside;
@@ -333,13 +312,11 @@ __global__ __launch_bounds__(kCompeteThreads) void k_compete_write(const Compete
     const int tid = threadIdx.x, lane = tid & 63;
     if (tid < 8) s_seeds[tid] = p.seeds[tid];
     __syncthreads();
-    const uint32_t total = (uint32_t) range_bricks(p.range);
-    const uint32_t k = blockIdx.x * (kCompeteThreads / 64) + (uint32_t) (tid >> 6);
-    if (k >= total) return;
-    int bx, by, bz;
-    range_brick(p.range, k, bx, by, bz);
-    const size_t first = grid_index(p.bnx, p.bnxy, bx, by, bz) * 512 + (size_t) lane * 8;
-    const int y = by * kBrick + (lane & 7), z = bz * kBrick + (lane >> 3);
+    WaveBrick w;
+    if (!wave_brick<kCompeteThreads>(p.range, p.bnx, p.bnxy, w)) return;
+    const uint32_t k = w.k;
+    const int bx = w.bx, y = w.y, z = w.z;
+    const size_t first = w.b * 512 + (size_t) lane * 8;
 
     uint32_t key[8];
     {

@@ -10,7 +10,6 @@
 
 namespace tbrm {
 
-enum : int { FMT_U8 = 0, FMT_U16 = 1, FMT_F32 = 2 };
 enum : int { ADDR_WRAP = 0, ADDR_CLAMP = 1, ADDR_BORDER = 2 };
 
 // what a propagation pass does with its light stream(s): Add (one light, stream a), Change (a added, r removed,
@@ -602,7 +601,6 @@ hipError_t launch_grow_write(const GrowParams& p, const BrickRange& w, hipStream
 
 // label morphology (tbrm_api_morph.cpp, tbrm_morph_kernels.hip; include/tbrm_morphology.h). It works in the scratch of region growing:
 // the 16 words of a brick are two boards of 8 slice words (bit y * 8 + x of word z), the two activity words are the boards' classes.
-enum : uint32_t { MORPH_EMPTY = 0, MORPH_FULL = 1, MORPH_MIXED = 2 }; // of a board: no bit, every in-volume bit, neither
 // the control words of a call (MorphParams::ctl), inside the GROW_CTL_WORDS words of the scratch: 64-bit counts, then the 32-bit box
 enum MorphCtl : int {
     MORPH_SOURCE, MORPH_RESULT, MORPH_ADDED, MORPH_REMOVED, MORPH_RELABELLED, MORPH_WINDOWS, MORPH_BRICKS_WRITTEN, MORPH_CTL_COUNTS, // uint64 each

@@ -249,7 +249,7 @@ __global__ __launch_bounds__(kMarginThreads) void k_margin_z(const MarginParams 
     }
     if constexpr (!MAP) {
         const bool some = __syncthreads_or(any) != 0, every = __syncthreads_and(all) != 0;
-        if (tid == 0) p.cls[1 - p.from][b] = !some ? MORPH_EMPTY : (every ? MORPH_FULL : MORPH_MIXED);
+        if (tid == 0) p.cls[1 - p.from][b] = board_class(some, every);
     }
 }
 

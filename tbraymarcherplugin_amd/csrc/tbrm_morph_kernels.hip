@@ -42,8 +42,6 @@ constexpr int kStepThreads = TBRM_MORPH_STEP_THREADS;
 constexpr int kStepRows = kWinRows / kStepThreads; // rows to a thread
 static_assert(kStepThreads % 64 == 0 && kStepRows * kStepThreads == kWinRows, "whole waves, whole rows");
 
-__device__ __forceinline__ uint32_t board_class(bool any, bool all) { return !any ? MORPH_EMPTY : (all ? MORPH_FULL : MORPH_MIXED); }
-
 } // namespace
 
 // ---- the source set ---------------------------------------------------------------------------------------------------------------
@@ -55,18 +53,11 @@ __global__ __launch_bounds__(kMorphWaveThreads) void k_morph_load(const MorphPar
     const int tid = threadIdx.x, lane = tid & 63;
     if (tid < 8) s_source[tid] = p.source[tid];
     __syncthreads();
-    const uint32_t total = (uint32_t) range_bricks(p.range);
-    const uint32_t k = blockIdx.x * (kMorphWaveThreads / 64) + (uint32_t) (tid >> 6);
-    if (k >= total) return;
-    int bx, by, bz;
-    range_brick(p.range, k, bx, by, bz);
-    const size_t b = grid_index(p.bnx, p.bnxy, bx, by, bz);
-    const uint32_t vol = row_in_volume(p.dims, bx, by * kBrick + (lane & 7), bz * kBrick + (lane >> 3));
-    const uint2 l = *reinterpret_cast<const uint2*>(p.labels + b * 512 + (size_t) lane * 8);
-    const uint32_t set = row_in_mask(l, s_source) & vol;
-    reinterpret_cast<uint8_t*>(p.bits + b * 16)[lane] = (uint8_t) set;
-    const bool any = __ballot(set != 0u) != 0ull, all = __ballot(set != vol) == 0ull;
-    if (lane == 0) p.cls[0][b] = board_class(any, all);
+    WaveBrick w;
+    if (!wave_brick<kMorphWaveThreads>(p.range, p.bnx, p.bnxy, w)) return;
+    const uint32_t vol = row_in_volume(p.dims, w.bx, w.y, w.z);
+    const uint2 l = *reinterpret_cast<const uint2*>(p.labels + w.b * 512 + (size_t) lane * 8);
+    store_board_row(p.bits + w.b * 16, &p.cls[0][w.b], lane, row_in_mask(l, s_source) & vol, vol);
 }
 
 hipError_t launch_morph_load(const MorphParams& p, hipStream_t s)
@@ -220,13 +211,10 @@ __global__ __launch_bounds__(kMorphWaveThreads) void k_morph_write(const MorphPa
     const int tid = threadIdx.x, lane = tid & 63;
     if (tid < 8) { s_source[tid] = p.source[tid]; s_writable[tid] = p.writable[tid]; }
     __syncthreads();
-    const uint32_t total = (uint32_t) range_bricks(p.wrange);
-    const uint32_t k = blockIdx.x * (kMorphWaveThreads / 64) + (uint32_t) (tid >> 6);
-    if (k >= total) return;
-    int bx, by, bz;
-    range_brick(p.wrange, k, bx, by, bz);
-    const size_t b = grid_index(p.bnx, p.bnxy, bx, by, bz);
-    const int y = by * kBrick + (lane & 7), z = bz * kBrick + (lane >> 3);
+    WaveBrick w;
+    if (!wave_brick<kMorphWaveThreads>(p.wrange, p.bnx, p.bnxy, w)) return;
+    const int bx = w.bx, y = w.y, z = w.z;
+    const size_t b = w.b;
     const uint32_t box = row_in_box(p.box, bx, y, z); // (the box lies inside the volume)
     uint2* const bytes = reinterpret_cast<uint2*>(p.labels + b * 512 + (size_t) lane * 8);
     const uint2 old = *bytes;

@@ -11,7 +11,7 @@
 //      all eight within that one segment put the whole brick in the stamp (the set is convex) and end the culling.
 //   3. otherwise every voxel: a lane tests its row against every survivor, ee and de advancing along x by additions. The survivor
 //      words are made wave-uniform first, so a segment is fetched once per wave.
-//   4. the gate, read only by bricks the stroke reaches: the row's 8 stored values against lo .. hi, as k_compete_init reads them.
+//   4. the gate, read only by bricks the stroke reaches: the row's 8 stored values against lo .. hi (row_values, row_gate).
 // With skip == 0 there is neither culling nor verdict: every row is tested against every segment of the stroke.
 // Inside its launch nothing that is read is written: board 0, the data volume, the segments and the runs in; board 1 and its class out.
 //
@@ -25,48 +25,16 @@ namespace {
 constexpr int kPaintThreads = 256; // four bricks to a workgroup, a wave each
 enum : int { PAINT_EVALUATE = 0, PAINT_WHOLE = 1, PAINT_UNTOUCHED = 2 };
 
-// bit i: the stored value of voxel i of the row that starts at element `first` passes the gate (a NaN fails both comparisons)
-template <int FMT> __device__ __forceinline__ uint32_t gate_row(const PaintParams& p, size_t first)
-{
-    uint32_t gate = 0u;
-    if constexpr (FMT == FMT_U8) {
-        const uint2 v = *reinterpret_cast<const uint2*>((const uint8_t*) p.data + first);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const uint32_t c = byte_of(v, i);
-            gate |= (uint32_t) (c >= p.lo_code && c <= p.hi_code) << i;
-        }
-    } else if constexpr (FMT == FMT_U16) {
-        const uint4 v = *reinterpret_cast<const uint4*>((const uint16_t*) p.data + first);
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const uint32_t c = (w[i >> 1] >> (16 * (i & 1))) & 65535u;
-            gate |= (uint32_t) (c >= p.lo_code && c <= p.hi_code) << i;
-        }
-    } else {
-        const float4 a = *reinterpret_cast<const float4*>((const float*) p.data + first);
-        const float4 b = *reinterpret_cast<const float4*>((const float*) p.data + first + 4);
-        const float f[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-        for (int i = 0; i < 8; ++i) gate |= (uint32_t) (f[i] >= p.lo_f && f[i] <= p.hi_f) << i;
-    }
-    return gate;
-}
-
 } // namespace
 
 template <int FMT>
 __global__ __launch_bounds__(kPaintThreads) void k_paint(const PaintParams p)
 {
     const int tid = threadIdx.x, lane = tid & 63;
-    const uint32_t total = (uint32_t) range_bricks(p.range);
-    const uint32_t k = blockIdx.x * (kPaintThreads / 64) + (uint32_t) (tid >> 6);
-    if (k >= total) return;
-    int bx, by, bz;
-    range_brick(p.range, k, bx, by, bz);
-    const size_t b = grid_index(p.bnx, p.bnxy, bx, by, bz);
-    const int x0 = bx * kBrick, y = by * kBrick + (lane & 7), z = bz * kBrick + (lane >> 3);
+    WaveBrick wb;
+    if (!wave_brick<kPaintThreads>(p.range, p.bnx, p.bnxy, wb)) return;
+    const int bx = wb.bx, by = wb.by, bz = wb.bz, x0 = bx * kBrick, y = wb.y, z = wb.z;
+    const size_t b = wb.b;
     const uint32_t vol = row_in_volume(p.dims, bx, y, z);
     const uint32_t S = reinterpret_cast<const uint8_t*>(p.bits + b * 16)[lane];
     unsigned long long* const counts = reinterpret_cast<unsigned long long*>(p.ctl);
@@ -124,7 +92,12 @@ __global__ __launch_bounds__(kPaintThreads) void k_paint(const PaintParams p)
     }
     M &= vol;
     if constexpr (FMT != kPaintNoGate) {
-        if (verdict != PAINT_UNTOUCHED) M &= gate_row<FMT>(p, b * 512 + (size_t) lane * 8);
+        if (verdict != PAINT_UNTOUCHED) {
+            uint32_t c[8];
+            float f[8];
+            row_values<FMT>(p.data, b * 512 + (size_t) lane * 8, c, f);
+            M &= row_gate<FMT>(c, f, p.lo_code, p.hi_code, p.lo_f, p.hi_f);
+        }
     }
 
     const int stamp = wave_sum((int) __popc(M & row_in_box(p.work, bx, y, z)));
@@ -133,10 +106,7 @@ __global__ __launch_bounds__(kPaintThreads) void k_paint(const PaintParams p)
         atomicAdd(counts + (verdict == PAINT_EVALUATE ? (int) MORPH_WINDOWS : (verdict == PAINT_WHOLE ? (int) PAINT_CTL_WHOLE : (int) PAINT_CTL_UNTOUCHED)), 1ull);
     }
 
-    const uint32_t R = paint_apply(p.op, S, M);
-    reinterpret_cast<uint8_t*>(p.bits + b * 16 + 8)[lane] = (uint8_t) R;
-    const bool some = __ballot(R != 0u) != 0ull, all = __ballot(R != vol) == 0ull;
-    if (lane == 0) p.cls[1][b] = !some ? MORPH_EMPTY : (all ? MORPH_FULL : MORPH_MIXED);
+    store_board_row(p.bits + b * 16 + 8, &p.cls[1][b], lane, paint_apply(p.op, S, M), vol);
 }
 
 hipError_t launch_paint(const PaintParams& p, hipStream_t s)

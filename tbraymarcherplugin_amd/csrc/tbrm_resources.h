@@ -509,6 +509,20 @@ int refuse_resident(const tbrm_resources* r);          // slab-resident handles 
 int begin_label_edit(const tbrm_resources* r, const char* no_labels);
 // after label bytes inside the voxels [bbox_min, bbox_max] changed (bbox_max[0] < 0: none did): the touched bricks' label sets, then refresh_live
 int labels_changed(tbrm_resources* r, const int32_t bbox_min[3], const int32_t bbox_max[3]);
+// a refused range lo .. hi of stored values (tbrm_box.h: value_range_refusal) as the call's error; TBRM_OK for one that holds
+int fail_value_range(const tbrm_resources* r, double lo, double hi, bool relative);
+// a scratch buffer of the handle that is only ever grown: a call that needs no more than one before it allocates nothing (what: how
+// tbrm_path_counters [12] names the allocation; null: it is not counted)
+int ensure_bytes(tbrm_resources* r, char*& buffer, size_t& have, size_t bytes, const char* what);
+// the data volume's format as the kernels' FMT
+inline int data_fmt(const tbrm_resources* r) { return r->desc.data_format == TBRM_FMT_G8 ? FMT_U8 : (r->desc.data_format == TBRM_FMT_G16 ? FMT_U16 : FMT_F32); }
+// a tbrm_*_counters getter: N words of the handle
+template <size_t N> int copy_counters(const tbrm_resources* r, uint64_t (tbrm_resources::*which)[N], uint64_t* out)
+{
+    if (!r || !out) return fail(TBRM_ERR_INVALID_ARG, "null argument");
+    for (size_t k = 0; k < N; ++k) out[k] = (r->*which)[k];
+    return TBRM_OK;
+}
 // the start values of a call's control words: zeros, and the bounding box at min_x .. min_x + 5 as (dims, -1)
 inline void ctl_start(int32_t* ctl, int words, int min_x, const int dims[3])
 {

@@ -113,13 +113,10 @@ hipError_t launch_scissors_summary(const ScissorsParams& p, hipStream_t s)
 __global__ __launch_bounds__(kScissorsThreads) void k_scissors(const ScissorsParams p)
 {
     const int tid = threadIdx.x, lane = tid & 63;
-    const uint32_t total = (uint32_t) range_bricks(p.range);
-    const uint32_t k = blockIdx.x * (kScissorsThreads / 64) + (uint32_t) (tid >> 6);
-    if (k >= total) return;
-    int bx, by, bz;
-    range_brick(p.range, k, bx, by, bz);
-    const size_t b = grid_index(p.bnx, p.bnxy, bx, by, bz);
-    const int y = by * kBrick + (lane & 7), z = bz * kBrick + (lane >> 3);
+    WaveBrick wb;
+    if (!wave_brick<kScissorsThreads>(p.range, p.bnx, p.bnxy, wb)) return;
+    const int bx = wb.bx, by = wb.by, bz = wb.bz, y = wb.y, z = wb.z;
+    const size_t b = wb.b;
     const uint32_t vol = row_in_volume(p.dims, bx, y, z);
     const uint32_t S = reinterpret_cast<const uint8_t*>(p.bits + b * 16)[lane];
     unsigned long long* const counts = reinterpret_cast<unsigned long long*>(p.ctl);
@@ -178,10 +175,7 @@ __global__ __launch_bounds__(kScissorsThreads) void k_scissors(const ScissorsPar
     if (lane == 0 && !from_source)
         atomicAdd(counts + (verdict == SCISSORS_PROJECT ? (int) MORPH_WINDOWS : (verdict == SCISSORS_INSIDE ? (int) SCISSORS_CTL_INSIDE : (int) SCISSORS_CTL_OUTSIDE)), 1ull);
 
-    const uint32_t R = from_source ? S : scissors_apply(p.op, S, M, vol);
-    reinterpret_cast<uint8_t*>(p.bits + b * 16 + 8)[lane] = (uint8_t) R;
-    const bool any = __ballot(R != 0u) != 0ull, all = __ballot(R != vol) == 0ull;
-    if (lane == 0) p.cls[1][b] = !any ? MORPH_EMPTY : (all ? MORPH_FULL : MORPH_MIXED);
+    store_board_row(p.bits + b * 16 + 8, &p.cls[1][b], lane, from_source ? S : scissors_apply(p.op, S, M, vol), vol);
 }
 
 hipError_t launch_scissors(const ScissorsParams& p, hipStream_t s)

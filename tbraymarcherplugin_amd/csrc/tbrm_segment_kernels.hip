@@ -38,38 +38,15 @@ __global__ __launch_bounds__(kGrowThreads) void k_grow_candidates(const GrowPara
     const int tid = threadIdx.x, lane = tid & 63;
     if (tid < 8) s_writable[tid] = p.writable[tid];
     __syncthreads();
-    const uint32_t total = (uint32_t) range_bricks(p.range);
-    const uint32_t k = blockIdx.x * (kGrowThreads / 64) + (uint32_t) (tid >> 6);
-    if (k >= total) return;
-    int bx, by, bz;
-    range_brick(p.range, k, bx, by, bz);
-    const size_t b = grid_index(p.bnx, p.bnxy, bx, by, bz);
-    const size_t first = b * 512 + (size_t) lane * 8;
+    WaveBrick w;
+    if (!wave_brick<kGrowThreads>(p.range, p.bnx, p.bnxy, w)) return;
+    const size_t b = w.b, first = b * 512 + (size_t) lane * 8;
 
-    const uint32_t inside = row_in_box(p.box, bx, by * kBrick + (lane & 7), bz * kBrick + (lane >> 3));
-    uint32_t in_range = 0u;
-    if constexpr (FMT == FMT_U8) {
-        const uint2 v = *reinterpret_cast<const uint2*>((const uint8_t*) p.data + first);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const uint32_t c = byte_of(v, i);
-            in_range |= (uint32_t) (c >= p.lo_code && c <= p.hi_code) << i;
-        }
-    } else if constexpr (FMT == FMT_U16) {
-        const uint4 v = *reinterpret_cast<const uint4*>((const uint16_t*) p.data + first);
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const uint32_t c = (w[i >> 1] >> (16 * (i & 1))) & 65535u;
-            in_range |= (uint32_t) (c >= p.lo_code && c <= p.hi_code) << i;
-        }
-    } else {
-        const float4 a = *reinterpret_cast<const float4*>((const float*) p.data + first);
-        const float4 c = *reinterpret_cast<const float4*>((const float*) p.data + first + 4);
-        const float f[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
-#pragma unroll
-        for (int i = 0; i < 8; ++i) in_range |= (uint32_t) (f[i] >= p.lo_f && f[i] <= p.hi_f) << i; // (a NaN fails both)
-    }
+    const uint32_t inside = row_in_box(p.box, w.bx, w.y, w.z);
+    uint32_t c[8];
+    float f[8];
+    row_values<FMT>(p.data, first, c, f);
+    const uint32_t in_range = row_gate<FMT>(c, f, p.lo_code, p.hi_code, p.lo_f, p.hi_f);
     uint32_t may = 0u; // bit i: the voxel's label may be grown over
     if (p.labels) may = row_in_mask(*reinterpret_cast<const uint2*>(p.labels + first), s_writable);
     else may = (s_writable[0] & 1u) ? 0xffu : 0u;
@@ -297,12 +274,9 @@ hipError_t launch_grow_measure(const GrowParams& p, hipStream_t s)
 __global__ __launch_bounds__(kGrowThreads) void k_grow_write(const GrowParams p, const BrickRange w)
 {
     const int tid = threadIdx.x, lane = tid & 63;
-    const uint32_t total = (uint32_t) range_bricks(w);
-    const uint32_t k = blockIdx.x * (kGrowThreads / 64) + (uint32_t) (tid >> 6);
-    if (k >= total) return;
-    int bx, by, bz;
-    range_brick(w, k, bx, by, bz);
-    const size_t b = grid_index(p.bnx, p.bnxy, bx, by, bz);
+    WaveBrick wb;
+    if (!wave_brick<kGrowThreads>(w, p.bnx, p.bnxy, wb)) return;
+    const size_t b = wb.b;
     const uint32_t vis = reinterpret_cast<const uint8_t*>(p.bits + b * 16)[64 + lane];
     if (__ballot(vis != 0u) == 0ull) return;
     int changed = 0;

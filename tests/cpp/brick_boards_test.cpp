@@ -219,6 +219,17 @@ int main()
                 }
         }
 
+    // ---- the class of a board, a range of stored values ---------------------------------------------------------------------------------
+    CHECK(board_class(false, false) == MORPH_EMPTY && board_class(false, true) == MORPH_EMPTY); // (no bit: empty even where no bit is in the volume)
+    CHECK(board_class(true, true) == MORPH_FULL && board_class(true, false) == MORPH_MIXED);
+    const double nan = std::nan(""), inf = HUGE_VAL;
+    CHECK(value_range_refusal(3, 3, false, 0, 255) == RANGE_OK && value_range_refusal(0, 255, false, 0, 255) == RANGE_OK);
+    CHECK(value_range_refusal(4, 3, false, 0, 255) == RANGE_ORDER && value_range_refusal(nan, 3, false, 0, 255) == RANGE_ORDER && value_range_refusal(3, nan, true, 0, 0) == RANGE_ORDER);
+    CHECK(value_range_refusal(-1, 3, false, 0, 255) == RANGE_CODES && value_range_refusal(0, 256, false, 0, 255) == RANGE_CODES && value_range_refusal(1.5, 3, false, 0, 255) == RANGE_CODES);
+    CHECK(value_range_refusal(-255, 0, false, -255, 255) == RANGE_OK && value_range_refusal(-256, 0, false, -255, 255) == RANGE_CODES);
+    CHECK(value_range_refusal(-inf, inf, false, 0, 65535) == RANGE_CODES && value_range_refusal(0, inf, true, 0, 0) == RANGE_FLOAT && value_range_refusal(-inf, 0, true, 0, 0) == RANGE_FLOAT);
+    CHECK(value_range_refusal(-1e30, 1e30, true, 0, 0) == RANGE_OK && value_range_refusal(0, 1e39, true, 0, 0) == RANGE_FLOAT && value_range_refusal(-1.5, 2.25, true, 0, 0) == RANGE_OK);
+
     std::printf("failures=%d\n", failures);
     return failures != 0;
 }
